@@ -16,7 +16,11 @@ outputs -> (N>1) one RCCL all-gather of the per-image detections.
 Weights are random-init (no checkpoints offline), data synthetic; images are
 sharded data-parallel (weak scaling: 8 images per GPU per step).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+Prints ONE JSON line (rank 0) with the driver's fields (metric, value, unit, higher_is_better,
+dtype, ms_per_step = the wall time of one timed step).  A plain run sets up, warms up, times the
+K steps and prints; --dump-outputs DIR also writes the last timed step's detections as
+DIR/{dets,labels,num_dets}.npy (float32; --config r50-train: its losses and a seeded parameter
+sample).  With --full the line also carries (null otherwise)
   roofline     -- the row-max kernel over the head logits (k_rowmax_nhwc for this channels-last
                   network, HBM bound).  `achieved` = the bytes THAT kernel moves per launch (class
                   + IoU logits read once, row maxima written: 66 124 800 B per image; the box
@@ -36,6 +40,10 @@ Prints ONE JSON line (rank 0) with the driver's fields plus
   pipeline     -- image -> result, the reference's fps definition (MODEL_ZOO.md:31): uint8 HWC BGR
                   images resident on the device -> ia_image_transform -> network -> detections ->
                   D2H + bbox2result, img/s (rank 0, N=1 only).
+  multi_rank   -- (N > 1) every rank's own img/s, the all-gather's time and the rank interleave
+                  checked against the reference's collect_results.
+  other_configs-- BASELINE configs 1 / 3 / 4 through the same path, a few steps each.
+In every run:
   rccl_ranks   -- the size of the process group as the collective library itself counts it
                   (all-reduce of ones); n_gpus comes from the group, not from --gpus.
 --config r101-bf16 / x101-64x4d run BASELINE configs 3 / 4 through the same path (sub-records
@@ -877,7 +885,7 @@ OTHER_CONFIGS = (
 
 
 def other_configs_record(device, budget_s=60.0):
-    """BASELINE configs 1, 3, 4 as bounded sub-records of the default run: the
+    """BASELINE configs 1, 3, 4 as bounded sub-records of the --full run: the
     same whole inference path (network -> ops.get_bboxes) on one GPU, a few steps each between a
     device synchronisation on both sides; config 3 also carries the bf16 3x3 kernel's rate."""
     out, t_start = {}, time.time()
@@ -936,6 +944,30 @@ def stage_traffic():
         return None
 
 
+def dump_detections(path, dets, labels, num):
+    """--dump-outputs: the detections of the last step as the caller receives them (rank 0: every
+    rank's images after the all-gather).  Rows past an image's count are not written by the kernels,
+    so they are zeroed (label -1) here: the files compare bit for bit between runs and builds."""
+    os.makedirs(path, exist_ok=True)
+    n = num.cpu().numpy().astype(np.int64)
+    valid = np.arange(dets.shape[1])[None, :] < n[:, None]
+    d = np.where(valid[..., None], dets.float().cpu().numpy(), 0).astype(np.float32)
+    lab = np.where(valid, labels.cpu().numpy(), -1).astype(np.float32)
+    for name, a in (('dets', d), ('labels', lab), ('num_dets', n.astype(np.float32))):
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def dump_train(path, log, model, sample=65536):
+    """--dump-outputs for --config r50-train: the last iteration's loss values and a fixed, seeded
+    sample of the parameters it updated (float32; parameters in module order)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'losses.npy'), np.array([float(v) for v in log.values()], np.float64))
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    idx = np.sort(np.random.RandomState(0).choice(flat.numel(), min(sample, flat.numel()), replace=False))
+    np.save(os.path.join(path, 'params_sample.npy'), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
+
+
 def main_train(args, cfg_name, world, rank, local_rank, device, sync, barrier, rccl_ranks,
                rank_devices, launched_by):
     """--config r50-train: BASELINE config 5 as the measured job -- whole training iterations
@@ -952,6 +984,8 @@ def main_train(args, cfg_name, world, rank, local_rank, device, sync, barrier, r
     def step():
         last['log'] = train_step(net, opt, img, ms, gtb, gtl, grad_clip=clip)
     elapsed = timed_region(step, args.steps, args.warmup, world, sync, barrier, device)
+    if rank == 0 and args.dump_outputs:
+        dump_train(args.dump_outputs, last['log'], model)
     if rank == 0:
         print(json.dumps({
             'metric': 'training images/sec at 1333x800, IoU-aware RetinaNet R-50-FPN',
@@ -983,6 +1017,13 @@ def main():
     ap.add_argument('--config', choices=sorted(CONFIGS), default='r50',
                     help='r50 = BASELINE config 2 (the headline); r101-bf16 = config 3; '
                          'x101-64x4d = config 4')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: roofline figures, the live PMC traffic, '
+                         'cpu_baseline, pipeline, train, other_configs and the N > 1 per-rank / '
+                         'interleave record (the --no-* options below switch parts of it off)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy '
+                         '(float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-live-pmc', action='store_true',
                     help='do not measure the decode stage HBM traffic with rocprofv3 child processes')
@@ -992,7 +1033,7 @@ def main():
     ap.add_argument('--no-train', action='store_true', help='skip the training sub-record')
     ap.add_argument('--no-pipeline', action='store_true', help='skip the image -> result sub-record')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the BASELINE config 1 / 3 / 4 sub-records of the default run')
+                    help='skip the BASELINE config 1 / 3 / 4 sub-records of the --full run')
     ap.add_argument('--train-find', action='store_true',
                     help='MIOpen find mode for the training sub-record (adds ~8 minutes)')
     ap.add_argument('--miopen-find', action='store_true',
@@ -1078,6 +1119,8 @@ def main():
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
+        if rank == 0 and args.dump_outputs:
+            dump_detections(args.dump_outputs, *stepper.last[:3])
         if not ok:
             raise SystemExit(1)
         return
@@ -1115,15 +1158,17 @@ def main():
     def step():
         stepper.step(timed=True)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         stepper.stage_events(args.steps, skip=args.warmup)
     info = {}
     elapsed = timed_region(step, args.steps, args.warmup, world, sync, barrier, reduce_device, drain=stepper.drain,
                            info=info)
-    in_step = stepper.stage_times_ms() if rank == 0 else []
+    in_step = stepper.stage_times_ms() if rank == 0 and args.full else []
     host_results = stepper.results
+    if rank == 0 and args.dump_outputs:
+        dump_detections(args.dump_outputs, *stepper.last[:3])
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         # what a scaling run is read by: every rank's own clock, the exchange step, the rank interleave
         clocks = [None] * world
         dist.all_gather_object(clocks, (rank, info['local_busy_s'], info['local_elapsed_s']))
@@ -1132,21 +1177,10 @@ def main():
                  'exchange': stepper.exchange_record(args.steps),
                  'interleave_equals_zip_part_list': bool(stepper.interleave_matches_part_list())}
 
-    wino = wino_roofline(stepper) if rank == 0 and dtype == torch.float32 else None
+    wino = wino_roofline(stepper) if args.full and rank == 0 and dtype == torch.float32 else None
     if rank == 0:
         esz = 4 if dtype == torch.float32 else 2
         n_img = batch * world * args.steps
-        ms_stage, ms_rowmax, nhwc = decode_stage_roofline(stepper)
-        tname = 'float' if esz == 4 else 'unsigned short'
-        rm_kernel = ('ia::k_rowmax_nhwc<%s, %d>' % (tname, 80 * esz // 16) if nhwc
-                     else 'ia::k_rowmax<%s>' % tname)
-        rowmax_bytes = ((64512000 + 806400) * esz // 4 + 806400) * batch
-        stage_bytes = HEAD_BYTES_PER_IMAGE * esz // 4 * batch
-        achieved = rowmax_bytes / (ms_rowmax * 1e-3) / 1e9
-        b2b = stage_bytes / (ms_stage * 1e-3) / 1e9
-        # the headline roofline figure: the stage's average duration INSIDE the timed steps
-        ms_in_step = sum(in_step) / len(in_step) if in_step else ms_stage
-        stage = stage_bytes / (ms_in_step * 1e-3) / 1e9
         out = {
             'metric': 'images/sec at 1333x800, IoU-aware RetinaNet R-50-FPN' if headline else
                       'images/sec at 1333x800, IoU-aware RetinaNet (%s)' % args.config,
@@ -1175,85 +1209,91 @@ def main():
                                         'dets_image0': int(sum(r.shape[0] for r in host_results[0])) if host_results else 0},
                        'global_batch': batch * world, 'parallelism': 'dp%d' % world,
                        'dets_per_image': int(stepper.last[2].float().mean().item())},
+            'roofline': None, 'cpu_baseline': None, 'pipeline': None, 'train': None,
+            'other_configs': None,
+        }
+        if args.full:
+            ms_stage, ms_rowmax, nhwc = decode_stage_roofline(stepper)
+            tname = 'float' if esz == 4 else 'unsigned short'
+            rm_kernel = ('ia::k_rowmax_nhwc<%s, %d>' % (tname, 80 * esz // 16) if nhwc
+                         else 'ia::k_rowmax<%s>' % tname)
+            rowmax_bytes = ((64512000 + 806400) * esz // 4 + 806400) * batch
+            stage_bytes = HEAD_BYTES_PER_IMAGE * esz // 4 * batch
+            achieved = rowmax_bytes / (ms_rowmax * 1e-3) / 1e9
+            b2b = stage_bytes / (ms_stage * 1e-3) / 1e9
+            # the headline roofline figure: the stage's average duration INSIDE the timed steps
+            ms_in_step = sum(in_step) / len(in_step) if in_step else ms_stage
+            stage = stage_bytes / (ms_in_step * 1e-3) / 1e9
             # SURVEY 8(d)'s unit: the decode stage (row-max + top-k + gather), cls + reg + iou
             # logits read once = 68 544 000 B per fp32 image; the row-max kernel alone below it
-            'roofline': {'bound': 'hbm',
-                         'kernel': 'decode stage: k_rowmax + k_sel_filter + k_sel_final + k_gather '
-                                   '(SURVEY 8d unit)',
-                         'timing': ('HIP events recorded by the library on the launch stream in front '
-                                    'of the stage\'s first launch and behind its last one, in every '
-                                    'step of the timed region (ia_profile_stage_events); average '
-                                    'over the %d timed steps' % len(in_step)) if in_step else
-                                   'back-to-back passes after the timed region (see back_to_back)',
-                         'achieved': round(stage, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(stage / HBM_PEAK_GBS, 4),
-                         'in_step_ms': {'mean': round(ms_in_step, 4),
-                                        'min': round(min(in_step), 4), 'max': round(max(in_step), 4),
-                                        'steps': len(in_step)} if in_step else None,
-                         'back_to_back': {'timing': 'HIP events around 10 back-to-back passes of the '
-                                                    'stage after the timed region, best of 5 '
-                                                    '(inter-kernel gaps included)',
-                                          'avg_launch_ms': round(ms_stage, 4),
-                                          'achieved': round(b2b, 1),
-                                          'frac': round(b2b / HBM_PEAK_GBS, 4)},
-                         'traffic': stage_traffic() if headline else None,
-                         'traffic_source': 'profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, '
-                                           'separate passes, same batch-8 launches)' % PMC_PROFILE,
-                         'bytes_per_launch': stage_bytes, 'avg_launch_ms': round(ms_in_step, 4),
-                         'rowmax': {'kernel': rm_kernel.split('::')[1].split('<')[0],
-                                    'bytes_per_launch': rowmax_bytes,
-                                    'avg_launch_ms': round(ms_rowmax, 4),
-                                    'achieved': round(achieved, 1),
-                                    'frac': round(achieved / HBM_PEAK_GBS, 4),
-                                    'traffic': rowmax_traffic(rm_kernel) if headline else None},
-                         'wino': wino},
-        }
-        # (with the CPU baseline, i.e. in the full default run only: the profiling scripts under tools/
-        # pass --no-cpu-baseline and run this file under rocprofv3 themselves -- never nest profilers)
-        under_profiler = any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)
-        if world == 1 and headline and not args.no_live_pmc and not args.no_cpu_baseline and not under_profiler:
-            live = live_stage_traffic()
-            if live is not None:
-                rf = out['roofline']
-                rf['traffic_committed_profile'] = rf['traffic']
-                rf['traffic'] = live['stage']
-                rf['traffic_source'] = ('measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child '
-                                        'processes (separate passes, --kernel-trace only) on the same batch-8 '
-                                        'launches (tools/time_head.py), 2 x FETCH_SIZE + WRITE_SIZE')
-                rf['traffic_kernels'] = live['kernels']
-                if live['rowmax'] is not None:
-                    rf['rowmax']['traffic'] = live['rowmax']
-            else:
-                out['roofline']['traffic_source'] += ' -- the live rocprofv3 pass of this run was not available'
-        if world == 1 and headline and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline()
-        else:
-            out['cpu_baseline'] = None
-        if world == 1 and not args.no_pipeline:
-            try:
-                out['pipeline'] = pipeline_record(model, device, batch)
-            except Exception as exc:
-                out['pipeline'] = {'error': '%s: %s' % (type(exc).__name__, exc)}
-        else:
-            out['pipeline'] = None
-        freed = False
-        if world == 1 and headline and not args.no_train:
-            del stepper, model, imgs
-            freed = True
-            torch.cuda.empty_cache()
-            try:
-                out['train'] = train_record(device, find=args.train_find)
-            except Exception as exc:                     # the headline number must still print
-                out['train'] = {'error': '%s: %s' % (type(exc).__name__, exc)}
-        else:
-            out['train'] = None
-        if world == 1 and headline and not args.no_other_configs:
-            if not freed:
+            out['roofline'] = {'bound': 'hbm',
+                              'kernel': 'decode stage: k_rowmax + k_sel_filter + k_sel_final + k_gather '
+                                        '(SURVEY 8d unit)',
+                              'timing': ('HIP events recorded by the library on the launch stream in front '
+                                         'of the stage\'s first launch and behind its last one, in every '
+                                         'step of the timed region (ia_profile_stage_events); average '
+                                         'over the %d timed steps' % len(in_step)) if in_step else
+                                        'back-to-back passes after the timed region (see back_to_back)',
+                              'achieved': round(stage, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                              'frac': round(stage / HBM_PEAK_GBS, 4),
+                              'in_step_ms': {'mean': round(ms_in_step, 4),
+                                             'min': round(min(in_step), 4), 'max': round(max(in_step), 4),
+                                             'steps': len(in_step)} if in_step else None,
+                              'back_to_back': {'timing': 'HIP events around 10 back-to-back passes of the '
+                                                         'stage after the timed region, best of 5 '
+                                                         '(inter-kernel gaps included)',
+                                               'avg_launch_ms': round(ms_stage, 4),
+                                               'achieved': round(b2b, 1),
+                                               'frac': round(b2b / HBM_PEAK_GBS, 4)},
+                              'traffic': stage_traffic() if headline else None,
+                              'traffic_source': 'profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, '
+                                                'separate passes, same batch-8 launches)' % PMC_PROFILE,
+                              'bytes_per_launch': stage_bytes, 'avg_launch_ms': round(ms_in_step, 4),
+                              'rowmax': {'kernel': rm_kernel.split('::')[1].split('<')[0],
+                                         'bytes_per_launch': rowmax_bytes,
+                                         'avg_launch_ms': round(ms_rowmax, 4),
+                                         'achieved': round(achieved, 1),
+                                         'frac': round(achieved / HBM_PEAK_GBS, 4),
+                                         'traffic': rowmax_traffic(rm_kernel) if headline else None},
+                              'wino': wino}
+            # (with the CPU baseline, i.e. in a --full run only: the profiling scripts under tools/
+            # pass --no-cpu-baseline and run this file under rocprofv3 themselves -- never nest profilers)
+            under_profiler = any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)
+            if world == 1 and headline and not args.no_live_pmc and not args.no_cpu_baseline and not under_profiler:
+                live = live_stage_traffic()
+                if live is not None:
+                    rf = out['roofline']
+                    rf['traffic_committed_profile'] = rf['traffic']
+                    rf['traffic'] = live['stage']
+                    rf['traffic_source'] = ('measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child '
+                                            'processes (separate passes, --kernel-trace only) on the same batch-8 '
+                                            'launches (tools/time_head.py), 2 x FETCH_SIZE + WRITE_SIZE')
+                    rf['traffic_kernels'] = live['kernels']
+                    if live['rowmax'] is not None:
+                        rf['rowmax']['traffic'] = live['rowmax']
+                else:
+                    out['roofline']['traffic_source'] += ' -- the live rocprofv3 pass of this run was not available'
+            if world == 1 and headline and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline()
+            if world == 1 and not args.no_pipeline:
+                try:
+                    out['pipeline'] = pipeline_record(model, device, batch)
+                except Exception as exc:
+                    out['pipeline'] = {'error': '%s: %s' % (type(exc).__name__, exc)}
+            freed = False
+            if world == 1 and headline and not args.no_train:
                 del stepper, model, imgs
-            torch.cuda.empty_cache()
-            out['other_configs'] = other_configs_record(device)
-        else:
-            out['other_configs'] = None
+                freed = True
+                torch.cuda.empty_cache()
+                try:
+                    out['train'] = train_record(device, find=args.train_find)
+                except Exception as exc:                     # the headline number must still print
+                    out['train'] = {'error': '%s: %s' % (type(exc).__name__, exc)}
+            if world == 1 and headline and not args.no_other_configs:
+                if not freed:
+                    del stepper, model, imgs
+                torch.cuda.empty_cache()
+                out['other_configs'] = other_configs_record(device)
         print(json.dumps(out))
     if world > 1:
         barrier()

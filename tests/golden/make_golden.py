@@ -998,9 +998,78 @@ def gen_model():
     print('wrote state_dict_keys.json', {k: len(v) for k, v in out.items()})
 
 
+def gen_ref_binaries():
+    """the reference's compiled NMS (nms_cpu.cpp) and Cython soft-NMS (soft_nms_cpu.pyx) on the
+    inputs tests/test_oracle_golden.py / test_oracle_softnms.py draw from their seeds"""
+    import build_ref
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    from test_oracle_softnms import _rand_dets
+    assert build_ref.build() and build_ref.build_soft()
+    nms_ref, soft_ref = build_ref.load(), build_ref.load_soft()
+    out = {}
+    rs = np.random.RandomState(5)
+    for n in (1, 17, 300, 1500):
+        x1, y1 = rs.uniform(0, 400, n), rs.uniform(0, 400, n)
+        dets = np.stack([x1, y1, x1 + rs.uniform(4, 150, n), y1 + rs.uniform(4, 150, n),
+                         rs.permutation(n) / n], 1).astype(np.float32)
+        out['dets_%d' % n] = dets
+        out['keep_%d' % n] = nms_ref.nms(torch.from_numpy(dets), 0.5).numpy()
+    save('nms_ref_binary', **out)
+    out = {}
+    rs = np.random.RandomState(5)
+    for trial in range(120):
+        n = int(rs.randint(1, 400))
+        d = _rand_dets(rs, n, float(rs.choice([50, 150, 600])), ties=(trial % 3 == 0))
+        for method, code in (('linear', 1), ('gaussian', 2)):
+            thr = float(rs.choice([0.3, 0.5, 0.7]))
+            sigma = float(rs.choice([0.3, 0.5, 1.0]))
+            ms = float(rs.choice([1e-3, 0.05, 0.2]))
+            a, ai = soft_ref.soft_nms_cpu(d.copy(), thr, method=code, sigma=sigma, min_score=ms)
+            key = '%d_%s' % (trial, method)
+            out['cfg_' + key] = np.array([thr, sigma, ms], np.float64)
+            out['new_dets_' + key] = a.astype(np.float32)
+            out['inds_' + key] = np.asarray(ai, np.int32)
+    save('soft_nms_ref_module', **out)
+
+
+def gen_ref_configs():
+    """the settings of the reference's four configs (top-level names -> values, JSON) and the head
+    outputs of the reference R-50 detector built from its config, weights by synth.e2e_fill_state(1),
+    on a seeded 64 x 64 image"""
+    import glob
+    import json
+    from mmdet.models import build_detector
+
+    def plain(v):
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple, range)):
+            return [plain(x) for x in v]
+        return v
+    cfgs = {}
+    for f in sorted(glob.glob(ref_shim.REF + '/configs/iou_aware_single_stage_detector/*.py')):
+        cfg = ref_shim.load_config(f)
+        cfgs[os.path.basename(f)[:-3]] = plain(cfg)
+    with open(os.path.join(HERE, 'ref_configs.json'), 'w') as fh:
+        json.dump(cfgs, fh, indent=1, sort_keys=True)
+    print('wrote ref_configs.json', sorted(cfgs))
+    rcfg = ref_shim.load_config(ref_shim.REF + '/configs/iou_aware_single_stage_detector/'
+                                'iou_aware_retinanet_r50_fpn_1x_4gpu.py')
+    rcfg.model['pretrained'] = None
+    ref = build_detector(rcfg.model, train_cfg=rcfg.train_cfg, test_cfg=rcfg.test_cfg).eval()
+    state = ref.state_dict()
+    synth.e2e_fill_state(state, 1)
+    ref.load_state_dict(state)
+    x = np.random.RandomState(2).standard_normal((1, 3, 64, 64)).astype(np.float32)
+    with torch.no_grad():
+        outs = ref.bbox_head(ref.extract_feat(torch.from_numpy(x)))
+    save('ref_r50_forward', x=x, **{'%s_%d' % (kind, l): t.numpy()
+                                    for kind, ts in zip(('cls', 'reg', 'iou'), outs) for l, t in enumerate(ts)})
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['anchors', 'delta2bbox', 'nms', 'get_bboxes', 'soft_nms', 'losses', 'losses_balanced', 'model', 'e2e', 'focal_op', 'train_e2e', 'e2e_backbones', 'mnms_quirk', 'get_bboxes_vecscale', 'nms_f64', 'mnms_big',
-                             'losses_mixed_pad', 'get_bboxes_softmax']
+                             'losses_mixed_pad', 'get_bboxes_softmax', 'ref_binaries']
     for w in which:
         if ':' in w:                          # e.g. e2e_backbones:r101_full,x101_64x4d_full
             w, only = w.split(':')

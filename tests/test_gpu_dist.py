@@ -192,7 +192,7 @@ def test_bench_gpus_8_rehearsal_on_one_gpu():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--rehearsal', '--steps', '3',
-                        '--warmup', '1', '--no-cpu-baseline', '--no-live-pmc', '--no-train', '--no-pipeline',
+                        '--warmup', '1', '--full', '--no-cpu-baseline', '--no-live-pmc', '--no-train', '--no-pipeline',
                         '--no-other-configs'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=850)
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
     assert p.returncode == 0 and lines, p.stderr.decode()[-3000:]

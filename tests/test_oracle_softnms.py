@@ -1,13 +1,12 @@
 """CPU: the soft-NMS restatement (oracle/iouaware_oracle_softnms.c) against
   * tests/golden/soft_nms.npz, captured from the imported reference (nms_wrapper.soft_nms over the
     reference's own Cython module; get_bboxes with test_cfg.nms.type='soft_nms'),
-  * the reference module itself (oracle/_ref_local/soft_nms_cpu.so, built by oracle/build_ref.py from
-    mmdet/ops/nms/src/soft_nms_cpu.pyx), on random and tie-heavy inputs: bit for bit.
+  * the reference module itself (built by oracle/build_ref.py from mmdet/ops/nms/src/soft_nms_cpu.pyx), on
+    random and tie-heavy inputs, through its outputs recorded in tests/golden/soft_nms_ref_module.npz: bit for bit.
 """
 import os
 
 import numpy as np
-import pytest
 
 import synth
 
@@ -61,23 +60,23 @@ def _rand_dets(rs, n, span, ties):
     return np.concatenate([xy, xy + wh, s[:, None]], 1).astype(np.float32)
 
 
-def test_soft_nms_matches_real_reference_module(oracle_lib):
-    import build_ref
-    ref = build_ref.load_soft()
-    if ref is None:
-        pytest.skip('oracle/_ref_local/soft_nms_cpu.so not built (reference tree absent)')
+def test_soft_nms_matches_real_reference_module(oracle_lib, golden_dir):
+    """against the reference's own Cython module on these inputs (tests/golden/soft_nms_ref_module.npz,
+    make_golden.py ref_binaries)"""
+    f = np.load(os.path.join(golden_dir, 'soft_nms_ref_module.npz'))
     rs = np.random.RandomState(5)
     for trial in range(120):
         n = int(rs.randint(1, 400))
         d = _rand_dets(rs, n, float(rs.choice([50, 150, 600])), ties=(trial % 3 == 0))
-        for method, code in (('linear', 1), ('gaussian', 2)):
+        for method in ('linear', 'gaussian'):
             thr = float(rs.choice([0.3, 0.5, 0.7]))
             sigma = float(rs.choice([0.3, 0.5, 1.0]))
             ms = float(rs.choice([1e-3, 0.05, 0.2]))
-            a, ai = ref.soft_nms_cpu(d.copy(), thr, method=code, sigma=sigma, min_score=ms)
+            key = '%d_%s' % (trial, method)
+            assert np.array_equal(f['cfg_' + key], [thr, sigma, ms]), 'inputs drifted'
             b, bi = oracle_lib.soft_nms(d, thr, method, sigma, ms)
-            assert np.array_equal(ai, bi), (trial, method)
-            assert np.array_equal(a.astype(np.float32), b), (trial, method)
+            assert np.array_equal(f['inds_' + key], bi), (trial, method)
+            assert np.array_equal(f['new_dets_' + key], b), (trial, method)
 
 
 def test_exp_f64_is_faithful(oracle_lib):

@@ -26,5 +26,5 @@ cp $ROOT/gpurun_out/profile/r101-bf16_step_summary.txt $OUT/config3_r101_bf16_b1
 bash $ROOT/tools/profile_x101.sh > $OUT/profile_x101.log 2>&1
 cp $ROOT/gpurun_out/profile/x101_step_summary.txt $OUT/x101_64x4d_third_step_summary.txt 2>/dev/null
 python $ROOT/tools/try_configs.py > $OUT/other_configs.txt 2>&1
-cd $ROOT && python bench.py > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+cd $ROOT && python bench.py --full > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
 tail -3 $OUT/other_configs.txt; cut -c1-400 $OUT/bench_default_run.json
