@@ -733,6 +733,70 @@ size_t ia_conv3x3_bf16_packed_bytes(int cin, int cout, int groups);
 int ia_conv3x3_bf16_pack(const void *w, int cin, int cout, int groups, void *wp, void *stream);
 int ia_conv3x3_bf16_levels(const ia_conv3x3_desc *d, const void *wp, const float *bias, int relu, void *stream);
 
+/* ------------------------------------------------------------------ IoU-aware FCOS
+ * GroupNorm + ReLU of the FCOS head towers (reference mmdet/models/anchor_heads/
+ * iou_aware_fcos_head.py:41-62: ConvModule(3x3, no bias, GN(32), ReLU); torch nn.GroupNorm:
+ * biased variance, y = (x - mean) / sqrt(var + eps) * gamma + beta) at inference, on the
+ * activations the Winograd output transform writes: per level x[l] (batch, H_l, W_l, channels)
+ * fp32 channels-last (both towers side by side: channels = 2 * 256, groups = 2 * 32, gamma / beta
+ * of the two towers concatenated).  Statistics per (level, image, group) over channels / groups
+ * channels x H_l x W_l values.
+ *   ia_groupnorm_stats: per workgroup (level, image, chunk of IA_GN_CHUNK pixels) fp64 sums and
+ *     sums of squares per group, written to the workspace (no atomics).
+ *   ia_groupnorm_apply: every workgroup sums its (level, image)'s partials in index order (fp64:
+ *     mean, var = E[x^2] - mean^2 stays accurate for |mean| >> std), s = gamma * rstd,
+ *     t = beta - mean * s per channel, then x = relu?(x * s + t) in place, 16-byte accesses.
+ * Same bits from run to run; an image's result does not depend on the other images / levels of
+ * the launch.  channels: 4 * 2^k, <= 1024; groups divides channels, channels / groups % 4 == 0;
+ * x[l] 16-byte aligned.  Pairs on one stream, the workspace untouched in between.            */
+#define IA_GN_CHUNK 256
+size_t ia_groupnorm_workspace_bytes(const ia_wino_geom *g, int channels, int groups);
+int ia_groupnorm_stats(const ia_wino_geom *g, const float *const *x, int channels, int groups,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int groups,
+                       const float *gamma, const float *beta, float eps, int relu,
+                       const void *workspace, size_t workspace_bytes, void *stream);
+/* The FCOS regression epilogue bbox_pred = exp(scale_l * x) (iou_aware_fcos_head.py:105) in place
+ * on per-level (batch, H_l, W_l, channels) fp32 tensors (channels % 4 == 0, 16-byte aligned);
+ * scales: (num_levels) fp32 device array (the head's Scale parameters).                      */
+int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, const float *scales,
+                        void *stream);
+
+/* Point head (IoU-aware FCOS) post-processing: get_bboxes / get_bboxes_single of
+ * iou_aware_fcos_head.py:248-370.  One point per position (no anchors), stored like the anchor
+ * head's outputs with A = 1: cls (B, C, H, W), reg (B, 4, H, W) = the already exponentiated
+ * distances (left, top, right, bottom), iou (B, 1, H, W); NCHW or channels-last (layout), fp32.
+ *   score_c = powf(sigmoid(cls_c), score_alpha) * powf(sigmoid(iou), 1 - score_alpha)
+ *     (:326-331, alpha = 0.3; centerness is not used, as in the reference);
+ *   per level the row max over classes and the top nms_pre (score desc, index asc) (:335-345);
+ *   point (x * stride + stride / 2, y * stride + stride / 2) (:379-388), distance2bbox clamped to
+ *   [0, w-1] x [0, h-1] (mmdet/core/bbox/transforms.py:169-190), true division by scale_factor;
+ *   the batched NMS of ia_get_bboxes (lazy: candidates >= 0, 0 = default; < 0: complete path).
+ * Outputs and workspace contract as ia_get_bboxes (rows = candidate row ids; the candidate's
+ * point index inside its level is cand_idx[row]).  ia_point_decode_stage: the decode stage only;
+ * ia_point_workspace_layout: where it leaves rowmax, cand_idx, boxes, scores_t, keep_count,
+ * keep_rows, best_score (offsets as ia_get_bboxes_workspace_layout).                        */
+typedef struct ia_point_head_geom {
+    int32_t num_levels;                 /* L <= IA_MAX_LEVELS */
+    int32_t num_classes;                /* C (80) */
+    int32_t nms_pre;                    /* <= 0: no per-level top-k */
+    int32_t H[IA_MAX_LEVELS];
+    int32_t W[IA_MAX_LEVELS];
+    int32_t stride[IA_MAX_LEVELS];
+    int32_t layout;                     /* IA_LAYOUT_* */
+    float score_alpha;                  /* in [0, 1] */
+} ia_point_head_geom;
+size_t ia_point_workspace_bytes(const ia_point_head_geom *g, int batch);
+int ia_point_workspace_layout(const ia_point_head_geom *g, int batch, size_t offsets[8]);
+int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                          const float *img_hw, const float *scale_factor, int rescale,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                        const float *img_hw, const float *scale_factor, int rescale,
+                        float score_thr, float iou_thr, int max_per_img, int candidates,
+                        void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                        int32_t *rows, int32_t *num, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

@@ -439,6 +439,94 @@ int ia_get_bboxes_lazy(const ia_head_geom *g, const ia_level_ptrs *p, int batch,
                            num, stream);
 }
 
+// point head (IoU-aware FCOS): the ia_get_bboxes workspace of the A = 1 geometry, its own decode
+// stage, the shared NMS stages
+size_t ia_point_workspace_bytes(const ia_point_head_geom *g, int batch)
+{
+    ia_head_geom hg;
+    if (ia::point_head_geom(g, hg)) return 0;
+    return ia_get_bboxes_workspace_bytes(&hg, batch);
+}
+
+int ia_point_workspace_layout(const ia_point_head_geom *g, int batch, size_t offsets[8])
+{
+    ia_head_geom hg;
+    int rc = ia::point_head_geom(g, hg);
+    if (rc) return rc;
+    return ia_get_bboxes_workspace_layout(&hg, batch, offsets);
+}
+
+static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                             const float *img_hw, const float *scale_factor, int rescale,
+                             void *workspace, size_t workspace_bytes, hipStream_t s,
+                             ia::WsLayout &w, ia::LevelTable &t)
+{
+    ia_head_geom hg;
+    int rc = ia::point_head_geom(g, hg);
+    if (rc) return rc;
+    if ((rc = ia::ws_layout(&hg, batch, w))) return rc;
+    if (!p || !workspace) return IA_E_ARG;
+    if (workspace_bytes < w.total) return IA_E_WORKSPACE;
+    if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
+    ia::make_level_table(&hg, t);
+    char *ws = static_cast<char *>(workspace);
+    return ia::launch_point_decode(g, t, *p, batch, img_hw, scale_factor, rescale,
+                                   reinterpret_cast<float *>(ws + w.off[0]),
+                                   reinterpret_cast<int32_t *>(ws + w.off[1]), ws + w.off[8],
+                                   reinterpret_cast<float *>(ws + w.off[2]),
+                                   reinterpret_cast<float *>(ws + w.off[3]),
+                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, s);
+}
+
+int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                          const float *img_hw, const float *scale_factor, int rescale,
+                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    ia::WsLayout w;
+    ia::LevelTable t;
+    return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
+                             (hipStream_t)stream, w, t);
+}
+
+int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                        const float *img_hw, const float *scale_factor, int rescale,
+                        float score_thr, float iou_thr, int max_per_img, int candidates,
+                        void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                        int32_t *rows, int32_t *num, void *stream)
+{
+    ia::WsLayout w;
+    ia::LevelTable t;
+    hipStream_t s = (hipStream_t)stream;
+    if (!dets || !labels || !rows || !num) return IA_E_ARG;
+    int rc = point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace,
+                               workspace_bytes, s, w, t);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(workspace);
+    float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
+    float *scores_t = reinterpret_cast<float *>(ws + w.off[3]);
+    int32_t *kc = reinterpret_cast<int32_t *>(ws + w.off[4]);
+    int32_t *kr = reinterpret_cast<int32_t *>(ws + w.off[5]);
+    float *best = reinterpret_cast<float *>(ws + w.off[6]);
+    void *nms_ws = ws + w.off[7];
+    const int32_t *gate = nullptr;
+    if (candidates >= 0) {
+        int32_t *need_full = reinterpret_cast<int32_t *>(ws + w.off[10]);
+        if ((rc = ia::launch_lazy_nms(boxes, scores_t, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
+                                      max_per_img, candidates, ws + w.off[9], dets, labels, rows,
+                                      num, need_full, s)))
+            return rc;
+        gate = need_full;
+    }
+    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
+                             nms_ws, kc, kr, s, gate)))
+        return rc;
+    size_t noff[3];
+    char *fin_ws = static_cast<char *>(nms_ws) +
+                   (ia::nms_workspace_bytes(batch, w.R, t.C, noff) + 255) / 256 * 256;
+    return ia::launch_finalize(boxes, scores_t, kc, kr, batch, w.R, w.Rs, t.C, max_per_img, fin_ws,
+                               dets, labels, rows, num, s, gate);
+}
+
 size_t ia_nms_workspace_bytes(int n)
 {
     return n > IA_MAX_CANDIDATES ? ia::nms_big_workspace_bytes(n) : ia::nms_single_workspace_bytes(n);

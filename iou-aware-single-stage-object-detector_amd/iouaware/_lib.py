@@ -17,6 +17,7 @@ IA_LAYOUT_NCHW, IA_LAYOUT_NHWC = 0, 1
 IA_CLS_SIGMOID, IA_CLS_SOFTMAX = 0, 1
 IA_LOSS_SLOTS = 64
 IA_MAX_TARGET_BATCH = 16
+IA_GN_CHUNK = 256
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'csrc')
 SO_PATH = os.path.abspath(os.path.join(_CSRC, 'libiouaware_hip.so'))
@@ -30,6 +31,14 @@ class HeadGeom(C.Structure):
                 ('base_anchors', ((C.c_float * 4) * IA_MAX_ANCHORS) * IA_MAX_LEVELS),
                 ('means', C.c_float * 4), ('stds', C.c_float * 4), ('layout', C.c_int32),
                 ('cls_activation', C.c_int32)]
+
+
+class PointHeadGeom(C.Structure):
+    """ia_point_head_geom"""
+    _fields_ = [('num_levels', C.c_int32), ('num_classes', C.c_int32), ('nms_pre', C.c_int32),
+                ('H', C.c_int32 * IA_MAX_LEVELS), ('W', C.c_int32 * IA_MAX_LEVELS),
+                ('stride', C.c_int32 * IA_MAX_LEVELS), ('layout', C.c_int32),
+                ('score_alpha', C.c_float)]
 
 
 class LevelPtrs(C.Structure):
@@ -81,6 +90,7 @@ class WinoSeg(C.Structure):
 
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 _G, _P = C.POINTER(HeadGeom), C.POINTER(LevelPtrs)
+_PG, _WG = C.POINTER(PointHeadGeom), C.POINTER(WinoGeom)
 
 # name -> (restype, argtypes); mirrors include/iouaware.h one to one
 SIGNATURES = {
@@ -195,6 +205,15 @@ SIGNATURES = {
     'ia_upsample2x_add_nhwc_dt': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_affine_relu_maxpool_nhwc_dt': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'ia_affine_relu_maxpool_nhwc': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'ia_groupnorm_workspace_bytes': (_sz, [_WG, _i, _i]),
+    'ia_groupnorm_stats': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _sz, _vp]),
+    'ia_groupnorm_apply': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),
+    'ia_scale_exp_levels': (_i, [_WG, C.POINTER(C.c_void_p), _i, _vp, _vp]),
+    'ia_point_workspace_bytes': (_sz, [_PG, _i]),
+    'ia_point_workspace_layout': (_i, [_PG, _i, C.POINTER(_sz * 8)]),
+    'ia_point_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    'ia_point_get_bboxes': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp, _vp,
+                                 _vp, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

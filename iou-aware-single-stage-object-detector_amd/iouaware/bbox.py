@@ -53,6 +53,21 @@ def delta2bbox(rois, deltas, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), max_
     return torch.stack([x1, y1, x2, y2], dim=-1).view_as(deltas)
 
 
+def distance2bbox(points, distance, max_shape=None):
+    """(n,2) points [x, y] + (n,4) distances (left, top, right, bottom) -> (n,4) boxes, clamped to
+    [0, w-1] / [0, h-1] when max_shape is given (transforms.py:169-190)."""
+    x1 = points[:, 0] - distance[:, 0]
+    y1 = points[:, 1] - distance[:, 1]
+    x2 = points[:, 0] + distance[:, 2]
+    y2 = points[:, 1] + distance[:, 3]
+    if max_shape is not None:
+        x1 = x1.clamp(min=0, max=max_shape[1] - 1)
+        y1 = y1.clamp(min=0, max=max_shape[0] - 1)
+        x2 = x2.clamp(min=0, max=max_shape[1] - 1)
+        y2 = y2.clamp(min=0, max=max_shape[0] - 1)
+    return torch.stack([x1, y1, x2, y2], -1)
+
+
 def bbox_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False):
     """(m,n) IoU / IoF matrix, or (m,) aligned pairs; widths are x2-x1+1."""
     if mode not in ('iou', 'iof'):

@@ -7,7 +7,7 @@ layout finds this build's implementations:
     from mmdet.ops import sigmoid_focal_loss          # -> HIP focal-loss op
     from mmdet.core import bbox2result, multiclass_nms, delta2bbox ...
 
-Only the names on the IoU-aware RetinaNet path exist (SURVEY.md section 8);
+Only the names on the IoU-aware RetinaNet and FCOS paths exist (SURVEY.md section 8);
 everything else of mmdetection is deliberately absent.
 """
 import sys
@@ -29,7 +29,7 @@ def install(force=False):
             return existing
         raise RuntimeError('a different `mmdet` is already imported')
     from . import (anchors, api, bbox, detectors, fpn, head, layers, losses, nms_op, registry,
-                   targets, backbones, dist as idist, focal_op, preprocess)
+                   targets, backbones, dist as idist, focal_op, preprocess, fcos_head)
     root = _mod('mmdet', __version__='0.6.0+iouaware', __iouaware__=True)
     models = _mod('mmdet.models', **{k: getattr(registry, k) for k in (
         'BACKBONES', 'NECKS', 'ROI_EXTRACTORS', 'SHARED_HEADS', 'HEADS', 'LOSSES', 'DETECTORS',
@@ -45,22 +45,24 @@ def install(force=False):
                             ResNeXt=backbones.ResNeXt, make_res_layer=backbones.make_res_layer)
     models.necks = _mod('mmdet.models.necks', FPN=fpn.FPN)
     models.anchor_heads = _mod('mmdet.models.anchor_heads', AnchorHead=head.AnchorHead,
-                               IoUawareRetinaHead=head.IoUawareRetinaHead)
+                               IoUawareRetinaHead=head.IoUawareRetinaHead,
+                               IoUawareFCOSHead=fcos_head.IoUawareFCOSHead)
     models.detectors = _mod('mmdet.models.detectors', BaseDetector=detectors.BaseDetector,
                             SingleStageDetector=detectors.SingleStageDetector,
-                            RetinaNet=detectors.RetinaNet)
+                            RetinaNet=detectors.RetinaNet, FCOS=detectors.FCOS)
     models.losses = _mod('mmdet.models.losses', FocalLoss=losses.FocalLoss,
                          SmoothL1Loss=losses.SmoothL1Loss,
                          IOUbalancedSigmoidFocalLoss=losses.IOUbalancedSigmoidFocalLoss,
                          IoUbalancedSmoothL1Loss=losses.IoUbalancedSmoothL1Loss)
     models.utils = _mod('mmdet.models.utils', **{k: getattr(layers, k) for k in (
         'ConvModule', 'build_conv_layer', 'build_norm_layer', 'xavier_init', 'normal_init',
-        'uniform_init', 'kaiming_init', 'bias_init_with_prob')})
+        'uniform_init', 'kaiming_init', 'bias_init_with_prob', 'Scale')})
     for k in ('ResNet', 'ResNeXt'):
         setattr(models, k, getattr(backbones, k))
     models.FPN, models.IoUawareRetinaHead, models.RetinaNet = fpn.FPN, head.IoUawareRetinaHead, \
         detectors.RetinaNet
     models.SingleStageDetector = detectors.SingleStageDetector
+    models.FCOS, models.IoUawareFCOSHead = detectors.FCOS, fcos_head.IoUawareFCOSHead
 
     ops_nms = _mod('mmdet.ops.nms', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
     ops_nms.nms_wrapper = _mod('mmdet.ops.nms.nms_wrapper', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
@@ -73,6 +75,7 @@ def install(force=False):
 
     core = _mod('mmdet.core', AnchorGenerator=anchors.AnchorGenerator,
                 anchor_target=targets.anchor_target, delta2bbox=bbox.delta2bbox,
+                distance2bbox=bbox.distance2bbox, iou_loss=losses.iou_loss,
                 bbox2delta=bbox.bbox2delta, bbox_overlaps=bbox.bbox_overlaps,
                 bbox2result=bbox.bbox2result, multi_apply=bbox.multi_apply,
                 multiclass_nms=nms_op.multiclass_nms, MaxIoUAssigner=targets.MaxIoUAssigner,
@@ -80,6 +83,7 @@ def install(force=False):
     core.anchor = _mod('mmdet.core.anchor', AnchorGenerator=anchors.AnchorGenerator,
                        anchor_target=targets.anchor_target)
     core.bbox = _mod('mmdet.core.bbox', delta2bbox=bbox.delta2bbox, bbox2delta=bbox.bbox2delta,
+                     distance2bbox=bbox.distance2bbox,
                      bbox_overlaps=bbox.bbox_overlaps, bbox2result=bbox.bbox2result,
                      MaxIoUAssigner=targets.MaxIoUAssigner, PseudoSampler=targets.PseudoSampler,
                      build_assigner=targets.build_assigner)

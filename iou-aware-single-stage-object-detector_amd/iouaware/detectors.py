@@ -155,3 +155,12 @@ class PendingResults(object):
 class RetinaNet(SingleStageDetector):
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
         super(RetinaNet, self).__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)
+
+
+@DETECTORS.register_module
+class FCOS(SingleStageDetector):
+    """IoU-aware FCOS (reference mmdet/models/detectors/fcos.py): a thin SingleStageDetector;
+    its head (IoUawareFCOSHead) returns (cls, bbox, centerness, iou) per level."""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
+        super(FCOS, self).__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)

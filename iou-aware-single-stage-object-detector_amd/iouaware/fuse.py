@@ -28,7 +28,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 
 from . import ops, train_fuse
 from .backbones import BasicBlock, Bottleneck, ResNet
-from .layers import ConvModule
+from .layers import ConvModule, Scale
 
 # channels per 16-byte vector of the fused elementwise kernels
 _VEC = {torch.float32: 4, torch.bfloat16: 8}
@@ -77,6 +77,11 @@ def _stamp_slots(module):
                 slots.append((m._buffers, 'running_var'))
                 if m.weight is not None:
                     slots.append((m._parameters, 'weight'))
+            elif isinstance(m, torch.nn.GroupNorm) and m.weight is not None:
+                slots.append((m._parameters, 'weight'))        # FCOS towers: copied into the runner
+                slots.append((m._parameters, 'bias'))
+            elif isinstance(m, Scale):
+                slots.append((m._parameters, 'scale'))
     return slots, links
 
 
@@ -428,6 +433,20 @@ def _head_forward(self, feats):
     return type(self).forward(self, feats)
 
 
+def _fcos_head_forward(self, feats):
+    """IoUawareFCOSHead at inference (eval, no grad, fp32 channels-last): the Winograd towers with
+    the HIP GroupNorm + ReLU (winograd.WinogradFCOSHead); anything else: the module's forward"""
+    w = self._ia_wino
+    if (not self.training) and w.usable(feats):
+        if getattr(self, '_ia_dirty', False) or self._ia_stamp != _stamp(self):
+            _fold(self)
+            w = self._ia_wino
+        return w(list(feats))
+    if self.training or torch.is_grad_enabled():
+        _mark_dirty(self)
+    return type(self).forward(self, feats)
+
+
 def _bf16_head_ok(feats):
     return (not torch.is_grad_enabled()) and all(
         x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
@@ -467,6 +486,9 @@ def _fold(m):
         from .winograd import WinogradHead
         m._ia_wino = WinogradHead(m)
         m._ia_c3 = None                           # bf16 weights are packed on the first bf16 call
+    elif type(m).__name__ == 'IoUawareFCOSHead':
+        from .winograd import WinogradFCOSHead
+        m._ia_wino = WinogradFCOSHead(m)
     elif isinstance(m, Bottleneck):
         f = {}
         f['s1'], f['b1'] = _fold_bn(m.norm1)
@@ -572,6 +594,8 @@ def _forward_for(m, winograd):
         return _fpn_forward if winograd else None
     if type(m).__name__ == 'IoUawareRetinaHead':
         return _head_forward if winograd else None
+    if type(m).__name__ == 'IoUawareFCOSHead':
+        return _fcos_head_forward if winograd else None
     for cls, fn in ((Bottleneck, _bottleneck_forward), (BasicBlock, _basic_forward),
                     (ResNet, _resnet_forward), (ConvModule, _convmodule_forward)):
         if isinstance(m, cls):

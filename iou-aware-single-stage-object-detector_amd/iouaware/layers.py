@@ -5,6 +5,7 @@ contractions and stay on PyTorch-ROCm (MIOpen / rocBLAS on MFMA)."""
 import math
 import warnings
 
+import torch
 import torch.nn as nn
 
 
@@ -149,3 +150,15 @@ class ConvModule(nn.Module):
         if do_act:
             x = self.activate(x)
         return self.conv(x)
+
+
+class Scale(nn.Module):
+    """one learnable scalar multiplier (reference mmdet/models/utils/scale.py); the FCOS head keeps
+    one per pyramid level as `scales.<l>.scale`."""
+
+    def __init__(self, scale=1.0):
+        super(Scale, self).__init__()
+        self.scale = nn.Parameter(torch.tensor(scale, dtype=torch.float))
+
+    def forward(self, x):
+        return x * self.scale

@@ -178,3 +178,17 @@ class IoUbalancedSmoothL1Loss(nn.Module):
         total = ops.smooth_l1_balanced_sum(pred.reshape(n, 4, 1, 1), target.reshape(n, 1, 4),
                                            weight.reshape(n, 1, 4), iou, 1, self.beta, self.delta)
         return total * (self.loss_weight / avg_factor)
+
+
+def iou_loss(pred_bboxes, target_bboxes, reduction='mean'):
+    """-log IoU of aligned box pairs (reference mmdet/core/loss/losses.py:636-646), torch ops: the
+    FCOS regression term, differentiable through both arguments."""
+    from .bbox import bbox_overlaps
+    loss = -bbox_overlaps(pred_bboxes, target_bboxes, is_aligned=True).log()
+    if reduction == 'none':
+        return loss
+    if reduction == 'mean':
+        return loss.mean()
+    if reduction == 'sum':
+        return loss.sum()
+    raise ValueError('{} is not a valid value for reduction'.format(reduction))

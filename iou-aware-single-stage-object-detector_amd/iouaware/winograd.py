@@ -309,3 +309,115 @@ class WinogradHead(object):
         output_transform(plan, m_ri, self.n_ri_pad, 1, self.b_ri, False,
                          [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
         return cls, reg, iou
+
+
+class WinogradFCOSHead(object):
+    """the GN conv towers and output convolutions of an IoUawareFCOSHead, all levels at once:
+    every tower layer is a Winograd convolution without bias / ReLU followed by the HIP GroupNorm +
+    ReLU over both towers (csrc/groupnorm.hip: 2 x num_groups groups, the two towers' affine
+    parameters side by side); outputs fcos_cls | fcos_centerness on the cls tower,
+    fcos_reg | fcos_iou on the reg tower, then exp(scale_l * reg) per level in place."""
+
+    def __init__(self, head):
+        convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
+        for m in convs_c + convs_r:
+            if not (m.with_norm and m.norm_cfg.get('type') == 'GN' and m.with_activatation
+                    and m.conv.bias is None and m.activate_last and _wino_ok_conv(m.conv)):
+                raise NotImplementedError('FCOS towers other than 3x3 conv (no bias) + GN + ReLU')
+        self.n_layers = len(convs_c)
+        F = head.feat_channels
+        if head.in_channels % 4 or F % 4:
+            raise ValueError('channel counts must be multiples of 4')
+        self.F, self.cin = F, head.in_channels
+        self.groups = 2 * int(convs_c[0].norm.num_groups)
+        self.eps = float(convs_c[0].norm.eps)
+        if any(float(m.norm.eps) != self.eps or 2 * int(m.norm.num_groups) != self.groups
+               for m in convs_c + convs_r):
+            raise NotImplementedError('towers with different GroupNorm settings')
+
+        def affine(mc, mr):
+            g = torch.cat([mc.norm.weight.detach(), mr.norm.weight.detach()]).float().contiguous()
+            b = torch.cat([mc.norm.bias.detach(), mr.norm.bias.detach()]).float().contiguous()
+            return g, b
+
+        self.u0 = torch.cat([transform_weight(convs_c[0].conv.weight),
+                             transform_weight(convs_r[0].conv.weight)], dim=2).contiguous()
+        self.gn = [affine(convs_c[0], convs_r[0])]
+        self.u = []
+        for i in range(1, self.n_layers):
+            self.u.append(torch.cat([transform_weight(convs_c[i].conv.weight),
+                                     transform_weight(convs_r[i].conv.weight)], dim=0).contiguous())
+            self.gn.append(affine(convs_c[i], convs_r[i]))
+        dev = self.u0.device
+
+        def pair(a, b):
+            """two output convolutions on one tower: (U (36, F, n_pad), bias (n_pad,), n_a, n_b)"""
+            na, nb = a.out_channels, b.out_channels
+            n_pad = (na + nb + 15) // 16 * 16
+            u = torch.zeros((36, F, n_pad), dtype=torch.float32, device=dev)
+            u[:, :, :na] = transform_weight(a.weight)
+            u[:, :, na:na + nb] = transform_weight(b.weight)
+            bias = torch.zeros(n_pad, dtype=torch.float32, device=dev)
+            bias[:na] = a.bias.detach().float()
+            bias[na:na + nb] = b.bias.detach().float()
+            return u.contiguous(), bias.contiguous(), na, nb
+
+        self.u_cc, self.b_cc, self.c_cls, self.c_ctr = pair(head.fcos_cls, head.fcos_centerness)
+        self.u_ri, self.b_ri, self.c_reg, self.c_iou = pair(head.fcos_reg, head.fcos_iou)
+        if self.c_reg % 4:
+            raise ValueError('the regression output needs a multiple of 4 channels')
+        self.scales = torch.stack([s.scale.detach().float() for s in head.scales]).contiguous()
+        self._plans = collections.OrderedDict()
+        self.calls = 0                        # forwards served (tests: the route was taken)
+
+    def usable(self, feats):
+        return len(feats) <= self.scales.numel() and \
+            all(_usable(x) and x.shape[1] == self.cin for x in feats) and not torch.is_grad_enabled()
+
+    def _gn(self, acts, i):
+        from .fcos_ops import groupnorm_relu_
+        g, b = self.gn[i]
+        groupnorm_relu_(acts, g, b, self.groups, self.eps, relu=True)
+
+    def __call__(self, feats):
+        """feats: per-level (B, Cin, H, W) channels-last fp32 -> (cls[L], bbox[L], centerness[L],
+        iou[L]), channels-last"""
+        B = feats[0].shape[0]
+        sizes = [tuple(x.shape[-2:]) for x in feats]
+        key = (B, tuple(sizes), feats[0].device, stream_id())
+        plan = _plan_for(self._plans, key, lambda: _Plan(sizes, B, feats[0].device))
+        T, F = plan.T, self.F
+        v = input_transform(plan, feats, 1, plan.buf('v', (36, T, self.cin)))
+        m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)))
+        acts = plan.acts('a', 2 * F)
+        output_transform(plan, m, 2 * F, 1, None, False, [(0, 2 * F, acts, 0)])
+        self._gn(acts, 0)
+        for i, u in enumerate(self.u):
+            v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
+            m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
+            nxt = plan.acts('b' if acts is plan.acts('a', 2 * F) else 'a', 2 * F)
+            output_transform(plan, m, 2 * F, 2, None, False, [(0, 2 * F, nxt, 0)])
+            self._gn(nxt, i + 1)
+            acts = nxt
+        v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
+        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=feats[0].device,  # noqa: E731
+                                     memory_format=torch.channels_last) for (h, w) in sizes]
+        cls, ctr, reg, iou = new(self.c_cls), new(self.c_ctr), new(self.c_reg), new(self.c_iou)
+        n_cc, n_ri = self.u_cc.shape[2], self.u_ri.shape[2]
+        m_cc = batched_gemm(v[:36], self.u_cc, plan.buf('mc', (36, T, n_cc)))
+        output_transform(plan, m_cc, n_cc, 1, self.b_cc, False,
+                         [(0, self.c_cls, cls, 0), (self.c_cls, self.c_ctr, ctr, 0)])
+        m_ri = batched_gemm(v[36:], self.u_ri, plan.buf('mr', (36, T, n_ri)))
+        output_transform(plan, m_ri, n_ri, 1, self.b_ri, False,
+                         [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
+        ptrs = (C.c_void_p * len(reg))(*[t.data_ptr() for t in reg])
+        _lib.check(_lib.lib().ia_scale_exp_levels(C.byref(plan.geom), ptrs, self.c_reg,
+                                                  _ptr(self.scales), _stream()),
+                   'ia_scale_exp_levels')
+        self.calls += 1
+        return cls, reg, ctr, iou
+
+
+def _wino_ok_conv(conv):
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1)
