@@ -80,7 +80,8 @@ typedef struct ia_head_geom {
     int32_t cls_activation;
 } ia_head_geom;
 
-/* Per-level device pointers of the three head outputs, each (B, ch, H, W). */
+/* Per-level device pointers of the three head outputs, each (B, ch, H, W).  The plain FCOS entries
+ * (ia_point_ctr_*) carry the centerness map (B, 1, H, W) in the iou slot. */
 typedef struct ia_level_ptrs {
     const void *cls[IA_MAX_LEVELS];
     const void *reg[IA_MAX_LEVELS];
@@ -796,6 +797,25 @@ int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int
                         float score_thr, float iou_thr, int max_per_img, int candidates,
                         void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                         int32_t *rows, int32_t *num, void *stream);
+
+/* Plain FCOS (reference mmdet/models/anchor_heads/fcos_head.py:225-272 with multiclass_nms(...,
+ * score_factors=centerness), mmdet/core/post_processing/bbox_nms.py:37-48): as the ia_point_*
+ * entries above, same geometry (score_alpha ignored), workspace, outputs and tie rule, with
+ * p->iou[l] = the centerness logits (B, 1, H, W) and these scores:
+ *   rowmax = max_c sigmoid(cls_c) * sigmoid(ctr) (fp32 product; the per-level top nms_pre);
+ *   scores_t[c] = sigmoid(cls_c) * sigmoid(ctr) where the RAW score sigmoid(cls_c) > score_thr
+ *     (a product of 0 included), else a negative sentinel that no NMS stage, key or output row
+ *     takes; best_score = the row maximum of what was written.
+ * NMS and the final max_per_img sort use the product.  ia_point_ctr_decode_stage: the decode
+ * stage only (it applies score_thr).                                                          */
+int ia_point_ctr_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                              const float *img_hw, const float *scale_factor, int rescale,
+                              float score_thr, void *workspace, size_t workspace_bytes, void *stream);
+int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                            const float *img_hw, const float *scale_factor, int rescale,
+                            float score_thr, float iou_thr, int max_per_img, int candidates,
+                            void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                            int32_t *rows, int32_t *num, void *stream);
 
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the

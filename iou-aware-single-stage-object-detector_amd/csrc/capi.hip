@@ -459,7 +459,7 @@ int ia_point_workspace_layout(const ia_point_head_geom *g, int batch, size_t off
 static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                              const float *img_hw, const float *scale_factor, int rescale,
                              void *workspace, size_t workspace_bytes, hipStream_t s,
-                             ia::WsLayout &w, ia::LevelTable &t)
+                             ia::WsLayout &w, ia::LevelTable &t, int kind, float score_thr)
 {
     ia_head_geom hg;
     int rc = ia::point_head_geom(g, hg);
@@ -475,7 +475,7 @@ static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p
                                    reinterpret_cast<int32_t *>(ws + w.off[1]), ws + w.off[8],
                                    reinterpret_cast<float *>(ws + w.off[2]),
                                    reinterpret_cast<float *>(ws + w.off[3]),
-                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, s);
+                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, kind, score_thr, s);
 }
 
 int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
@@ -485,21 +485,33 @@ int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, i
     ia::WsLayout w;
     ia::LevelTable t;
     return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
-                             (hipStream_t)stream, w, t);
+                             (hipStream_t)stream, w, t, 0, 0.0f);
 }
 
-int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
-                        const float *img_hw, const float *scale_factor, int rescale,
-                        float score_thr, float iou_thr, int max_per_img, int candidates,
-                        void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
-                        int32_t *rows, int32_t *num, void *stream)
+int ia_point_ctr_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                              const float *img_hw, const float *scale_factor, int rescale,
+                              float score_thr, void *workspace, size_t workspace_bytes, void *stream)
 {
     ia::WsLayout w;
     ia::LevelTable t;
-    hipStream_t s = (hipStream_t)stream;
+    return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
+                             (hipStream_t)stream, w, t, 1, score_thr);
+}
+
+// decode stage of `kind`, then the shared NMS stages at `stage_thr` (the IoU-aware head: its
+// score_thr; plain FCOS: kPointCtrStageThr, the raw threshold having been applied by the gather)
+static int point_get_bboxes_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                                 const float *img_hw, const float *scale_factor, int rescale,
+                                 int kind, float score_thr, float stage_thr, float iou_thr,
+                                 int max_per_img, int candidates, void *workspace,
+                                 size_t workspace_bytes, float *dets, int32_t *labels,
+                                 int32_t *rows, int32_t *num, hipStream_t s)
+{
+    ia::WsLayout w;
+    ia::LevelTable t;
     if (!dets || !labels || !rows || !num) return IA_E_ARG;
     int rc = point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace,
-                               workspace_bytes, s, w, t);
+                               workspace_bytes, s, w, t, kind, score_thr);
     if (rc) return rc;
     char *ws = static_cast<char *>(workspace);
     float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
@@ -511,13 +523,13 @@ int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int
     const int32_t *gate = nullptr;
     if (candidates >= 0) {
         int32_t *need_full = reinterpret_cast<int32_t *>(ws + w.off[10]);
-        if ((rc = ia::launch_lazy_nms(boxes, scores_t, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
+        if ((rc = ia::launch_lazy_nms(boxes, scores_t, batch, w.R, w.Rs, t.C, stage_thr, iou_thr,
                                       max_per_img, candidates, ws + w.off[9], dets, labels, rows,
                                       num, need_full, s)))
             return rc;
         gate = need_full;
     }
-    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
+    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.R, w.Rs, t.C, stage_thr, iou_thr,
                              nms_ws, kc, kr, s, gate)))
         return rc;
     size_t noff[3];
@@ -525,6 +537,28 @@ int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int
                    (ia::nms_workspace_bytes(batch, w.R, t.C, noff) + 255) / 256 * 256;
     return ia::launch_finalize(boxes, scores_t, kc, kr, batch, w.R, w.Rs, t.C, max_per_img, fin_ws,
                                dets, labels, rows, num, s, gate);
+}
+
+int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                        const float *img_hw, const float *scale_factor, int rescale,
+                        float score_thr, float iou_thr, int max_per_img, int candidates,
+                        void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                        int32_t *rows, int32_t *num, void *stream)
+{
+    return point_get_bboxes_impl(g, p, batch, img_hw, scale_factor, rescale, 0, 0.0f, score_thr,
+                                 iou_thr, max_per_img, candidates, workspace, workspace_bytes, dets,
+                                 labels, rows, num, (hipStream_t)stream);
+}
+
+int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                            const float *img_hw, const float *scale_factor, int rescale,
+                            float score_thr, float iou_thr, int max_per_img, int candidates,
+                            void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                            int32_t *rows, int32_t *num, void *stream)
+{
+    return point_get_bboxes_impl(g, p, batch, img_hw, scale_factor, rescale, 1, score_thr,
+                                 ia::kPointCtrStageThr, iou_thr, max_per_img, candidates, workspace,
+                                 workspace_bytes, dets, labels, rows, num, (hipStream_t)stream);
 }
 
 size_t ia_nms_workspace_bytes(int n)

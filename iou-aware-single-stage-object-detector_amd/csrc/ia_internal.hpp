@@ -164,12 +164,18 @@ int launch_nms_single(const float *dets, int n, float iou_thr, int32_t *keep, in
                       void *workspace, size_t workspace_bytes, hipStream_t s);
 
 // point head (pointdecode.hip): the A = 1 anchor-head geometry of the same maps, and the decode
-// stage (row max, the shared top-k, gather / distance2bbox) into the ia_get_bboxes workspace slots
+// stage (row max, the shared top-k, gather / distance2bbox) into the ia_get_bboxes workspace slots.
+// kind 0: IoU-aware fused score; kind 1: plain FCOS, sigmoid(cls) * sigmoid(centerness) where
+// sigmoid(cls) > score_thr, else kPointCtrSentinel -- the NMS stages behind it then run with
+// score threshold kPointCtrStageThr, which every product (>= 0) passes and no sentinel does.
+constexpr float kPointCtrSentinel = -1.0f;
+constexpr float kPointCtrStageThr = -0.5f;
 int point_head_geom(const ia_point_head_geom *pg, ia_head_geom &g);
 int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const ia_level_ptrs &p,
                         int batch, const float *img_hw, const float *scale_factor, int rescale,
                         float *rowmax, int32_t *cand_idx, void *select_ws, float *boxes,
-                        float *scores_t, float *best_score, int Rs, hipStream_t s);
+                        float *scores_t, float *best_score, int Rs, int kind, float score_thr,
+                        hipStream_t s);
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 

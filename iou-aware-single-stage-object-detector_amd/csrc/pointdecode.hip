@@ -1,6 +1,6 @@
-// Decode stage of the point head (IoU-aware FCOS, reference
-// mmdet/models/anchor_heads/iou_aware_fcos_head.py:310-350): fused scores, per-level row max,
-// candidate gather and distance2bbox.  The top-k between the two kernels and the NMS behind them
+// Decode stage of the point heads (IoU-aware FCOS, reference
+// mmdet/models/anchor_heads/iou_aware_fcos_head.py:310-350, and plain FCOS, fcos_head.py:225-272):
+// scores, per-level row max, candidate gather and distance2bbox.  The top-k between the two kernels and the NMS behind them
 // are the anchor head's (select.hip, nms.hip, lazynms.hip), run on the level table of the same
 // feature maps with one "anchor" per position -- the row-max array is then in point order in
 // either memory layout, the tie rule (score desc, index asc) and the workspace contract are shared.
@@ -14,6 +14,17 @@
 //                    (B, C, Rs) array, their maximum into best_score, and the box
 //                    (px - l, py - t, px + r, py + b) with px = x * stride + stride / 2, clamped to
 //                    [0, w-1] x [0, h-1], divided by scale_factor when rescaling.
+//
+// Both kernels are templates on the score kind (launch-uniform):
+//   kPointIouAware   the fused score above (the third map is the IoU logit);
+//   kPointCtr        plain FCOS: the third map is the centerness logit.  Row max
+//                    max_c(sigmoid(x_c) * sigmoid(ctr)) (fp32 product, the reference's max_scores);
+//                    the gather writes sigmoid(x_c) * sigmoid(ctr) where the RAW score
+//                    sigmoid(x_c) > score_thr and kPointCtrSentinel (< 0) elsewhere
+//                    (multiclass_nms with score_factors, bbox_nms.py:37-48: threshold on the raw
+//                    score, NMS / final sort on the product).  The shared NMS stages then run with
+//                    the threshold kPointCtrStageThr, between the sentinel and 0: every product
+//                    (>= 0, an underflowed 0 included) passes it, no sentinel does.
 #include "ia_internal.hpp"
 #include "ia_math.hpp"
 
@@ -28,9 +39,13 @@ struct PointArgs {
     const float *img_hw, *scale_factor;
     float *boxes, *scores_t, *best_score;
     int32_t R, Rs, rescale, batch;
+    float score_thr;                         // kPointCtr: the raw-score threshold of the gather
 };
 
-struct PointLevel { int l, base, H, W, stride; const float *cls, *reg, *iou; };
+// score kinds (template parameter of the two kernels)
+constexpr int kPointIouAware = 0, kPointCtr = 1;
+
+struct PointLevel { int l, base, H, W, stride; const float *cls, *reg, *iou; };   // iou: or centerness
 
 // level of an index into a prefix table (the per-level scalars through selects: scalar kernarg
 // loads, no per-lane indexing of the argument block)
@@ -56,11 +71,20 @@ __device__ __forceinline__ PointLevel point_level(const PointArgs &a, const int3
     return s;
 }
 
-__device__ __forceinline__ float point_score(float x, float fi, float alpha)
+// the per-point factor of the score: powf(sigmoid(iou), 1 - alpha), or sigmoid(centerness)
+template <int KIND>
+__device__ __forceinline__ float point_factor(float x, float beta)
 {
-    return powf_pos_(sigmoidf_(x), alpha) * fi;
+    return KIND == kPointCtr ? sigmoidf_(x) : powf_pos_(sigmoidf_(x), beta);
 }
 
+template <int KIND>
+__device__ __forceinline__ float point_score(float x, float fi, float alpha)
+{
+    return KIND == kPointCtr ? sigmoidf_(x) * fi : powf_pos_(sigmoidf_(x), alpha) * fi;
+}
+
+template <int KIND>
 __global__ void __launch_bounds__(256) k_point_rowmax(PointArgs a)
 {
     const int N = a.t.anchor_off[a.t.num_levels];
@@ -69,27 +93,28 @@ __global__ void __launch_bounds__(256) k_point_rowmax(PointArgs a)
     const int b = (int)(gid / N), i = (int)(gid - (int64_t)b * N);
     const PointLevel lv = point_level(a, a.t.anchor_off, i);
     const int pos = i - lv.base, HW = lv.H * lv.W, C = a.t.C;
-    const float fi = powf_pos_(sigmoidf_(lv.iou[(size_t)b * HW + pos]), a.beta);
+    const float fi = point_factor<KIND>(lv.iou[(size_t)b * HW + pos], a.beta);
     float best = 0.0f;                       // scores are >= 0
     if (a.t.layout == IA_LAYOUT_NHWC) {
         const float4 *row = reinterpret_cast<const float4 *>(lv.cls + ((size_t)b * HW + pos) * C);
         for (int v = 0; v < C / 4; ++v) {
             const float4 q = row[v];
-            float sc = point_score(q.x, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score(q.y, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score(q.z, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score(q.w, fi, a.alpha); best = (best < sc) ? sc : best;
+            float sc = point_score<KIND>(q.x, fi, a.alpha); best = (best < sc) ? sc : best;
+            sc = point_score<KIND>(q.y, fi, a.alpha); best = (best < sc) ? sc : best;
+            sc = point_score<KIND>(q.z, fi, a.alpha); best = (best < sc) ? sc : best;
+            sc = point_score<KIND>(q.w, fi, a.alpha); best = (best < sc) ? sc : best;
         }
     } else {
         const float *cls = lv.cls + (size_t)b * C * HW + pos;
         for (int c = 0; c < C; ++c) {
-            const float sc = point_score(cls[(size_t)c * HW], fi, a.alpha);
+            const float sc = point_score<KIND>(cls[(size_t)c * HW], fi, a.alpha);
             best = (best < sc) ? sc : best;
         }
     }
     a.rowmax[(size_t)b * N + i] = best;
 }
 
+template <int KIND>
 __global__ void __launch_bounds__(256) k_point_gather(PointArgs a)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,16 +125,29 @@ __global__ void __launch_bounds__(256) k_point_gather(PointArgs a)
     const int pos = a.cand_idx[(size_t)b * a.R + r];
     const bool nhwc = a.t.layout == IA_LAYOUT_NHWC;
     const size_t cs = nhwc ? (size_t)1 : (size_t)HW;
-    const float fi = powf_pos_(sigmoidf_(lv.iou[(size_t)b * HW + pos]), a.beta);
+    const float fi = point_factor<KIND>(lv.iou[(size_t)b * HW + pos], a.beta);
     const float *cls = lv.cls + (nhwc ? ((size_t)b * HW + pos) * C : (size_t)b * C * HW + pos);
     float *so = a.scores_t + (size_t)b * C * a.Rs + r;
-    float best = 0.0f;
-    for (int c = 0; c < C; ++c) {
-        const float sc = point_score(cls[(size_t)c * cs], fi, a.alpha);
-        so[(size_t)c * a.Rs] = sc;
-        best = (best < sc) ? sc : best;
+    if (KIND == kPointCtr) {
+        // raw-score threshold, then the product; best = max of what was written (the sentinel
+        // when no class passes: the row then stays out of k_adj's relation)
+        float best = kPointCtrSentinel;
+        for (int c = 0; c < C; ++c) {
+            const float s = sigmoidf_(cls[(size_t)c * cs]);
+            const float sc = (s > a.score_thr) ? s * fi : kPointCtrSentinel;
+            so[(size_t)c * a.Rs] = sc;
+            best = (best < sc) ? sc : best;
+        }
+        if (a.best_score) a.best_score[(size_t)b * a.R + r] = best;
+    } else {
+        float best = 0.0f;
+        for (int c = 0; c < C; ++c) {
+            const float sc = point_score<KIND>(cls[(size_t)c * cs], fi, a.alpha);
+            so[(size_t)c * a.Rs] = sc;
+            best = (best < sc) ? sc : best;
+        }
+        if (a.best_score) a.best_score[(size_t)b * a.R + r] = best;
     }
-    if (a.best_score) a.best_score[(size_t)b * a.R + r] = best;
     const float *reg = lv.reg + (nhwc ? ((size_t)b * HW + pos) * 4 : (size_t)b * 4 * HW + pos);
     const int y = pos / lv.W, x = pos - y * lv.W;
     const float px = (float)(x * lv.stride + lv.stride / 2), py = (float)(y * lv.stride + lv.stride / 2);
@@ -154,26 +192,36 @@ int point_head_geom(const ia_point_head_geom *pg, ia_head_geom &g)
 int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const ia_level_ptrs &p,
                         int batch, const float *img_hw, const float *scale_factor, int rescale,
                         float *rowmax, int32_t *cand_idx, void *select_ws, float *boxes,
-                        float *scores_t, float *best_score, int Rs, hipStream_t s)
+                        float *scores_t, float *best_score, int Rs, int kind, float score_thr,
+                        hipStream_t s)
 {
     if (batch < 1 || !img_hw || (rescale && !scale_factor)) return IA_E_ARG;
+    if (kind != kPointIouAware && kind != kPointCtr) return IA_E_ARG;
     PointArgs a;
     a.t = t; a.p = p;
     a.alpha = pg->score_alpha; a.beta = 1.0f - pg->score_alpha;
     a.rowmax = rowmax; a.cand_idx = cand_idx; a.img_hw = img_hw; a.scale_factor = scale_factor;
     a.boxes = boxes; a.scores_t = scores_t; a.best_score = best_score;
     a.R = t.cand_off[t.num_levels]; a.Rs = Rs; a.rescale = rescale ? 1 : 0; a.batch = batch;
+    a.score_thr = score_thr;
     for (int l = 0; l < t.num_levels; ++l) {
         if (!p.cls[l] || !p.reg[l] || !p.iou[l]) return IA_E_ARG;
         if (t.layout == IA_LAYOUT_NHWC && ((uintptr_t)p.cls[l] & 15u)) return IA_E_ARG;
     }
     const int64_t n = (int64_t)batch * t.anchor_off[t.num_levels];
-    hipLaunchKernelGGL(k_point_rowmax, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    if (kind == kPointCtr)
+        hipLaunchKernelGGL(k_point_rowmax<kPointCtr>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_point_rowmax<kPointIouAware>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                           s, a);
     int rc = hip_status(hipGetLastError());
     if (rc) return rc;
     if ((rc = launch_select(t, rowmax, batch, cand_idx, select_ws, s, false))) return rc;
-    hipLaunchKernelGGL(k_point_gather, dim3((unsigned)((a.R + 255) / 256), (unsigned)batch), dim3(256),
-                       0, s, a);
+    const dim3 grid((unsigned)((a.R + 255) / 256), (unsigned)batch);
+    if (kind == kPointCtr)
+        hipLaunchKernelGGL(k_point_gather<kPointCtr>, grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_point_gather<kPointIouAware>, grid, dim3(256), 0, s, a);
     return hip_status(hipGetLastError());
 }
 

@@ -214,6 +214,9 @@ SIGNATURES = {
     'ia_point_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     'ia_point_get_bboxes': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp, _vp,
                                  _vp, _vp]),
+    'ia_point_ctr_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _vp, _sz, _vp]),
+    'ia_point_ctr_get_bboxes': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp,
+                                     _vp, _vp, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

@@ -46,7 +46,8 @@ def install(force=False):
     models.necks = _mod('mmdet.models.necks', FPN=fpn.FPN)
     models.anchor_heads = _mod('mmdet.models.anchor_heads', AnchorHead=head.AnchorHead,
                                IoUawareRetinaHead=head.IoUawareRetinaHead,
-                               IoUawareFCOSHead=fcos_head.IoUawareFCOSHead)
+                               IoUawareFCOSHead=fcos_head.IoUawareFCOSHead,
+                               FCOSHead=fcos_head.FCOSHead)
     models.detectors = _mod('mmdet.models.detectors', BaseDetector=detectors.BaseDetector,
                             SingleStageDetector=detectors.SingleStageDetector,
                             RetinaNet=detectors.RetinaNet, FCOS=detectors.FCOS)
@@ -63,6 +64,7 @@ def install(force=False):
         detectors.RetinaNet
     models.SingleStageDetector = detectors.SingleStageDetector
     models.FCOS, models.IoUawareFCOSHead = detectors.FCOS, fcos_head.IoUawareFCOSHead
+    models.FCOSHead = fcos_head.FCOSHead
 
     ops_nms = _mod('mmdet.ops.nms', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
     ops_nms.nms_wrapper = _mod('mmdet.ops.nms.nms_wrapper', nms=nms_op.nms, soft_nms=nms_op.soft_nms)

@@ -9,6 +9,7 @@ ndarray list for a batch of one.  Lifted: the batch-1 assert of the reference
 (base.py:96-98) -- `simple_test_batch` / `forward_test` handle B images per
 call (BASELINE configs 2, 3) and the whole post-conv path is one library call.
 """
+import inspect
 import logging
 
 import torch
@@ -107,8 +108,10 @@ class SingleStageDetector(BaseDetector):
             return [bbox2result(dets[b, :k], labels[b, :k], self.bbox_head.num_classes)
                     for b, k in enumerate(num)]
         outs = self.forward_head(img)
-        bbox_list = self.bbox_head.get_bboxes(*(outs + (gt_bboxes, gt_labels, img_meta,
-                                                        self.test_cfg, rescale)))
+        # the fork's heads take the gt arguments (base.py:62-67); plain FCOSHead.get_bboxes does not
+        gts = (gt_bboxes, gt_labels) if 'gt_bboxes' in inspect.signature(
+            self.bbox_head.get_bboxes).parameters else ()
+        bbox_list = self.bbox_head.get_bboxes(*(outs + gts + (img_meta, self.test_cfg, rescale)))
         return [bbox2result(d, l, self.bbox_head.num_classes) for d, l in bbox_list]
 
     def simple_test_batch_submit(self, img, img_meta, rescale=False):
@@ -159,8 +162,9 @@ class RetinaNet(SingleStageDetector):
 
 @DETECTORS.register_module
 class FCOS(SingleStageDetector):
-    """IoU-aware FCOS (reference mmdet/models/detectors/fcos.py): a thin SingleStageDetector;
-    its head (IoUawareFCOSHead) returns (cls, bbox, centerness, iou) per level."""
+    """FCOS (reference mmdet/models/detectors/fcos.py): a thin SingleStageDetector; its head
+    returns (cls, bbox, centerness, iou) per level (IoUawareFCOSHead) or (cls, bbox, centerness)
+    (FCOSHead)."""
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
         super(FCOS, self).__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)

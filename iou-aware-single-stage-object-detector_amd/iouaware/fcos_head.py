@@ -1,12 +1,14 @@
-"""IoU-aware FCOS head (reference mmdet/models/anchor_heads/iou_aware_fcos_head.py), with the
-reference's registry name, constructor kwargs, parameter names and method signatures.
+"""FCOS heads: plain FCOS (reference mmdet/models/anchor_heads/fcos_head.py) and IoU-aware FCOS
+(reference mmdet/models/anchor_heads/iou_aware_fcos_head.py), with the reference's registry names,
+constructor kwargs, parameter names and method signatures.
 
-  * forward / forward_single: the 4 + 4 GN towers and the four output convolutions as PyTorch
+  * forward / forward_single: the 4 + 4 GN towers and the output convolutions as PyTorch
     modules (the training route; at inference `fuse.fuse_inference(winograd=True)` swaps in the
     Winograd runner with the HIP GroupNorm + ReLU, winograd.WinogradFCOSHead);
-  * get_bboxes: one call into the HIP library for the whole batch (fused alpha score, row max,
-    per-level top-k, distance2bbox, batched NMS: ia_point_get_bboxes);
-  * loss: targets and the four terms in torch ops on the device, the class term through the
+  * get_bboxes: one call into the HIP library for the whole batch (row max, per-level top-k,
+    distance2bbox, batched NMS): ia_point_get_bboxes with the fused alpha score (IoU-aware),
+    ia_point_ctr_get_bboxes with the raw-threshold / centerness-product scores (plain);
+  * loss: targets and the terms in torch ops on the device, the class term through the
     HIP sigmoid focal-loss op (integer targets, the reference CUDA op's semantics).
 There is no CPU fallback for get_bboxes / loss: they need tensors on a gfx950 device.
 """
@@ -24,17 +26,17 @@ from .registry import HEADS
 INF = 1e8
 
 
-@HEADS.register_module
-class IoUawareFCOSHead(nn.Module):
-    # score = sigmoid(cls) ** alpha * sigmoid(iou) ** (1 - alpha), hard-coded in the reference
-    # (iou_aware_fcos_head.py:326)
+class _FCOSHeadBase(nn.Module):
+    """what the two FCOS heads share: constructor, points, targets, the flattened loss inputs and
+    the point geometry of the HIP decode"""
+    # the geometry's score_alpha (ia_point_head_geom); the plain head's entries ignore it
     score_alpha = 0.3
 
     def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4,
                  strides=(4, 8, 16, 32, 64),
                  regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)),
                  conv_cfg=None, norm_cfg=dict(type='GN', num_groups=32, requires_grad=True)):
-        super(IoUawareFCOSHead, self).__init__()
+        super(_FCOSHeadBase, self).__init__()
         self.num_classes = num_classes
         self.cls_out_channels = num_classes - 1
         self.in_channels = in_channels
@@ -46,7 +48,8 @@ class IoUawareFCOSHead(nn.Module):
         self.norm_cfg = norm_cfg
         self._init_layers()
 
-    def _init_layers(self):
+    def _init_towers(self):
+        """the GN towers and fcos_cls / fcos_centerness / fcos_reg, in the reference's order"""
         self.cls_convs = nn.ModuleList()
         self.reg_convs = nn.ModuleList()
         for i in range(self.stacked_convs):
@@ -58,10 +61,8 @@ class IoUawareFCOSHead(nn.Module):
         self.fcos_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.fcos_centerness = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
         self.fcos_reg = nn.Conv2d(self.feat_channels, 4, 3, padding=1)
-        self.fcos_iou = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
-        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
 
-    def init_weights(self):
+    def _init_tower_weights(self):
         for m in self.cls_convs:
             normal_init(m.conv, std=0.01)
         for m in self.reg_convs:
@@ -69,24 +70,6 @@ class IoUawareFCOSHead(nn.Module):
         normal_init(self.fcos_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.fcos_reg, std=0.01)
         normal_init(self.fcos_centerness, std=0.01)
-        normal_init(self.fcos_iou, std=0.01)
-
-    def forward(self, feats):
-        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L], ious[L])"""
-        return multi_apply(self.forward_single, feats, self.scales)
-
-    def forward_single(self, x, scale):
-        cls_feat = x
-        reg_feat = x
-        for cls_layer in self.cls_convs:
-            cls_feat = cls_layer(cls_feat)
-        cls_score = self.fcos_cls(cls_feat)
-        centerness = self.fcos_centerness(cls_feat)
-        for reg_layer in self.reg_convs:
-            reg_feat = reg_layer(reg_feat)
-        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
-        iou = self.fcos_iou(reg_feat)
-        return cls_score, bbox_pred, centerness, iou
 
     # ------------------------------------------------------------------ points / targets
     def get_points(self, featmap_sizes, dtype, device):
@@ -155,12 +138,8 @@ class IoUawareFCOSHead(nn.Module):
         return torch.sqrt(c)
 
     # ------------------------------------------------------------------ training
-    def loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, img_metas,
-             cfg, gt_bboxes_ignore=None):
-        """the reference's four terms (iou_aware_fcos_head.py:121-244); the IoU target is NOT
-        detached (as in the reference: its gradient reaches bbox_preds too)"""
-        if not len(cls_scores) == len(bbox_preds) == len(centernesses) == len(ious):
-            raise AssertionError('level count mismatch')
+    def _flat_loss_inputs(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels):
+        """targets and the per-point flattened outputs of the batch (image-major inside a level)"""
         featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores]
         all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device)
         labels, bbox_targets = self.fcos_target(all_level_points, gt_bboxes, gt_labels)
@@ -169,10 +148,64 @@ class IoUawareFCOSHead(nn.Module):
                               for c in cls_scores])
         flat_bbox = torch.cat([b.permute(0, 2, 3, 1).reshape(-1, 4) for b in bbox_preds])
         flat_ctr = torch.cat([c.permute(0, 2, 3, 1).reshape(-1) for c in centernesses])
-        flat_iou = torch.cat([i.permute(0, 2, 3, 1).reshape(-1) for i in ious])
         flat_labels = torch.cat(labels)
         flat_bbox_targets = torch.cat(bbox_targets)
         flat_points = torch.cat([points.repeat(num_imgs, 1) for points in all_level_points])
+        return num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points
+
+    # ------------------------------------------------------------------ inference
+    def geometry(self, featmap_sizes, nms_pre=-1):
+        key = (tuple(tuple(int(v) for v in s) for s in featmap_sizes), int(nms_pre))
+        cache = self.__dict__.setdefault('_geom_cache', {})
+        g = cache.get(key)
+        if g is None:
+            g = cache[key] = fcos_ops.PointGeometry(key[0], self.strides[:len(featmap_sizes)],
+                                                    self.cls_out_channels, nms_pre,
+                                                    self.score_alpha)
+        return g
+
+
+@HEADS.register_module
+class IoUawareFCOSHead(_FCOSHeadBase):
+    # score = sigmoid(cls) ** alpha * sigmoid(iou) ** (1 - alpha), hard-coded in the reference
+    # (iou_aware_fcos_head.py:326)
+    score_alpha = 0.3
+
+    def _init_layers(self):
+        self._init_towers()
+        self.fcos_iou = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
+
+    def init_weights(self):
+        self._init_tower_weights()
+        normal_init(self.fcos_iou, std=0.01)
+
+    def forward(self, feats):
+        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L], ious[L])"""
+        return multi_apply(self.forward_single, feats, self.scales)
+
+    def forward_single(self, x, scale):
+        cls_feat = x
+        reg_feat = x
+        for cls_layer in self.cls_convs:
+            cls_feat = cls_layer(cls_feat)
+        cls_score = self.fcos_cls(cls_feat)
+        centerness = self.fcos_centerness(cls_feat)
+        for reg_layer in self.reg_convs:
+            reg_feat = reg_layer(reg_feat)
+        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
+        iou = self.fcos_iou(reg_feat)
+        return cls_score, bbox_pred, centerness, iou
+
+    def loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, img_metas,
+             cfg, gt_bboxes_ignore=None):
+        """the reference's four terms (iou_aware_fcos_head.py:121-244); the IoU target is NOT
+        detached (as in the reference: its gradient reaches bbox_preds too)"""
+        if not len(cls_scores) == len(bbox_preds) == len(centernesses) == len(ious):
+            raise AssertionError('level count mismatch')
+        num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points = \
+            self._flat_loss_inputs(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels)
+        flat_iou = torch.cat([i.permute(0, 2, 3, 1).reshape(-1) for i in ious])
 
         pos_inds = flat_labels.nonzero().reshape(-1)
         num_pos = len(pos_inds)
@@ -204,16 +237,6 @@ class IoUawareFCOSHead(nn.Module):
                     loss_iou=loss_iou)
 
     # ------------------------------------------------------------------ inference
-    def geometry(self, featmap_sizes, nms_pre=-1):
-        key = (tuple(tuple(int(v) for v in s) for s in featmap_sizes), int(nms_pre))
-        cache = self.__dict__.setdefault('_geom_cache', {})
-        g = cache.get(key)
-        if g is None:
-            g = cache[key] = fcos_ops.PointGeometry(key[0], self.strides[:len(featmap_sizes)],
-                                                    self.cls_out_channels, nms_pre,
-                                                    self.score_alpha)
-        return g
-
     def get_bboxes_batched(self, cls_scores, bbox_preds, centernesses, ious, img_metas, cfg,
                            rescale=False):
         """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
@@ -239,6 +262,96 @@ class IoUawareFCOSHead(nn.Module):
                    img_metas, cfg, rescale=None):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64)"""
         dets, labels, _, num = self.get_bboxes_batched(cls_scores, bbox_preds, centernesses, ious,
+                                                       img_metas, cfg, rescale)
+        counts = num.tolist()
+        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
+
+
+@HEADS.register_module
+class FCOSHead(_FCOSHeadBase):
+    """plain FCOS (reference fcos_head.py): centerness on the cls tower, no IoU branch; at
+    inference the raw class score is thresholded and NMS ranks sigmoid(cls) * sigmoid(centerness)
+    (multiclass_nms with score_factors, bbox_nms.py:37-48)"""
+
+    def _init_layers(self):
+        self._init_towers()
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
+
+    def init_weights(self):
+        self._init_tower_weights()
+
+    def forward(self, feats):
+        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L])"""
+        return multi_apply(self.forward_single, feats, self.scales)
+
+    def forward_single(self, x, scale):
+        cls_feat = x
+        reg_feat = x
+        for cls_layer in self.cls_convs:
+            cls_feat = cls_layer(cls_feat)
+        cls_score = self.fcos_cls(cls_feat)
+        centerness = self.fcos_centerness(cls_feat)
+        for reg_layer in self.reg_convs:
+            reg_feat = reg_layer(reg_feat)
+        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
+        return cls_score, bbox_pred, centerness
+
+    # ------------------------------------------------------------------ training
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, cfg,
+             gt_bboxes_ignore=None):
+        """the reference's three terms (fcos_head.py:105-191): focal classification over
+        (num_pos + num_imgs), the centerness-weighted IoU loss, the centerness BCE"""
+        if not len(cls_scores) == len(bbox_preds) == len(centernesses):
+            raise AssertionError('level count mismatch')
+        num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points = \
+            self._flat_loss_inputs(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels)
+        pos_inds = flat_labels.nonzero().reshape(-1)
+        num_pos = len(pos_inds)
+        loss_cls = sigmoid_focal_loss(flat_cls.contiguous(), flat_labels, cfg.gamma, cfg.alpha,
+                                      'none').sum()[None] / (num_pos + num_imgs)
+        pos_bbox_preds = flat_bbox[pos_inds]
+        pos_bbox_targets = flat_bbox_targets[pos_inds]
+        pos_centerness = flat_ctr[pos_inds]
+        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
+        if num_pos > 0:
+            pos_points = flat_points[pos_inds]
+            pos_decoded_bbox_preds = distance2bbox(pos_points, pos_bbox_preds)
+            pos_decoded_target_preds = distance2bbox(pos_points, pos_bbox_targets)
+            loss_reg = ((iou_loss(pos_decoded_bbox_preds, pos_decoded_target_preds,
+                                  reduction='none') * pos_centerness_targets).sum() /
+                        pos_centerness_targets.sum())[None]
+            loss_centerness = F.binary_cross_entropy_with_logits(
+                pos_centerness, pos_centerness_targets, reduction='mean')[None]
+        else:
+            loss_reg = pos_bbox_preds.sum()[None]
+            loss_centerness = pos_centerness.sum()[None]
+        return dict(loss_cls=loss_cls, loss_reg=loss_reg, loss_centerness=loss_centerness)
+
+    # ------------------------------------------------------------------ inference
+    def get_bboxes_batched(self, cls_scores, bbox_preds, centernesses, img_metas, cfg,
+                           rescale=False):
+        """Device-side result of the whole batch: dets (B,max,5) (score = sigmoid(cls) *
+        sigmoid(centerness)), labels (B,max) int32, rows (B,max) int32, num (B) int32 -- no host
+        synchronisation."""
+        if not len(cls_scores) == len(bbox_preds) == len(centernesses) == len(self.strides):
+            raise AssertionError('level count mismatch')
+        nms_cfg = dict(cfg.nms)
+        nms_type = nms_cfg.pop('type', 'nms')
+        if nms_type != 'nms':
+            raise NotImplementedError('FCOSHead: test_cfg.nms.type %r (hard NMS only)' % nms_type)
+        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
+        shapes = [m['img_shape'] for m in img_metas]
+        factors = [m['scale_factor'] for m in img_metas]
+        return fcos_ops.point_ctr_get_bboxes(geom, [c.detach() for c in cls_scores],
+                                             [b.detach() for b in bbox_preds],
+                                             [c.detach() for c in centernesses], shapes, factors,
+                                             rescale, cfg.score_thr, nms_cfg['iou_thr'],
+                                             cfg.max_per_img)
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale=None):
+        """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64)"""
+        dets, labels, _, num = self.get_bboxes_batched(cls_scores, bbox_preds, centernesses,
                                                        img_metas, cfg, rescale)
         counts = num.tolist()
         return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]

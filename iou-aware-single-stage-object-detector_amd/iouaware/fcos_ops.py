@@ -1,5 +1,6 @@
-"""torch front-end of the IoU-aware FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip):
-the point head's post-conv path (ia_point_get_bboxes) and the towers' GroupNorm + ReLU.
+"""torch front-end of the FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip): the point
+heads' post-conv paths (ia_point_get_bboxes: IoU-aware; ia_point_ctr_get_bboxes: plain FCOS, the
+centerness map in the third slot) and the towers' GroupNorm + ReLU.
 Device tensors only, launched on the current torch stream, like ops.py."""
 import ctypes as C
 
@@ -48,7 +49,7 @@ class PointGeometry(object):
         return t
 
 
-def _point_ptrs(geom, cls, reg, iou):
+def _point_ptrs(geom, cls, reg, iou, third='iou_pred'):
     if not (len(cls) == len(reg) == len(iou) == geom.L):
         raise AssertionError('expected %d levels' % geom.L)
     B = cls[0].shape[0]
@@ -56,7 +57,7 @@ def _point_ptrs(geom, cls, reg, iou):
     for l in range(geom.L):
         h, w = geom.featmap_sizes[l]
         for name, t, ch in (('cls_score', cls[l], geom.C), ('bbox_pred', reg[l], 4),
-                            ('iou_pred', iou[l], 1)):
+                            (third, iou[l], 1)):
             _require_gpu(t, name)
             if tuple(t.shape) != (B, ch, h, w):
                 raise AssertionError('%s level %d has shape %s, expected %s'
@@ -111,15 +112,27 @@ def point_decode_stage(geom, cls, reg, iou, img_shapes, scale_factors, rescale):
     return _views(geom, B, ws)
 
 
-def point_get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_thr, iou_thr,
-                     max_per_img, lazy=True, debug=False):
-    """Whole post-conv path of the point head for a batch -> device tensors dets (B,max,5),
-    labels (B,max) int32, rows (B,max) int32 (candidate rows), num (B) int32 (+ the decode-stage
-    views with debug=True)."""
+def point_ctr_decode_stage(geom, cls, reg, ctr, img_shapes, scale_factors, rescale, score_thr):
+    """plain FCOS decode stage -> the views of point_decode_stage; scores_t holds
+    sigmoid(cls) * sigmoid(ctr) where sigmoid(cls) > score_thr and a negative sentinel elsewhere"""
+    cls, reg, ctr = list(cls), list(reg), list(ctr)
+    p, B, geom = _point_ptrs(geom, cls, reg, ctr, 'centerness')
+    dev = cls[0].device
+    nbytes, ws = _workspace(geom, B, dev)
+    hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
+    _lib.check(_lib.lib().ia_point_ctr_decode_stage(geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf),
+                                                    int(bool(rescale)), float(score_thr), _ptr(ws),
+                                                    nbytes, _stream()),
+               'ia_point_ctr_decode_stage')
+    return _views(geom, B, ws)
+
+
+def _get_bboxes(entry, third, geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_thr,
+                iou_thr, max_per_img, lazy, debug):
     if max_per_img > _lib.IA_MAX_PER_IMG:
         raise _lib.IouAwareLibraryError('max_per_img above %d' % _lib.IA_MAX_PER_IMG)
     cls, reg, iou = list(cls), list(reg), list(iou)
-    p, B, geom = _point_ptrs(geom, cls, reg, iou)
+    p, B, geom = _point_ptrs(geom, cls, reg, iou, third)
     dev = cls[0].device
     nbytes, ws = _workspace(geom, B, dev)
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
@@ -127,13 +140,31 @@ def point_get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, sc
     labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
     rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
     num = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().ia_point_get_bboxes(
+    _lib.check(getattr(_lib.lib(), entry)(
         geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf), int(bool(rescale)), float(score_thr),
         float(iou_thr), int(max_per_img), 0 if lazy else -1, _ptr(ws), nbytes, _ptr(dets),
-        _ptr(labels), _ptr(rows), _ptr(num), _stream()), 'ia_point_get_bboxes')
+        _ptr(labels), _ptr(rows), _ptr(num), _stream()), entry)
     if not debug:
         return dets, labels, rows, num
     return dets, labels, rows, num, _views(geom, B, ws)
+
+
+def point_get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_thr, iou_thr,
+                     max_per_img, lazy=True, debug=False):
+    """Whole post-conv path of the point head for a batch -> device tensors dets (B,max,5),
+    labels (B,max) int32, rows (B,max) int32 (candidate rows), num (B) int32 (+ the decode-stage
+    views with debug=True)."""
+    return _get_bboxes('ia_point_get_bboxes', 'iou_pred', geom, cls, reg, iou, img_shapes,
+                       scale_factors, rescale, score_thr, iou_thr, max_per_img, lazy, debug)
+
+
+def point_ctr_get_bboxes(geom, cls, reg, ctr, img_shapes, scale_factors, rescale, score_thr,
+                         iou_thr, max_per_img, lazy=True, debug=False):
+    """point_get_bboxes for plain FCOS (ia_point_ctr_get_bboxes): the raw score sigmoid(cls) is
+    thresholded, NMS and the final sort run on sigmoid(cls) * sigmoid(ctr); geom.score_alpha is
+    not used."""
+    return _get_bboxes('ia_point_ctr_get_bboxes', 'centerness', geom, cls, reg, ctr, img_shapes,
+                       scale_factors, rescale, score_thr, iou_thr, max_per_img, lazy, debug)
 
 
 def _wino_geom(xs):

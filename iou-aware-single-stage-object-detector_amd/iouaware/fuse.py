@@ -434,8 +434,9 @@ def _head_forward(self, feats):
 
 
 def _fcos_head_forward(self, feats):
-    """IoUawareFCOSHead at inference (eval, no grad, fp32 channels-last): the Winograd towers with
-    the HIP GroupNorm + ReLU (winograd.WinogradFCOSHead); anything else: the module's forward"""
+    """IoUawareFCOSHead / FCOSHead at inference (eval, no grad, fp32 channels-last): the Winograd
+    towers with the HIP GroupNorm + ReLU (winograd.WinogradFCOSHead); anything else: the module's
+    forward"""
     w = self._ia_wino
     if (not self.training) and w.usable(feats):
         if getattr(self, '_ia_dirty', False) or self._ia_stamp != _stamp(self):
@@ -486,7 +487,7 @@ def _fold(m):
         from .winograd import WinogradHead
         m._ia_wino = WinogradHead(m)
         m._ia_c3 = None                           # bf16 weights are packed on the first bf16 call
-    elif type(m).__name__ == 'IoUawareFCOSHead':
+    elif type(m).__name__ in ('IoUawareFCOSHead', 'FCOSHead'):
         from .winograd import WinogradFCOSHead
         m._ia_wino = WinogradFCOSHead(m)
     elif isinstance(m, Bottleneck):
@@ -594,7 +595,7 @@ def _forward_for(m, winograd):
         return _fpn_forward if winograd else None
     if type(m).__name__ == 'IoUawareRetinaHead':
         return _head_forward if winograd else None
-    if type(m).__name__ == 'IoUawareFCOSHead':
+    if type(m).__name__ in ('IoUawareFCOSHead', 'FCOSHead'):
         return _fcos_head_forward if winograd else None
     for cls, fn in ((Bottleneck, _bottleneck_forward), (BasicBlock, _basic_forward),
                     (ResNet, _resnet_forward), (ConvModule, _convmodule_forward)):

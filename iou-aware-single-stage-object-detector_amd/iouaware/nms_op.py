@@ -70,11 +70,15 @@ def soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3):
 def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1,
                    score_factors=None):
     """multi_bboxes (n,4), multi_scores (n,C+1) with the background column first.
-    -> (bboxes (k,5), labels (k,) int64).  One batched launch for all classes."""
+    -> (bboxes (k,5), labels (k,) int64).  One batched launch for all classes.
+
+    score_factors (n,) (plain FCOS: sigmoid(centerness), bbox_nms.py:37-48): the threshold applies
+    to the RAW class score, the survivors' scores are then multiplied by their factor and NMS and
+    the max_num sort run on the product.  Factors must be finite and >= 0 (ValueError)."""
     if multi_bboxes.shape[1] != 4:
         raise NotImplementedError('class-specific boxes (n, C*4) are a two-stage feature')
     if score_factors is not None:
-        raise NotImplementedError('score_factors is unused on this path')
+        score_factors = _check_factors(score_factors, multi_scores.shape[0])
     cfg = dict(nms_cfg)
     nms_type = cfg.pop('type', 'nms')
     if nms_type not in ('nms', 'soft_nms'):
@@ -85,12 +89,16 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1,
     src = multi_bboxes.device
     if not multi_bboxes.is_cuda:                           # CPU inputs: staged to the device and back
         multi_bboxes, multi_scores = _stage(multi_bboxes), _stage(multi_scores)
+    if score_factors is not None:
+        score_factors = score_factors.to(multi_scores.device)
     cap = ops._lib.IA_MAX_PER_IMG
+    raw_thr = score_thr
     drop_last = max_num is None or max_num < 0
     if n > ops._lib.IA_MAX_CANDIDATES or (not drop_last and max_num > cap):
         # beyond the batched kernels' capacities: the reference's own structure, one NMS per class
         # (bbox_nms.py:33-56) on the single-problem entry, which takes any n
-        b, l = _multiclass_nms_per_class(multi_bboxes, multi_scores, score_thr, nms_type, cfg, max_num)
+        b, l = _multiclass_nms_per_class(multi_bboxes, multi_scores, raw_thr, nms_type, cfg, max_num,
+                                         score_factors)
         return b.to(src), l.to(src)
     if drop_last:
         # reference quirk (bbox_nms.py:52-56): `shape[0] > -1` is always true, so ALL survivors
@@ -105,6 +113,13 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1,
     Rs = (n + 63) // 64 * 64
     scores_t = multi_bboxes.new_zeros((1, Cn, Rs), dtype=torch.float32)
     scores_t[0, :, :n] = multi_scores[:, 1:].t().to(torch.float32)
+    if score_factors is not None:
+        # raw score > score_thr -> the product (>= 0), else a negative sentinel; the kernels then
+        # run at a threshold between the two, which every product passes and no sentinel does
+        raw = scores_t[0, :, :n]
+        prod = raw * score_factors.to(torch.float32)[None, :]
+        scores_t[0, :, :n] = torch.where(raw > score_thr, prod, prod.new_full((), _SENTINEL))
+        score_thr = _STAGE_THR
     boxes = multi_bboxes.to(torch.float32).reshape(1, n, 4)
     if nms_type == 'soft_nms':
         kw = dict(cfg)
@@ -116,7 +131,8 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1,
     if drop_last:
         if k >= cap:
             # more survivors than the batched kernel's output holds: the per-class route
-            b, l = _multiclass_nms_per_class(multi_bboxes, multi_scores, score_thr, nms_type, cfg, max_num)
+            b, l = _multiclass_nms_per_class(multi_bboxes, multi_scores, raw_thr, nms_type, cfg, max_num,
+                                             score_factors)
             return b.to(src), l.to(src)
         dets, labels = out[0][0, :k], out[1][0, :k].to(torch.long)
         # stable: equal scores keep their concatenation order (class ascending, row ascending)
@@ -125,7 +141,24 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1,
     return out[0][0, :k].to(src), out[1][0, :k].to(torch.long).to(src)
 
 
-def _multiclass_nms_per_class(multi_bboxes, multi_scores, score_thr, nms_type, cfg, max_num):
+# multiclass_nms(score_factors=): the score of a pair whose raw score fails score_thr, and the
+# threshold the batched kernels then run at (as ia_point_ctr_get_bboxes does)
+_SENTINEL, _STAGE_THR = -1.0, -0.5
+
+
+def _check_factors(f, n):
+    if not isinstance(f, torch.Tensor):
+        f = torch.as_tensor(np.asarray(f, np.float32))
+    f = f.reshape(-1)
+    if f.numel() != n:
+        raise ValueError('score_factors: %d values for %d boxes' % (f.numel(), n))
+    if n and not bool((torch.isfinite(f) & (f >= 0)).all()):
+        raise ValueError('score_factors must be finite and >= 0')
+    return f
+
+
+def _multiclass_nms_per_class(multi_bboxes, multi_scores, score_thr, nms_type, cfg, max_num,
+                              score_factors=None):
     """multiclass_nms as the reference writes it (bbox_nms.py:33-56): a loop over the classes,
     one single-problem NMS each (ia_nms takes any n; soft-NMS up to IA_MAX_CANDIDATES per class),
     class-major concatenation, then the score sort when more than max_num survive (with
@@ -138,7 +171,10 @@ def _multiclass_nms_per_class(multi_bboxes, multi_scores, score_thr, nms_type, c
         cls_inds = multi_scores[:, i] > score_thr
         if not bool(cls_inds.any()):
             continue
-        cls_dets = torch.cat([multi_bboxes[cls_inds, :], multi_scores[cls_inds, i, None]], dim=1)
+        _scores = multi_scores[cls_inds, i]
+        if score_factors is not None:                       # bbox_nms.py:46-47: raw threshold, then the product
+            _scores = _scores * score_factors[cls_inds].to(_scores.dtype)
+        cls_dets = torch.cat([multi_bboxes[cls_inds, :], _scores[:, None]], dim=1)
         if nms_type == 'soft_nms':
             cls_dets, _ = soft_nms(cls_dets, **cfg)
         else:

@@ -312,11 +312,12 @@ class WinogradHead(object):
 
 
 class WinogradFCOSHead(object):
-    """the GN conv towers and output convolutions of an IoUawareFCOSHead, all levels at once:
-    every tower layer is a Winograd convolution without bias / ReLU followed by the HIP GroupNorm +
-    ReLU over both towers (csrc/groupnorm.hip: 2 x num_groups groups, the two towers' affine
-    parameters side by side); outputs fcos_cls | fcos_centerness on the cls tower,
-    fcos_reg | fcos_iou on the reg tower, then exp(scale_l * reg) per level in place."""
+    """the GN conv towers and output convolutions of an IoUawareFCOSHead or a plain FCOSHead, all
+    levels at once: every tower layer is a Winograd convolution without bias / ReLU followed by the
+    HIP GroupNorm + ReLU over both towers (csrc/groupnorm.hip: 2 x num_groups groups, the two
+    towers' affine parameters side by side); outputs fcos_cls | fcos_centerness on the cls tower,
+    fcos_reg | fcos_iou (plain head: fcos_reg alone) on the reg tower, then exp(scale_l * reg) per
+    level in place."""
 
     def __init__(self, head):
         convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
@@ -351,19 +352,23 @@ class WinogradFCOSHead(object):
         dev = self.u0.device
 
         def pair(a, b):
-            """two output convolutions on one tower: (U (36, F, n_pad), bias (n_pad,), n_a, n_b)"""
-            na, nb = a.out_channels, b.out_channels
+            """one or two output convolutions on one tower: (U (36, F, n_pad), bias (n_pad,),
+            n_a, n_b); b None: n_b = 0"""
+            na, nb = a.out_channels, (0 if b is None else b.out_channels)
             n_pad = (na + nb + 15) // 16 * 16
             u = torch.zeros((36, F, n_pad), dtype=torch.float32, device=dev)
             u[:, :, :na] = transform_weight(a.weight)
-            u[:, :, na:na + nb] = transform_weight(b.weight)
             bias = torch.zeros(n_pad, dtype=torch.float32, device=dev)
             bias[:na] = a.bias.detach().float()
-            bias[na:na + nb] = b.bias.detach().float()
+            if b is not None:
+                u[:, :, na:na + nb] = transform_weight(b.weight)
+                bias[na:na + nb] = b.bias.detach().float()
             return u.contiguous(), bias.contiguous(), na, nb
 
         self.u_cc, self.b_cc, self.c_cls, self.c_ctr = pair(head.fcos_cls, head.fcos_centerness)
-        self.u_ri, self.b_ri, self.c_reg, self.c_iou = pair(head.fcos_reg, head.fcos_iou)
+        # the plain FCOSHead has no IoU branch: its reg tower feeds fcos_reg alone (c_iou = 0)
+        self.u_ri, self.b_ri, self.c_reg, self.c_iou = pair(head.fcos_reg,
+                                                            getattr(head, 'fcos_iou', None))
         if self.c_reg % 4:
             raise ValueError('the regression output needs a multiple of 4 channels')
         self.scales = torch.stack([s.scale.detach().float() for s in head.scales]).contiguous()
@@ -381,7 +386,7 @@ class WinogradFCOSHead(object):
 
     def __call__(self, feats):
         """feats: per-level (B, Cin, H, W) channels-last fp32 -> (cls[L], bbox[L], centerness[L],
-        iou[L]), channels-last"""
+        iou[L]) (plain head: (cls[L], bbox[L], centerness[L])), channels-last"""
         B = feats[0].shape[0]
         sizes = [tuple(x.shape[-2:]) for x in feats]
         key = (B, tuple(sizes), feats[0].device, stream_id())
@@ -402,19 +407,24 @@ class WinogradFCOSHead(object):
         v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
         new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=feats[0].device,  # noqa: E731
                                      memory_format=torch.channels_last) for (h, w) in sizes]
-        cls, ctr, reg, iou = new(self.c_cls), new(self.c_ctr), new(self.c_reg), new(self.c_iou)
+        cls, ctr, reg = new(self.c_cls), new(self.c_ctr), new(self.c_reg)
+        iou = new(self.c_iou) if self.c_iou else None
         n_cc, n_ri = self.u_cc.shape[2], self.u_ri.shape[2]
         m_cc = batched_gemm(v[:36], self.u_cc, plan.buf('mc', (36, T, n_cc)))
         output_transform(plan, m_cc, n_cc, 1, self.b_cc, False,
                          [(0, self.c_cls, cls, 0), (self.c_cls, self.c_ctr, ctr, 0)])
         m_ri = batched_gemm(v[36:], self.u_ri, plan.buf('mr', (36, T, n_ri)))
-        output_transform(plan, m_ri, n_ri, 1, self.b_ri, False,
-                         [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
+        segs = [(0, self.c_reg, reg, 0)]
+        if iou is not None:
+            segs.append((self.c_reg, self.c_iou, iou, 0))
+        output_transform(plan, m_ri, n_ri, 1, self.b_ri, False, segs)
         ptrs = (C.c_void_p * len(reg))(*[t.data_ptr() for t in reg])
         _lib.check(_lib.lib().ia_scale_exp_levels(C.byref(plan.geom), ptrs, self.c_reg,
                                                   _ptr(self.scales), _stream()),
                    'ia_scale_exp_levels')
         self.calls += 1
+        if iou is None:
+            return cls, reg, ctr
         return cls, reg, ctr, iou
 
 

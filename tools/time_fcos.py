@@ -1,10 +1,12 @@
-"""Time the IoU-aware FCOS whole path (backbone -> FPN -> head -> ia_point_get_bboxes) at batch 8,
+"""Time the FCOS whole path (backbone -> FPN -> head -> ia_point_get_bboxes, or for the plain
+FCOSHead with --head plain ia_point_ctr_get_bboxes) at batch 8,
 1333 x 800 (800 x 1344 padded), fp32: the module route (torch GroupNorm towers, MIOpen
 convolutions) against the fused route (fuse_inference(winograd=True), channels-last: Winograd
 towers + the HIP GroupNorm + ReLU), and the GroupNorm kernels alone on one tower layer's
 activations (both towers, 512 channels, all five levels) with their share of the HBM bound.
 
-    python tools/time_fcos.py [--batch 8] [--iters 20] [--warmup 5] [--out results.json]
+    python tools/time_fcos.py [--head {iou_aware,plain}] [--batch 8] [--iters 20] [--warmup 5]
+                              [--out results.json]
 
 Device events around the timed window, after warm-up of every shape; the detections of the two
 routes are compared on the same input (name-seeded weights, tests/synth_fcos.py)."""
@@ -23,7 +25,10 @@ for p in (os.path.join(ROOT, 'iou-aware-single-stage-object-detector_amd'), os.p
 HBM_PEAK = 8.0e12            # MI355X HBM3E, spec (bytes / s)
 
 
-def build(seed=5):
+HEADS = dict(iou_aware='IoUawareFCOSHead', plain='FCOSHead')
+
+
+def build(seed=5, head='iou_aware'):
     import iouaware
     from iouaware.config import ConfigDict
     import synth_fcos
@@ -34,7 +39,7 @@ def build(seed=5):
         neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
                   add_extra_convs=True, extra_convs_on_inputs=False, num_outs=5,
                   relu_before_extra_convs=True),
-        bbox_head=dict(type='IoUawareFCOSHead', num_classes=81, in_channels=256, stacked_convs=4,
+        bbox_head=dict(type=HEADS[head], num_classes=81, in_channels=256, stacked_convs=4,
                        feat_channels=256, strides=[8, 16, 32, 64, 128]))
     test_cfg = dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_thr=0.5),
                     max_per_img=100)
@@ -62,6 +67,7 @@ def time_fn(fn, iters, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--head', choices=sorted(HEADS), default='iou_aware')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
@@ -78,7 +84,9 @@ def main():
     meta = [dict(ori_shape=(800, 1333, 3), img_shape=(800, 1333, 3), pad_shape=(pad_h, pad_w, 3),
                  scale_factor=1.0, flip=False)] * B
     res = dict(batch=B, pad=[pad_h, pad_w])
-    m = build()
+    if a.head != 'iou_aware':
+        res['head'] = a.head
+    m = build(head=a.head)
     with torch.no_grad():
         run = lambda xx: m.simple_test_device(xx, meta, rescale=True)    # noqa: E731
         res['module_ms'] = time_fn(lambda: run(x), a.iters, a.warmup)
@@ -93,6 +101,12 @@ def main():
         same = [int(min(p, q)) for p, q in zip(n0.tolist(), n1.tolist())]
         res['max_det_diff'] = max(float((d0[b, :k] - d1[b, :k]).abs().max()) if k else 0.0
                                   for b, k in enumerate(same))
+        if a.head != 'iou_aware':
+            # rank-wise score difference: insensitive to the order of near-equal scores (the plain
+            # head's products are close together, neighbours can swap between the routes)
+            res['max_sorted_score_diff'] = max(
+                float((d0[b, :k, 4].sort()[0] - d1[b, :k, 4].sort()[0]).abs().max()) if k else 0.0
+                for b, k in enumerate(same))
         # GroupNorm + ReLU alone: one tower layer (both towers, 512 channels, five levels)
         sizes = synth_fcos.level_shapes(pad_h, pad_w)
         acts = [torch.randn((B, 512, h, w), device='cuda').contiguous(memory_format=torch.channels_last)
