@@ -47,6 +47,8 @@ extern "C" {
 
 #define IA_CLS_SIGMOID 0
 #define IA_CLS_SOFTMAX 1
+#define IA_CLS_SIGMOID_NOIOU 2   /* plain RetinaNet (retina_head.py): no IoU map, score = sigmoid(cls) */
+#define IA_CLS_SOFTMAX_NOIOU 3   /* plain RetinaNet, use_sigmoid_cls=False: score = softmax(cls) */
 
 #define IA_LOSS_SLOTS 64     /* partial sums written by the *_fwd loss kernels */
 
@@ -76,12 +78,19 @@ typedef struct ia_head_geom {
      * the background; score_c = sqrt(softmax(x)_{c+1}) * sqrt(sigmoid(iou)) for c = 0..C-1 and the
      * row maximum runs over the foreground columns only (scores[:, 1:].max).  Everything behind the
      * gather (NMS, labels) is the same.  Covers the inference entries (row-max, top-k, gather,
-     * ia_get_bboxes*, ia_decode_stage); the loss entries are sigmoid-only.                       */
+     * ia_get_bboxes*, ia_decode_stage); the loss entries are sigmoid-only.
+     * IA_CLS_SIGMOID_NOIOU / IA_CLS_SOFTMAX_NOIOU: the plain RetinaHead (retina_head.py, scores as in
+     * anchor_head.py:364-450): no IoU branch, score_c = sigmoid(x_c), resp. softmax(x)_{c+1} with the
+     * row maximum over the foreground columns; the ranking is by these values (equal scores from
+     * different logits tie, lower index first).  Every p->iou[l] must be NULL with these kinds and
+     * non-NULL with the IoU-aware ones (IA_E_ARG otherwise).  Inference entries only: the fused
+     * head-loss entries (ia_head_loss_*) take IA_CLS_SIGMOID alone.                               */
     int32_t cls_activation;
 } ia_head_geom;
 
 /* Per-level device pointers of the three head outputs, each (B, ch, H, W).  The plain FCOS entries
- * (ia_point_ctr_*) carry the centerness map (B, 1, H, W) in the iou slot. */
+ * (ia_point_ctr_*) carry the centerness map (B, 1, H, W) in the iou slot; the plain RetinaNet kinds
+ * (IA_CLS_*_NOIOU) leave it NULL. */
 typedef struct ia_level_ptrs {
     const void *cls[IA_MAX_LEVELS];
     const void *reg[IA_MAX_LEVELS];
@@ -100,9 +109,9 @@ const char *ia_version(void);
  * (mmdet/core/post_processing/bbox_nms.py:6-67).                             */
 
 /* iou_aware_retina_head.py:502-531,539: per anchor max over classes of
- * sqrt(sigmoid(cls)) * sqrt(sigmoid(iou)).  rowmax: (B, N) fp32; inside an image
- * each level is an (A, H*W) block (anchor-major), i.e. element a*HW + p holds the
- * reference's anchor index p*A + a (IA_LAYOUT_NCHW), or the reference's own order
+ * sqrt(sigmoid(cls)) * sqrt(sigmoid(iou)) (IA_CLS_SIGMOID_NOIOU: of sigmoid(cls)).
+ * rowmax: (B, N) fp32; inside an image each level is an (A, H*W) block (anchor-major), i.e.
+ * element a*HW + p holds the reference's anchor index p*A + a (IA_LAYOUT_NCHW), or the reference's own order
  * p*A + a (IA_LAYOUT_NHWC).  ia_select_topk reads whichever g->layout implies.   */
 int ia_decode_fuse_rowmax(const ia_head_geom *g, const ia_level_ptrs *p, int batch, int dtype,
                           float *rowmax, void *stream);

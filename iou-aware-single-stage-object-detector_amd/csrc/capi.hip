@@ -124,7 +124,7 @@ int ia_decode_fuse_rowmax_grouped(const ia_head_geom *g, const ia_level_ptrs *p,
     if (workspace_bytes < ia::select_workspace_bytes(t, batch)) return IA_E_WORKSPACE;
     float *groupmax = ia::select_workspace_groupmax(t, batch, select_workspace);
     rc = ia::launch_rowmax(t, *p, batch, dtype, rowmax, (hipStream_t)stream, groupmax);
-    if (!rc && t.softmax)       // the softmax row-score kernel does not emit the group maxima
+    if (!rc && t.softmax())     // the softmax row-score kernel does not emit the group maxima
         rc = ia::launch_groupmax(t, rowmax, batch, select_workspace, (hipStream_t)stream);
     return rc;
 }

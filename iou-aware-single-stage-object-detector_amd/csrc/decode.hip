@@ -21,7 +21,13 @@
 // sqrt(sigmoid(.)) is monotone non-decreasing in
 // fp32 (exhaustively checked by tests/test_oracle_math.py), so the max over
 // classes is taken on the raw logits and the transcendental part runs once
-// per anchor instead of once per class.
+// per anchor instead of once per class.  The same holds for sigmoid(.) alone
+// (tests/test_gpu_retina_plain.py checks the device function over every float
+// of [-110, 100]).
+//
+// Score kind (template parameter IOU, ia_head_geom.cls_activation): IOU = true is the IoU-aware
+// score sqrt(sigmoid(cls)) * sqrt(sigmoid(iou)); IOU = false the plain RetinaNet score
+// sigmoid(cls) (softmax(cls) on the softmax kernels), with no IoU map read.
 #include "ia_internal.hpp"
 #include "ia_math.hpp"
 #include "ia_rowmax_dev.hpp"
@@ -48,7 +54,7 @@ struct RowmaxArgs {
 // levels' streaming instead of forming a tail.  Loads are never predicated:
 // out-of-range lanes read a clamped in-range address and drop the result, which
 // keeps the class loop a straight, software-pipelined run of independent loads.
-template <typename T>
+template <typename T, bool IOU>
 __global__ void __launch_bounds__(64) k_rowmax(RowmaxArgs a)
 {
     constexpr int PPL = Lane<T>::PPL;
@@ -66,7 +72,7 @@ __global__ void __launch_bounds__(64) k_rowmax(RowmaxArgs a)
     const int an = rem / tiles;
     const int p0 = (rem - an * tiles) * TILE;
     const T *cls = static_cast<const T *>(a.p.cls[l]) + ((size_t)b * A + an) * C * HW;
-    const T *iou = static_cast<const T *>(a.p.iou[l]) + ((size_t)b * A + an) * HW;
+    const T *iou = IOU ? static_cast<const T *>(a.p.iou[l]) + ((size_t)b * A + an) * HW : nullptr;
     // row-max array: per level an (A, HW) block, anchor-major -> contiguous, full-line stores
     float *out = a.rowmax + (size_t)b * a.anchors_per_img + a.t.anchor_off[l] + (size_t)an * HW;
 
@@ -88,7 +94,7 @@ __global__ void __launch_bounds__(64) k_rowmax(RowmaxArgs a)
 #pragma unroll
             for (int j = 0; j < PPL; ++j) m[j] = (m[j] < v[j]) ? v[j] : m[j];
         }
-        Lane<T>::load(iou + pc, il);
+        if (IOU) Lane<T>::load(iou + pc, il);
     } else {
         int pc[PPL];
 #pragma unroll
@@ -105,13 +111,15 @@ __global__ void __launch_bounds__(64) k_rowmax(RowmaxArgs a)
                 m[j] = (m[j] < v) ? v : m[j];
             }
         }
+        if (IOU) {
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) il[j] = load_f32<T>(iou + pc[j]);
+            for (int j = 0; j < PPL; ++j) il[j] = load_f32<T>(iou + pc[j]);
+        }
     }
     float sc[PPL];
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
-        sc[j] = sqrt_sigmoidf_(m[j]) * sqrt_sigmoidf_(il[j]);
+        sc[j] = IOU ? sqrt_sigmoidf_(m[j]) * sqrt_sigmoidf_(il[j]) : sigmoidf_(m[j]);
         if (pos[j] < HW) out[pos[j]] = sc[j];
         else sc[j] = 0.0f;                                  // scores are >= 0
     }
@@ -157,7 +165,7 @@ __global__ void __launch_bounds__(64) k_rowmax(RowmaxArgs a)
 // fully coalesced, non-temporal 16-byte loads per lane (1 KiB per instruction); lane maxima
 // are transposed through LDS (row stride VPR+1: conflict-free) so that lane r reduces row r,
 // and the row maxima are stored in row order p*A + a, 256 B per wavefront.
-template <typename T, int VPR_T>         // VPR_T = 0: run-time vectors per row
+template <typename T, int VPR_T, bool IOU>         // VPR_T = 0: run-time vectors per row
 __global__ void __launch_bounds__(64) k_rowmax_nhwc(RowmaxNhwcArgs a)
 {
     __shared__ float s_m[64 * ((VPR_T ? VPR_T : kMaxVpr) + 1)];
@@ -165,7 +173,7 @@ __global__ void __launch_bounds__(64) k_rowmax_nhwc(RowmaxNhwcArgs a)
     while (rem >= a.blk_off[rl + 1]) ++rl;
     rem -= a.blk_off[rl];
     const int l = a.big_first ? rl : a.t.num_levels - 1 - rl;
-    rowmax_nhwc_wave<T, VPR_T, false>(a, l, rem, s_m, (int)threadIdx.x);
+    rowmax_nhwc_wave<T, VPR_T, false, IOU>(a, l, rem, s_m, (int)threadIdx.x);
 }
 
 // unused dynamic LDS per workgroup = an occupancy cap for the streaming kernel (tools/ubench/
@@ -199,13 +207,19 @@ static int launch_rowmax_nhwc(const LevelTable &t, const ia_level_ptrs &p, int b
     dim3 grid((unsigned)a.blk_off[t.num_levels]);
     const int vpr = t.C / ppl;
     const size_t pad = (size_t)rowmax_nhwc_lds_pad;
-    if (dtype == IA_F32) {
-        if (vpr == 20) hipLaunchKernelGGL((k_rowmax_nhwc<float, 20>), grid, dim3(64), pad, s, a);
-        else hipLaunchKernelGGL((k_rowmax_nhwc<float, 0>), grid, dim3(64), pad, s, a);
-    } else {
-        if (vpr == 10) hipLaunchKernelGGL((k_rowmax_nhwc<uint16_t, 10>), grid, dim3(64), pad, s, a);
-        else hipLaunchKernelGGL((k_rowmax_nhwc<uint16_t, 0>), grid, dim3(64), pad, s, a);
-    }
+#define IA_ROWMAX_NHWC_LAUNCH(IOU)                                                                  \
+    do {                                                                                            \
+        if (dtype == IA_F32) {                                                                      \
+            if (vpr == 20) hipLaunchKernelGGL((k_rowmax_nhwc<float, 20, IOU>), grid, dim3(64), pad, s, a); \
+            else hipLaunchKernelGGL((k_rowmax_nhwc<float, 0, IOU>), grid, dim3(64), pad, s, a);     \
+        } else {                                                                                    \
+            if (vpr == 10) hipLaunchKernelGGL((k_rowmax_nhwc<uint16_t, 10, IOU>), grid, dim3(64), pad, s, a); \
+            else hipLaunchKernelGGL((k_rowmax_nhwc<uint16_t, 0, IOU>), grid, dim3(64), pad, s, a);  \
+        }                                                                                           \
+    } while (0)
+    if (t.iou()) IA_ROWMAX_NHWC_LAUNCH(true);
+    else IA_ROWMAX_NHWC_LAUNCH(false);
+#undef IA_ROWMAX_NHWC_LAUNCH
     return hip_status(hipGetLastError());
 }
 
@@ -218,7 +232,8 @@ static int launch_rowmax_nhwc(const LevelTable &t, const ia_level_ptrs &p, int b
 // sqrt(sigmoid(iou)).  Correctly rounded division, square root and the product with a value >= 0
 // are non-decreasing, so the maximum over c of score_c is the score of the largest exp(x_c - m).
 // None of the four IoU-aware configs takes this branch: one thread per anchor row, both memory
-// orders, no tuning -- a correct path, not a streaming kernel.
+// orders, no tuning -- a correct path, not a streaming kernel.  IOU = false (IA_CLS_SOFTMAX_NOIOU,
+// anchor_head.py:375-376,387-388): score_c = exp(x_c - m) / s, no square root, no IoU map.
 struct SoftmaxRowArgs {
     LevelTable t;
     ia_level_ptrs p;
@@ -242,7 +257,7 @@ __device__ __forceinline__ void softmax_row_stats(const T *x, size_t cs, int Cin
     }
 }
 
-template <typename T>
+template <typename T, bool IOU>
 __global__ void __launch_bounds__(256) k_rowscore_softmax(SoftmaxRowArgs a)
 {
     const int l = (int)blockIdx.y % a.t.num_levels, b = (int)blockIdx.y / a.t.num_levels;
@@ -259,7 +274,7 @@ __global__ void __launch_bounds__(256) k_rowscore_softmax(SoftmaxRowArgs a)
     float m, s, e;
     softmax_row_stats<T>(cls, cs, Cin, m, s, e);
     a.rowmax[(size_t)b * a.anchors_per_img + a.t.anchor_off[l] + i] =
-        __builtin_sqrtf(e / s) * sqrt_sigmoidf_(load_f32<T>(iou));
+        IOU ? __builtin_sqrtf(e / s) * sqrt_sigmoidf_(load_f32<T>(iou)) : e / s;
 }
 
 static int launch_rowscore_softmax(const LevelTable &t, const ia_level_ptrs &p, int batch, int dtype,
@@ -274,8 +289,13 @@ static int launch_rowscore_softmax(const LevelTable &t, const ia_level_ptrs &p, 
     }
     if ((int64_t)batch * t.num_levels > 65535) return IA_E_ARG;
     const dim3 grid((unsigned)((nmax + 255) / 256), (unsigned)(batch * t.num_levels));
-    if (dtype == IA_F32) hipLaunchKernelGGL(k_rowscore_softmax<float>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_rowscore_softmax<uint16_t>, grid, dim3(256), 0, s, a);
+    if (t.iou()) {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_rowscore_softmax<float, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_rowscore_softmax<uint16_t, true>), grid, dim3(256), 0, s, a);
+    } else {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_rowscore_softmax<float, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_rowscore_softmax<uint16_t, false>), grid, dim3(256), 0, s, a);
+    }
     return hip_status(hipGetLastError());
 }
 
@@ -284,7 +304,8 @@ int launch_rowmax(const LevelTable &t, const ia_level_ptrs &p, int batch, int dt
 {
     if (batch < 1 || !rowmax) return IA_E_ARG;
     if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
-    if (t.softmax) {
+    if (int rc = check_iou_ptrs(t, p)) return rc;
+    if (t.softmax()) {
         // (group maxima, when wanted, are derived from the finished array by the caller:
         // launch_groupmax -- this kernel does not emit them)
         (void)groupmax;
@@ -308,8 +329,13 @@ int launch_rowmax(const LevelTable &t, const ia_level_ptrs &p, int batch, int dt
     a.blocks_per_img = a.blk_off[t.num_levels];
     a.anchors_per_img = t.anchor_off[t.num_levels];
     dim3 grid((unsigned)(a.blocks_per_img * batch));
-    if (dtype == IA_F32) hipLaunchKernelGGL(k_rowmax<float>, grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_rowmax<uint16_t>, grid, dim3(64), 0, s, a);
+    if (t.iou()) {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_rowmax<float, true>), grid, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((k_rowmax<uint16_t, true>), grid, dim3(64), 0, s, a);
+    } else {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_rowmax<float, false>), grid, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((k_rowmax<uint16_t, false>), grid, dim3(64), 0, s, a);
+    }
     return hip_status(hipGetLastError());
 }
 
@@ -321,7 +347,7 @@ namespace ia {
 
 constexpr int kGroups = 4;   // class groups per candidate (threadIdx.y)
 
-template <typename T>
+template <typename T, bool IOU>
 __global__ void __launch_bounds__(64 * kGroups) k_gather(GatherArgs a)
 {
     __shared__ float gmax[kGroups][64];
@@ -344,7 +370,7 @@ __global__ void __launch_bounds__(64 * kGroups) k_gather(GatherArgs a)
                    (nhwc ? row * C : ((size_t)b * A + an) * C * HW + pos);
     const T *iou = static_cast<const T *>(lv.iou) +
                    (nhwc ? row : ((size_t)b * A + an) * HW + pos);
-    const float sq_iou = sqrt_sigmoidf_(load_f32<T>(iou));
+    const float sq_iou = IOU ? sqrt_sigmoidf_(load_f32<T>(iou)) : 1.0f;
     const int cpg = (C + kGroups - 1) / kGroups;
     const int c0 = grp * cpg;
     const int c1 = (c0 + cpg < C) ? (c0 + cpg) : C;
@@ -353,7 +379,7 @@ __global__ void __launch_bounds__(64 * kGroups) k_gather(GatherArgs a)
 #pragma unroll 4
     for (int c = c0; c < c1; ++c) {
         float x = load_f32<T>(cls + (size_t)c * cs);
-        float sc = sqrt_sigmoidf_(x) * sq_iou;
+        float sc = IOU ? sqrt_sigmoidf_(x) * sq_iou : sigmoidf_(x);
         if (live) so[(size_t)c * a.Rs] = sc;
         best = (best < sc) ? sc : best;
     }
@@ -397,7 +423,7 @@ __device__ unsigned long long g_gather_blk[8][160][4];      // per block: start,
 #define GPROF(i) do { } while (0)
 #endif
 
-template <typename T, int VT, int MAXL>
+template <typename T, int VT, int MAXL, bool IOU = true>
 __global__ void __launch_bounds__(1024) k_gather_nhwc(GatherArgs a, int tpc)
 {
     constexpr int PPL = Lane<T>::PPL;
@@ -423,7 +449,7 @@ __global__ void __launch_bounds__(1024) k_gather_nhwc(GatherArgs a, int tpc)
 #pragma unroll
     for (int u = 0; u < VT; ++u)
         Lane<T>::load_cached(static_cast<const T *>(lv.cls) + row * C + (w + u * tpc) * PPL, x[u]);
-    const float iou = load_f32<T>(static_cast<const T *>(lv.iou) + row);
+    const float iou = IOU ? load_f32<T>(static_cast<const T *>(lv.iou) + row) : 0.0f;
     // the first thread of a candidate also decodes its box (a few lanes of every wavefront,
     // ahead of the barrier, rather than one wavefront's worth behind it)
     const bool boxer = w == 0 && r_raw < a.R;
@@ -435,13 +461,13 @@ __global__ void __launch_bounds__(1024) k_gather_nhwc(GatherArgs a, int tpc)
         ba0 = ba[0]; ba1 = ba[1]; ba2 = ba[2]; ba3 = ba[3];
     }
     GPROF(2);
-    const float sq = sqrt_sigmoidf_(iou);
+    const float sq = IOU ? sqrt_sigmoidf_(iou) : 1.0f;
     float best = 0.0f;                                          // scores are >= 0
 #pragma unroll
     for (int u = 0; u < VT; ++u)
 #pragma unroll
         for (int j = 0; j < PPL; ++j) {
-            const float sc = sqrt_sigmoidf_(x[u][j]) * sq;
+            const float sc = IOU ? sqrt_sigmoidf_(x[u][j]) * sq : sigmoidf_(x[u][j]);
             s_tile[((w + u * tpc) * PPL + j) * (kGTile + 1) + cand] = sc;
             best = (best < sc) ? sc : best;
         }
@@ -467,7 +493,7 @@ __global__ void __launch_bounds__(1024) k_gather_nhwc(GatherArgs a, int tpc)
 
 // softmax head (see k_rowscore_softmax): one thread per candidate, the C foreground scores from the
 // C + 1 logits of its row, class-major like the other gather kernels; both memory orders
-template <typename T>
+template <typename T, bool IOU>
 __global__ void __launch_bounds__(64) k_gather_softmax(GatherArgs a)
 {
     const int b = blockIdx.y;
@@ -483,13 +509,14 @@ __global__ void __launch_bounds__(64) k_gather_softmax(GatherArgs a)
     const size_t row = ((size_t)b * HW + pos) * A + an;
     const T *cls = static_cast<const T *>(lv.cls) + (nhwc ? row * Cin : ((size_t)b * A + an) * Cin * HW + pos);
     const T *iou = static_cast<const T *>(lv.iou) + (nhwc ? row : ((size_t)b * A + an) * HW + pos);
-    const float sq_iou = sqrt_sigmoidf_(load_f32<T>(iou));
+    const float sq_iou = IOU ? sqrt_sigmoidf_(load_f32<T>(iou)) : 1.0f;
     float m, s, e_fg;
     softmax_row_stats<T>(cls, cs, Cin, m, s, e_fg);
     float *so = a.scores_t + (size_t)b * C * a.Rs + r;
     float best = 0.0f;
     for (int c = 0; c < C; ++c) {
-        const float sc = __builtin_sqrtf(expf_(load_f32<T>(cls + (size_t)(c + 1) * cs) - m) / s) * sq_iou;
+        const float p = expf_(load_f32<T>(cls + (size_t)(c + 1) * cs) - m) / s;
+        const float sc = IOU ? __builtin_sqrtf(p) * sq_iou : p;
         so[(size_t)c * a.Rs] = sc;
         best = (best < sc) ? sc : best;
     }
@@ -515,10 +542,17 @@ int launch_gather(const LevelTable &t, const BaseAnchors &ba, const float *means
     a.boxes = boxes; a.scores_t = scores_t; a.best_score = best_score;
     a.R = t.cand_off[t.num_levels]; a.Rs = Rs; a.rescale = rescale;
     if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
-    if (t.softmax) {
+    if (int rc = check_iou_ptrs(t, p)) return rc;
+    const bool iou = t.iou();
+    if (t.softmax()) {
         const dim3 grid((unsigned)((a.R + 63) / 64), (unsigned)batch);
-        if (dtype == IA_F32) hipLaunchKernelGGL(k_gather_softmax<float>, grid, dim3(64), 0, s, a);
-        else hipLaunchKernelGGL(k_gather_softmax<uint16_t>, grid, dim3(64), 0, s, a);
+        if (iou) {
+            if (dtype == IA_F32) hipLaunchKernelGGL((k_gather_softmax<float, true>), grid, dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((k_gather_softmax<uint16_t, true>), grid, dim3(64), 0, s, a);
+        } else {
+            if (dtype == IA_F32) hipLaunchKernelGGL((k_gather_softmax<float, false>), grid, dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((k_gather_softmax<uint16_t, false>), grid, dim3(64), 0, s, a);
+        }
         return hip_status(hipGetLastError());
     }
     const int esz = dtype == IA_F32 ? 4 : 2;
@@ -533,10 +567,14 @@ int launch_gather(const LevelTable &t, const BaseAnchors &ba, const float *means
             const int tpc = two ? vpr / 2 : vpr;               // threads per candidate
             const dim3 block((unsigned)(kGTile * tpc));
             const bool few = t.num_levels <= 5;                 // the usual P3..P7 pyramid
+#define IA_GATHER_LAUNCH2(TT, VT, IOU)                                                            \
+    do {                                                                                          \
+        if (few) hipLaunchKernelGGL((k_gather_nhwc<TT, VT, 5, IOU>), grid, block, lds, s, a, tpc); \
+        else hipLaunchKernelGGL((k_gather_nhwc<TT, VT, IA_MAX_LEVELS, IOU>), grid, block, lds, s, a, tpc); \
+    } while (0)
 #define IA_GATHER_LAUNCH(TT, VT)                                                                  \
     do {                                                                                          \
-        if (few) hipLaunchKernelGGL((k_gather_nhwc<TT, VT, 5>), grid, block, lds, s, a, tpc);      \
-        else hipLaunchKernelGGL((k_gather_nhwc<TT, VT, IA_MAX_LEVELS>), grid, block, lds, s, a, tpc); \
+        if (iou) IA_GATHER_LAUNCH2(TT, VT, true); else IA_GATHER_LAUNCH2(TT, VT, false);           \
     } while (0)
             if (dtype == IA_F32) {
                 if (two) IA_GATHER_LAUNCH(float, 2); else IA_GATHER_LAUNCH(float, 1);
@@ -544,14 +582,19 @@ int launch_gather(const LevelTable &t, const BaseAnchors &ba, const float *means
                 if (two) IA_GATHER_LAUNCH(uint16_t, 2); else IA_GATHER_LAUNCH(uint16_t, 1);
             }
 #undef IA_GATHER_LAUNCH
+#undef IA_GATHER_LAUNCH2
             return hip_status(hipGetLastError());
         }
     }
     dim3 block(64, kGroups);
     dim3 grid((unsigned)((a.R + 63) / 64), (unsigned)batch);
-    if (dtype == IA_F32) hipLaunchKernelGGL(k_gather<float>, grid, block, 0, s, a);
-    else if (dtype == IA_BF16) hipLaunchKernelGGL(k_gather<uint16_t>, grid, block, 0, s, a);
-    else return IA_E_ARG;
+    if (iou) {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_gather<float, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_gather<uint16_t, true>), grid, block, 0, s, a);
+    } else {
+        if (dtype == IA_F32) hipLaunchKernelGGL((k_gather<float, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_gather<uint16_t, false>), grid, block, 0, s, a);
+    }
     return hip_status(hipGetLastError());
 }
 

@@ -9,11 +9,14 @@ namespace ia {
 // per-level scalars used by kernels that do not need the base anchors
 struct LevelTable {
     int32_t num_levels, A, C, nms_pre, layout;
-    int32_t softmax;                         // IA_CLS_SOFTMAX: class tensors carry C + 1 channels per anchor
+    int32_t act;                             // ia_head_geom.cls_activation (IA_CLS_*; bit 0: softmax, bit 1: no IoU map)
     int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
     int32_t anchor_off[IA_MAX_LEVELS + 1];   // prefix of N_l   (anchors per image)
     int32_t cand_off[IA_MAX_LEVELS + 1];     // prefix of k_l   (candidates per image)
     int32_t tile_off[IA_MAX_LEVELS + 1];     // prefix of ceil(HW_l / 256) row-max tiles
+    // host-side dispatch: the kernels take the score kind as a template parameter
+    bool softmax() const { return (act & 1) != 0; }   // class tensors carry C + 1 channels per anchor
+    bool iou() const { return (act & 2) == 0; }       // score fused with sigmoid(iou); else sigmoid / softmax alone
 };
 
 struct BaseAnchors { float v[IA_MAX_LEVELS][IA_MAX_ANCHORS][4]; };
@@ -26,9 +29,9 @@ inline int make_level_table(const ia_head_geom *g, LevelTable &t)
     if (g->num_classes < 1 || g->num_classes > 4096) return IA_E_ARG;
     if (g->nms_pre > IA_MAX_NMS_PRE) return IA_E_LIMIT_NMS_PRE;
     if (g->layout != IA_LAYOUT_NCHW && g->layout != IA_LAYOUT_NHWC) return IA_E_ARG;
-    if (g->cls_activation != IA_CLS_SIGMOID && g->cls_activation != IA_CLS_SOFTMAX) return IA_E_ARG;
+    if (g->cls_activation < IA_CLS_SIGMOID || g->cls_activation > IA_CLS_SOFTMAX_NOIOU) return IA_E_ARG;
     t.layout = g->layout;
-    t.softmax = g->cls_activation == IA_CLS_SOFTMAX ? 1 : 0;
+    t.act = g->cls_activation;
     t.num_levels = g->num_levels; t.A = g->num_anchors; t.C = g->num_classes; t.nms_pre = g->nms_pre;
     t.anchor_off[0] = t.cand_off[0] = t.tile_off[0] = 0;
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
@@ -176,6 +179,15 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
                         float *rowmax, int32_t *cand_idx, void *select_ws, float *boxes,
                         float *scores_t, float *best_score, int Rs, int kind, float score_thr,
                         hipStream_t s);
+
+// the IoU maps the score kind needs: every level's iou pointer set (IoU-aware kinds) or every one
+// NULL (IA_CLS_*_NOIOU)
+inline int check_iou_ptrs(const LevelTable &t, const ia_level_ptrs &p)
+{
+    for (int l = 0; l < t.num_levels; ++l)
+        if ((p.iou[l] != nullptr) != t.iou()) return IA_E_ARG;
+    return 0;
+}
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 

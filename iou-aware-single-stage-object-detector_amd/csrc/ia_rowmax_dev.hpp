@@ -93,7 +93,9 @@ __device__ __forceinline__ void store_wt_b32(float *p, float v)
 //                    counter, and only then stores the group maxima of its rows -- non-zero words
 //                    (ordered keys) that are the "these 64 rows are in memory" flags the filter
 //                    workgroups of the same launch wait for (Guideline 16 R1: payload, drain, flag).
-template <typename T, int VPR_T, bool PUBLISH, typename AT = RowmaxNhwcArgs>   // VPR_T = 0: run-time vectors per row
+//   IOU = true : score sqrt(sigmoid(max logit)) * sqrt(sigmoid(iou)) (IA_CLS_SIGMOID);
+//   IOU = false: score sigmoid(max logit), no IoU map (IA_CLS_SIGMOID_NOIOU).
+template <typename T, int VPR_T, bool PUBLISH, bool IOU = true, typename AT = RowmaxNhwcArgs>   // VPR_T = 0: run-time vectors per row
 __device__ __forceinline__ void rowmax_nhwc_wave(const AT &a, int l, int rem, float *s_m, int lane)
 {
     constexpr int PPL = Lane<T>::PPL;
@@ -108,7 +110,7 @@ __device__ __forceinline__ void rowmax_nhwc_wave(const AT &a, int l, int rem, fl
     // this lane's row: its IoU logit is requested first so that its latency hides behind the
     // class loads instead of following the barrier
     const int64_t g = r0 + ((lane < nrow) ? lane : (nrow - 1));
-    const float il = load_f32<T>(static_cast<const T *>(a.p.iou[l]) + g);
+    const float il = IOU ? load_f32<T>(static_cast<const T *>(a.p.iou[l]) + g) : 0.0f;
     // All loads of a batch are issued before the first one is consumed: written as one loop
     // (load, reduce, LDS store per vector) the compiler waits for each load before issuing the
     // next -- ONE kilobyte in flight per wavefront, a latency-bound kernel that only its 29
@@ -154,7 +156,7 @@ __device__ __forceinline__ void rowmax_nhwc_wave(const AT &a, int l, int rem, fl
 #ifdef IA_ROWMAX_NOMATH                                      /* tools/ubench/rowmax_bench.hip only */
         score = m * il;
 #else
-        score = sqrt_sigmoidf_(m) * sqrt_sigmoidf_(il);
+        score = IOU ? sqrt_sigmoidf_(m) * sqrt_sigmoidf_(il) : sigmoidf_(m);
 #endif
     }
     const int grp = a.plan.grp[l];

@@ -490,7 +490,7 @@ struct FusedOrder {
     int32_t n_items;
 };
 
-template <typename T, int VPR_T>
+template <typename T, int VPR_T, bool IOU>        // IOU: score kind (ia_rowmax_dev.hpp, rowmax_nhwc_wave)
 __global__ void __launch_bounds__(kFilterThreads, 4) k_rowmax_filter_nhwc(RowmaxNhwcArgs ra, SelArgs sa,
                                                                        FusedOrder fo)
 {
@@ -508,7 +508,7 @@ __global__ void __launch_bounds__(kFilterThreads, 4) k_rowmax_filter_nhwc(Rowmax
         if (threadIdx.x == 0 && blockIdx.x < 8192) g_blk_t[blockIdx.x][0] = wall_clock64();
 #endif
         if (unit < fo.units[l])
-            rowmax_nhwc_wave<T, VPR_T, true>(ra, l, unit, reinterpret_cast<float *>(s_raw) + wv * kTile,
+            rowmax_nhwc_wave<T, VPR_T, true, IOU>(ra, l, unit, reinterpret_cast<float *>(s_raw) + wv * kTile,
                                              (int)(threadIdx.x & 63));
 #ifdef IA_SEL_PROFILE
         if (threadIdx.x == 0 && blockIdx.x < 8192) g_blk_t[blockIdx.x][1] = wall_clock64();
@@ -940,7 +940,8 @@ int launch_rowmax_select(const LevelTable &t, const ia_level_ptrs &p, int batch,
         const char *e = getenv("IA_FUSED_ROWMAX_FILTER");
         return !(e && e[0] == '0');
     }();
-    if (t.softmax) {            // softmax row scores (decode.hip), then the separate selection kernels
+    if ((rc = check_iou_ptrs(t, p))) return rc;
+    if (t.softmax()) {          // softmax row scores (decode.hip), then the separate selection kernels
         rc = launch_rowmax(t, p, batch, dtype, rowmax, s);
         if (rc) return rc;
         return launch_select(t, rowmax, batch, cand_idx, workspace, s, false);
@@ -1002,13 +1003,19 @@ int launch_rowmax_select(const LevelTable &t, const ia_level_ptrs &p, int batch,
     uint32_t id = ++g_fused_calls;
     if (id == 0u) id = ++g_fused_calls;                    // 0 = "not a fused launch"
     a.call_id = id;
-    if (dtype == IA_F32) {
-        if (vpr == 20) hipLaunchKernelGGL((k_rowmax_filter_nhwc<float, 20>), grid, block, 0, s, ra, a, fo);
-        else hipLaunchKernelGGL((k_rowmax_filter_nhwc<float, 0>), grid, block, 0, s, ra, a, fo);
-    } else {
-        if (vpr == 10) hipLaunchKernelGGL((k_rowmax_filter_nhwc<uint16_t, 10>), grid, block, 0, s, ra, a, fo);
-        else hipLaunchKernelGGL((k_rowmax_filter_nhwc<uint16_t, 0>), grid, block, 0, s, ra, a, fo);
-    }
+#define IA_FUSED_LAUNCH(IOU)                                                                          \
+    do {                                                                                              \
+        if (dtype == IA_F32) {                                                                        \
+            if (vpr == 20) hipLaunchKernelGGL((k_rowmax_filter_nhwc<float, 20, IOU>), grid, block, 0, s, ra, a, fo); \
+            else hipLaunchKernelGGL((k_rowmax_filter_nhwc<float, 0, IOU>), grid, block, 0, s, ra, a, fo); \
+        } else {                                                                                      \
+            if (vpr == 10) hipLaunchKernelGGL((k_rowmax_filter_nhwc<uint16_t, 10, IOU>), grid, block, 0, s, ra, a, fo); \
+            else hipLaunchKernelGGL((k_rowmax_filter_nhwc<uint16_t, 0, IOU>), grid, block, 0, s, ra, a, fo); \
+        }                                                                                             \
+    } while (0)
+    if (t.iou()) IA_FUSED_LAUNCH(true);
+    else IA_FUSED_LAUNCH(false);
+#undef IA_FUSED_LAUNCH
     rc = hip_status(hipGetLastError());
     if (!rc) {
         hipLaunchKernelGGL(k_sel_final, dim3((unsigned)t.num_levels, (unsigned)batch),

@@ -15,6 +15,7 @@ IA_MAX_PER_IMG = 1024
 IA_F32, IA_BF16, IA_F16, IA_F64 = 0, 1, 2, 3
 IA_LAYOUT_NCHW, IA_LAYOUT_NHWC = 0, 1
 IA_CLS_SIGMOID, IA_CLS_SOFTMAX = 0, 1
+IA_CLS_SIGMOID_NOIOU, IA_CLS_SOFTMAX_NOIOU = 2, 3     # plain RetinaHead: no IoU map (NULL pointers)
 IA_LOSS_SLOTS = 64
 IA_MAX_TARGET_BATCH = 16
 IA_GN_CHUNK = 256

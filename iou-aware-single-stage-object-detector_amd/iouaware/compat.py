@@ -46,6 +46,7 @@ def install(force=False):
     models.necks = _mod('mmdet.models.necks', FPN=fpn.FPN)
     models.anchor_heads = _mod('mmdet.models.anchor_heads', AnchorHead=head.AnchorHead,
                                IoUawareRetinaHead=head.IoUawareRetinaHead,
+                               RetinaHead=head.RetinaHead,
                                IoUawareFCOSHead=fcos_head.IoUawareFCOSHead,
                                FCOSHead=fcos_head.FCOSHead)
     models.detectors = _mod('mmdet.models.detectors', BaseDetector=detectors.BaseDetector,
@@ -65,6 +66,7 @@ def install(force=False):
     models.SingleStageDetector = detectors.SingleStageDetector
     models.FCOS, models.IoUawareFCOSHead = detectors.FCOS, fcos_head.IoUawareFCOSHead
     models.FCOSHead = fcos_head.FCOSHead
+    models.RetinaHead = head.RetinaHead
 
     ops_nms = _mod('mmdet.ops.nms', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
     ops_nms.nms_wrapper = _mod('mmdet.ops.nms.nms_wrapper', nms=nms_op.nms, soft_nms=nms_op.soft_nms)

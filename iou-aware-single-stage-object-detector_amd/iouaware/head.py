@@ -1,7 +1,8 @@
 """IoU-aware RetinaNet head (reference
 mmdet/models/anchor_heads/iou_aware_retina_head.py:64-564 on top of
 anchor_head.py:21-148), with the reference's registry name, constructor
-kwargs, parameter names and method signatures.
+kwargs, parameter names and method signatures; and the plain RetinaHead it is
+measured against (retina_head.py:9-90, anchor_head.py:150-450).
 
 What is different from the reference is WHERE the work after the last
 convolution happens:
@@ -96,6 +97,8 @@ class AnchorHead(nn.Module):
             valid_flag_list.append(flags)
         return anchor_list, valid_flag_list
 
+    iou_branch = True                     # the decode fuses sigmoid(iou) into the score
+
     def geometry(self, featmap_sizes, nms_pre=-1):
         """ia_head_geom for these feature-map sizes (cached)."""
         key = (tuple(tuple(int(v) for v in s) for s in featmap_sizes), int(nms_pre))
@@ -106,31 +109,24 @@ class AnchorHead(nn.Module):
             # num_classes channels per anchor with the background in channel 0 (:506-507,540-541)
             g = ops.HeadGeometry(key[0], self.anchor_strides, base, self.num_classes - 1,
                                  nms_pre=nms_pre, means=self.target_means, stds=self.target_stds,
-                                 softmax=not self.use_sigmoid_cls)
+                                 softmax=not self.use_sigmoid_cls, iou_branch=self.iou_branch)
             self._geom_cache[key] = g
         return g
 
 
-@HEADS.register_module
-class IoUawareRetinaHead(AnchorHead):
-    """RetinaNet head with a class-agnostic IoU branch: `retina_iou` (A channels) reads
-    the regression tower's last feature; detection confidence is
-    sigmoid(cls)^0.5 * sigmoid(iou)^0.5 (alpha = 0.5 hard-coded in the reference, :510)."""
-
-    score_alpha = 0.5
+class _RetinaHeadBase(AnchorHead):
+    """What the plain and the IoU-aware RetinaNet heads share: the constructor arguments and
+    anchors (retina_head.py:11-31), the two conv towers with retina_cls / retina_reg and their
+    initialisation, the batched decode of get_bboxes, and the target dispatch of loss() (HIP
+    assigner where it applies, targets.py otherwise)."""
 
     def __init__(self, num_classes, in_channels, stacked_convs=4, octave_base_scale=4,
-                 scales_per_octave=3, conv_cfg=None, norm_cfg=None,
-                 loss_iou=dict(type='GHMIoU', bins=30, momentum=0.75, use_sigmoid=True,
-                               loss_weight=1.0),
-                 attach_iou_target=True, **kwargs):
+                 scales_per_octave=3, conv_cfg=None, norm_cfg=None, **kwargs):
         self.stacked_convs = stacked_convs
         self.octave_base_scale, self.scales_per_octave = octave_base_scale, scales_per_octave
         self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
-        # `loss_iou` is accepted and ignored, exactly like the reference (:74, never used).
-        self.attach_iou_target = attach_iou_target
         octave_scales = np.array([2 ** (i / scales_per_octave) for i in range(scales_per_octave)])
-        super(IoUawareRetinaHead, self).__init__(
+        super(_RetinaHeadBase, self).__init__(
             num_classes, in_channels, anchor_scales=octave_scales * octave_base_scale, **kwargs)
 
     def _init_layers(self):
@@ -145,15 +141,123 @@ class IoUawareRetinaHead(AnchorHead):
         self.retina_cls = nn.Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3,
                                     padding=1)
         self.retina_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
-        self.shared_conv = 4              # IoU branch shares all four regression convs
-        self.use_feature_alignment = False
-        self.retina_iou = nn.Conv2d(self.feat_channels, self.num_anchors, 3, padding=1)
 
     def init_weights(self):
         for m in list(self.cls_convs) + list(self.reg_convs):
             normal_init(m.conv, std=0.01)
         normal_init(self.retina_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.retina_reg, std=0.01)
+
+    def _towers(self, x):
+        cls_feat = reg_feat = x
+        for conv in self.cls_convs:
+            cls_feat = conv(cls_feat)
+        for conv in self.reg_convs:
+            reg_feat = conv(reg_feat)
+        return cls_feat, reg_feat
+
+    # ------------------------------------------------------------------ inference
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, iou_preds, img_metas, cfg, rescale):
+        """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
+        rows (B,max) int32, num (B) int32 -- no host synchronisation.  iou_preds None: the plain
+        score kind (the geometry of a head without the IoU branch)."""
+        if not (len(cls_scores) == len(bbox_preds) == len(self.anchor_generators)
+                and (iou_preds is None or len(iou_preds) == len(cls_scores))):
+            raise AssertionError('level count mismatch')
+        nms_cfg = dict(cfg.nms)
+        nms_type = nms_cfg.pop('type', 'nms')
+        if nms_type not in ('nms', 'soft_nms'):
+            raise AttributeError("module 'nms_wrapper' has no attribute '%s'" % nms_type)
+        iou_thr = nms_cfg.pop('iou_thr')
+        soft = nms_cfg if nms_type == 'soft_nms' else None      # method / sigma / min_score
+        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
+        shapes = [m['img_shape'] for m in img_metas]
+        factors = [m['scale_factor'] for m in img_metas]
+        cls_scores = [c.detach() for c in cls_scores]
+        bbox_preds = [b.detach() for b in bbox_preds]
+        if iou_preds is not None:
+            iou_preds = [i.detach() for i in iou_preds]
+        return ops.get_bboxes(geom, cls_scores, bbox_preds, iou_preds, shapes, factors, rescale,
+                              cfg.score_thr, iou_thr, cfg.max_per_img, soft=soft)
+
+    @staticmethod
+    def _per_image(dets, labels, rows, num):
+        """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64), k <= max_per_img"""
+        counts = num.tolist()                                   # the one host sync per batch
+        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
+
+    # ------------------------------------------------------------------ training
+    def _device_targets_ok(self, cfg, gt_bboxes, gt_bboxes_ignore, device):
+        """the HIP assigner covers the IoU-aware configs' train_cfg (MaxIoUAssigner,
+        gt_max_assign_all, allowed_border=-1, no ignore regions, no sampling); anything else
+        takes the torch path in targets.py"""
+        a = cfg.assigner
+        return (device.type == 'cuda' and not self.sampling and isinstance(a, dict)
+                and a.get('type') == 'MaxIoUAssigner' and a.get('gt_max_assign_all', True)
+                and isinstance(a.get('neg_iou_thr'), float) and cfg.allowed_border < 0
+                and not (a.get('ignore_iof_thr', -1) > 0 and gt_bboxes_ignore is not None)
+                and all(g.shape[0] >= 1 for g in gt_bboxes)
+                and max(g.shape[0] for g in gt_bboxes) <= 512)
+
+    def _targets(self, featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
+                 gt_bboxes_ignore, device, counts_as_normaliser=False):
+        """-> (labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts), or None
+        when an image has no valid anchor (targets.py).  From the HIP assigner (whole batch in two
+        launches, nothing returns to the host): level_anchors are None, counts the per-image
+        device counts, and the normaliser num_total_pos = sum_i max(n_pos_i, 1)
+        (anchor_target.py:94) a device scalar -- or `counts` itself with counts_as_normaliser
+        (reduced inside the fused head-loss kernel)."""
+        if self._device_targets_ok(cfg, gt_bboxes, gt_bboxes_ignore, device):
+            acfg = cfg.assigner
+            labels, label_w, bbox_t, bbox_w, counts = ops.anchor_targets(
+                geom, gt_bboxes, gt_labels, [m['pad_shape'] for m in img_metas],
+                acfg['pos_iou_thr'], acfg['neg_iou_thr'], acfg.get('min_pos_iou', .0),
+                cfg.pos_weight)
+            norm = counts if counts_as_normaliser else counts[:, 0].clamp(min=1).sum().to(torch.float32)
+            return labels, label_w, bbox_t, bbox_w, [None] * len(featmap_sizes), norm, counts
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        targets = anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas,
+                                self.target_means, self.target_stds, cfg,
+                                gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                gt_labels_list=gt_labels, label_channels=label_channels,
+                                sampling=self.sampling)
+        if targets is None:
+            return None
+        labels, label_w, bbox_t, bbox_w, n_pos, n_neg, level_anchors = targets
+        num_total_samples = n_pos + n_neg if self.sampling else n_pos
+        return labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, None
+
+
+@HEADS.register_module
+class IoUawareRetinaHead(_RetinaHeadBase):
+    """RetinaNet head with a class-agnostic IoU branch: `retina_iou` (A channels) reads
+    the regression tower's last feature; detection confidence is
+    sigmoid(cls)^0.5 * sigmoid(iou)^0.5 (alpha = 0.5 hard-coded in the reference, :510)."""
+
+    score_alpha = 0.5
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, octave_base_scale=4,
+                 scales_per_octave=3, conv_cfg=None, norm_cfg=None,
+                 loss_iou=dict(type='GHMIoU', bins=30, momentum=0.75, use_sigmoid=True,
+                               loss_weight=1.0),
+                 attach_iou_target=True, **kwargs):
+        # `loss_iou` is accepted and ignored, exactly like the reference (:74, never used).
+        self.attach_iou_target = attach_iou_target
+        super(IoUawareRetinaHead, self).__init__(
+            num_classes, in_channels, stacked_convs=stacked_convs,
+            octave_base_scale=octave_base_scale, scales_per_octave=scales_per_octave,
+            conv_cfg=conv_cfg, norm_cfg=norm_cfg, **kwargs)
+
+    def _init_layers(self):
+        super(IoUawareRetinaHead, self)._init_layers()
+        self.shared_conv = 4              # IoU branch shares all four regression convs
+        self.use_feature_alignment = False
+        self.retina_iou = nn.Conv2d(self.feat_channels, self.num_anchors, 3, padding=1)
+
+    def init_weights(self):
+        super(IoUawareRetinaHead, self).init_weights()
         normal_init(self.retina_iou, std=0.01)
 
     train_winograd = True                 # training: all-levels Winograd convolutions when usable
@@ -169,44 +273,22 @@ class IoUawareRetinaHead(AnchorHead):
         return super(IoUawareRetinaHead, self).forward(feats)
 
     def forward_single(self, x):
-        cls_feat = reg_feat = x
-        for conv in self.cls_convs:
-            cls_feat = conv(cls_feat)
-        for conv in self.reg_convs:
-            reg_feat = conv(reg_feat)
+        cls_feat, reg_feat = self._towers(x)
         return self.retina_cls(cls_feat), self.retina_reg(reg_feat), self.retina_iou(reg_feat)
 
     # ------------------------------------------------------------------ inference
     def get_bboxes_batched(self, cls_scores, bbox_preds, iou_preds, img_metas, cfg, rescale=False):
         """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
         rows (B,max) int32, num (B) int32 -- no host synchronisation."""
-        if not len(cls_scores) == len(bbox_preds) == len(iou_preds) == len(self.anchor_generators):
-            raise AssertionError('level count mismatch')
-        nms_cfg = dict(cfg.nms)
-        nms_type = nms_cfg.pop('type', 'nms')
-        if nms_type not in ('nms', 'soft_nms'):
-            raise AttributeError("module 'nms_wrapper' has no attribute '%s'" % nms_type)
-        iou_thr = nms_cfg.pop('iou_thr')
-        soft = nms_cfg if nms_type == 'soft_nms' else None      # method / sigma / min_score
-        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
-        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
-        shapes = [m['img_shape'] for m in img_metas]
-        factors = [m['scale_factor'] for m in img_metas]
-        cls_scores = [c.detach() for c in cls_scores]
-        bbox_preds = [b.detach() for b in bbox_preds]
-        iou_preds = [i.detach() for i in iou_preds]
-        return ops.get_bboxes(geom, cls_scores, bbox_preds, iou_preds, shapes, factors, rescale,
-                              cfg.score_thr, iou_thr, cfg.max_per_img, soft=soft)
+        return self._get_bboxes_batched(cls_scores, bbox_preds, iou_preds, img_metas, cfg, rescale)
 
     def get_bboxes(self, cls_scores, bbox_preds, iou_preds, gt_bboxes, gt_labels, img_metas, cfg,
                    rescale=False):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64), k <= max_per_img.
         gt_bboxes / gt_labels are accepted positionally like the fork's signature (:390-398);
         they only feed dead code there (:517-524) and are unused."""
-        dets, labels, _, num = self.get_bboxes_batched(cls_scores, bbox_preds, iou_preds, img_metas,
-                                                       cfg, rescale)
-        counts = num.tolist()                                   # the one host sync per batch
-        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
+        return self._per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, iou_preds,
+                                                        img_metas, cfg, rescale))
 
     # ------------------------------------------------------------------ training
     def loss_single(self, cls_score, bbox_pred, iou_pred, labels, label_weights, bbox_targets,
@@ -241,17 +323,6 @@ class IoUawareRetinaHead(AnchorHead):
                                                    self.num_anchors, num_total_samples)
         return loss_cls, loss_bbox, loss_iou
 
-    def _device_targets_ok(self, cfg, gt_bboxes, gt_bboxes_ignore, device):
-        """the HIP assigner covers the IoU-aware configs' train_cfg (MaxIoUAssigner,
-        gt_max_assign_all, allowed_border=-1, no ignore regions, no sampling); anything else
-        takes the torch path in targets.py"""
-        a = cfg.assigner
-        return (device.type == 'cuda' and not self.sampling and isinstance(a, dict)
-                and a.get('type') == 'MaxIoUAssigner' and a.get('gt_max_assign_all', True)
-                and isinstance(a.get('neg_iou_thr'), float) and cfg.allowed_border < 0
-                and not (a.get('ignore_iof_thr', -1) > 0 and gt_bboxes_ignore is not None)
-                and all(g.shape[0] >= 1 for g in gt_bboxes)
-                and max(g.shape[0] for g in gt_bboxes) <= 512)
 
     fuse_levels = True                    # all-levels loss kernels when the configuration allows
 
@@ -270,35 +341,14 @@ class IoUawareRetinaHead(AnchorHead):
         featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
         if len(featmap_sizes) != len(self.anchor_generators):
             raise AssertionError('level count mismatch')
-        device = cls_scores[0].device
         geom = self.geometry(featmap_sizes, -1)
-        if self._device_targets_ok(cfg, gt_bboxes, gt_bboxes_ignore, device):
-            # whole batch in two HIP launches, nothing returns to the host: the normaliser
-            # num_total_pos = sum_i max(n_pos_i, 1) (anchor_target.py:94) stays a device scalar
-            acfg = cfg.assigner
-            labels, label_w, bbox_t, bbox_w, counts = ops.anchor_targets(
-                geom, gt_bboxes, gt_labels, [m['pad_shape'] for m in img_metas],
-                acfg['pos_iou_thr'], acfg['neg_iou_thr'], acfg.get('min_pos_iou', .0),
-                cfg.pos_weight)
-            level_anchors = [None] * len(featmap_sizes)
-            if self._fused_loss_ok(cls_scores):
-                num_total_samples = counts             # reduced inside the finalize kernel
-            else:
-                num_total_samples = counts[:, 0].clamp(min=1).sum().to(torch.float32)
-        else:
-            anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
-            label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-            targets = anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas,
-                                    self.target_means, self.target_stds, cfg,
-                                    gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                    gt_labels_list=gt_labels, label_channels=label_channels,
-                                    sampling=self.sampling)
-            if targets is None:
-                return None
-            labels, label_w, bbox_t, bbox_w, n_pos, n_neg, level_anchors = targets
-            num_total_samples = n_pos + n_neg if self.sampling else n_pos
-            counts = None
-        if self._fused_loss_ok(cls_scores):
+        fused = self._fused_loss_ok(cls_scores)
+        targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
+                                gt_bboxes_ignore, cls_scores[0].device, counts_as_normaliser=fused)
+        if targets is None:
+            return None
+        labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts = targets
+        if fused:
             # all levels, all three losses: one autograd node, 3 + 2 kernel launches
             # (csrc/headloss.hip); the per-level path below stays for the other loss types
             on_dev = level_anchors[0] is None          # targets came from the HIP assigner
@@ -316,3 +366,72 @@ class IoUawareRetinaHead(AnchorHead):
                for l in range(len(featmap_sizes))]
         losses_cls, losses_bbox, losses_iou = map(list, zip(*out))
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, losses_iou=losses_iou)
+
+
+@HEADS.register_module
+class RetinaHead(_RetinaHeadBase):
+    """Plain RetinaNet head (reference retina_head.py:9-90): the towers with retina_cls /
+    retina_reg and no `retina_iou`.  forward -> (cls_scores, bbox_preds); detection score =
+    sigmoid(cls) (softmax with use_sigmoid_cls=False), decoded by the same HIP path as the
+    IoU-aware head with the IA_CLS_*_NOIOU score kind (anchor_head.py:364-450)."""
+
+    iou_branch = False
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, octave_base_scale=4,
+                 scales_per_octave=3, conv_cfg=None, norm_cfg=None, **kwargs):
+        for k in ('loss_iou', 'attach_iou_target'):
+            if k in kwargs:          # AnchorHead.__init__ of the reference takes neither
+                raise TypeError("__init__() got an unexpected keyword argument '%s'" % k)
+        super(RetinaHead, self).__init__(
+            num_classes, in_channels, stacked_convs=stacked_convs,
+            octave_base_scale=octave_base_scale, scales_per_octave=scales_per_octave,
+            conv_cfg=conv_cfg, norm_cfg=norm_cfg, **kwargs)
+
+    def forward_single(self, x):
+        cls_feat, reg_feat = self._towers(x)
+        return self.retina_cls(cls_feat), self.retina_reg(reg_feat)
+
+    # ------------------------------------------------------------------ inference
+    def get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale=False):
+        """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
+        rows (B,max) int32, num (B) int32 -- no host synchronisation."""
+        return self._get_bboxes_batched(cls_scores, bbox_preds, None, img_metas, cfg, rescale)
+
+    def get_bboxes(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, cfg,
+                   rescale=False):
+        """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64).  The fork's
+        signature (anchor_head.py:301-308): gt_bboxes / gt_labels are positional and unused."""
+        return self._per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg,
+                                                        rescale))
+
+    # ------------------------------------------------------------------ training
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, cfg,
+             gt_bboxes_ignore=None):
+        """-> dict(loss_cls, loss_bbox), each a list of per-level (1,) tensors, or None when an
+        image has no valid anchor (anchor_head.py:234-299): focal / cross-entropy and smooth-L1
+        per level on the HIP loss kernels."""
+        for lo in (self.loss_cls, self.loss_bbox):
+            if type(lo).__name__ in ('IOUbalancedSigmoidFocalLoss', 'IoUbalancedSmoothL1Loss'):
+                raise NotImplementedError('%s on RetinaHead needs an IoU target without an IoU '
+                                          'map; not supported' % type(lo).__name__)
+        featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
+        if len(featmap_sizes) != len(self.anchor_generators):
+            raise AssertionError('level count mismatch')
+        for t in list(cls_scores) + list(bbox_preds):
+            ops._require_gpu(t, 'head output')
+        geom = self.geometry(featmap_sizes, -1)
+        targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
+                                gt_bboxes_ignore, cls_scores[0].device)
+        if targets is None:
+            return None
+        labels, label_w, bbox_t, bbox_w, _, num_total_samples, _ = targets
+        losses_cls, losses_bbox = [], []
+        for l in range(len(featmap_sizes)):
+            B, n_l = cls_scores[l].shape[0], geom.level_anchors[l]
+            losses_cls.append(self.loss_cls.forward_level(
+                cls_scores[l], labels[l].reshape(B, n_l), label_w[l].reshape(B, n_l),
+                self.num_anchors, num_total_samples))
+            losses_bbox.append(self.loss_bbox.forward_level(
+                bbox_preds[l], bbox_t[l].reshape(B, n_l, 4), bbox_w[l].reshape(B, n_l, 4),
+                self.num_anchors, num_total_samples))
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)

@@ -57,10 +57,12 @@ class HeadGeometry(object):
     (fills the C struct ia_head_geom)."""
 
     def __init__(self, featmap_sizes, strides, base_anchors, num_classes, nms_pre=-1,
-                 means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), softmax=False):
+                 means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), softmax=False, iou_branch=True):
         """num_classes: foreground classes C (the score columns).  softmax=True: the head's
         use_sigmoid_cls=False branch (iou_aware_retina_head.py:506-507,540-541): the class tensors
-        carry A * (C + 1) channels, channel 0 of an anchor = background."""
+        carry A * (C + 1) channels, channel 0 of an anchor = background.  iou_branch=False: the
+        plain RetinaHead (IA_CLS_*_NOIOU): score = sigmoid(cls) / softmax(cls) alone, and every
+        entry below takes iou=None."""
         base = np.asarray(base_anchors, dtype=np.float32)
         L, A = base.shape[0], base.shape[1]
         if L != len(featmap_sizes) or L != len(strides):
@@ -76,10 +78,14 @@ class HeadGeometry(object):
                     g.base_anchors[l][a][k] = float(base[l, a, k])
         for k in range(4):
             g.means[k], g.stds[k] = float(means[k]), float(stds[k])
-        g.cls_activation = _lib.IA_CLS_SOFTMAX if softmax else _lib.IA_CLS_SIGMOID
+        if iou_branch:
+            g.cls_activation = _lib.IA_CLS_SOFTMAX if softmax else _lib.IA_CLS_SIGMOID
+        else:
+            g.cls_activation = _lib.IA_CLS_SOFTMAX_NOIOU if softmax else _lib.IA_CLS_SIGMOID_NOIOU
         self.struct = g
         self.L, self.A, self.C = L, A, int(num_classes)
         self.softmax = bool(softmax)
+        self.iou_branch = bool(iou_branch)
         self.Cin = self.C + 1 if softmax else self.C          # class channels per anchor
         self.featmap_sizes = [tuple(int(v) for v in s) for s in featmap_sizes]
         self.strides = [int(s) for s in strides]
@@ -92,7 +98,8 @@ class HeadGeometry(object):
         self.layout = _lib.IA_LAYOUT_NCHW
         self._twin = None
         # what the workspace carve-up depends on (besides batch, layout and dtype)
-        self.key = (tuple(self.featmap_sizes), A, int(num_classes), int(nms_pre), bool(softmax))
+        self.key = (tuple(self.featmap_sizes), A, int(num_classes), int(nms_pre), bool(softmax),
+                    bool(iou_branch))
 
     def ref(self):
         return C.byref(self.struct)
@@ -138,20 +145,33 @@ def _nhwc_ok(geom, tensors):
                for t in tensors)
 
 
+def _as_list(x):
+    return None if x is None else list(x)
+
+
 def level_ptrs(geom, cls, reg, iou):
-    """Validate the per-level head outputs and pack their device pointers.
+    """Validate the per-level head outputs and pack their device pointers.  iou: the IoU maps, or
+    None for a geometry without the IoU branch (their pointers stay NULL).
     -> (ptrs, batch, dtype code, geometry for the memory order the tensors are in)"""
+    if (iou is None) == geom.iou_branch:
+        raise ValueError('iou maps %s for a head %s the IoU branch'
+                         % (('missing', 'with') if iou is None else ('given', 'without')))
+    if iou is None:
+        iou = [None] * geom.L
     if not (len(cls) == len(reg) == len(iou) == geom.L):
         raise AssertionError('expected %d levels' % geom.L)
     p = LevelPtrs()
     B = cls[0].shape[0]
     dt = _dtype_code(cls[0])
-    nhwc = _nhwc_ok(geom, list(cls) + list(reg) + list(iou))
+    maps = list(cls) + list(reg) + [t for t in iou if t is not None]
+    nhwc = _nhwc_ok(geom, maps)
     geom = geom.with_layout(_lib.IA_LAYOUT_NHWC if nhwc else _lib.IA_LAYOUT_NCHW)
     for l in range(geom.L):
         h, w = geom.featmap_sizes[l]
         for name, t, ch in (('cls_score', cls[l], geom.A * geom.Cin), ('bbox_pred', reg[l], geom.A * 4),
                             ('iou_pred', iou[l], geom.A)):
+            if t is None:
+                continue
             _require_gpu(t, name)
             if tuple(t.shape) != (B, ch, h, w):
                 raise AssertionError('%s level %d has shape %s, expected %s'
@@ -161,8 +181,10 @@ def level_ptrs(geom, cls, reg, iou):
         if not nhwc:
             cls[l] = to_nchw(cls[l])
             reg[l] = to_nchw(reg[l])
-            iou[l] = to_nchw(iou[l])
-        p.cls[l], p.reg[l], p.iou[l] = cls[l].data_ptr(), reg[l].data_ptr(), iou[l].data_ptr()
+            if iou[l] is not None:
+                iou[l] = to_nchw(iou[l])
+        p.cls[l], p.reg[l] = cls[l].data_ptr(), reg[l].data_ptr()
+        p.iou[l] = iou[l].data_ptr() if iou[l] is not None else None
     return p, B, dt, geom
 
 
@@ -237,7 +259,7 @@ def stage_events(begin=None, end=None):
 
 def state_workspace_for(geom, cls, reg, iou):
     """the persistent workspace `get_bboxes` uses for these head outputs (tests / telemetry)"""
-    p, B, dt, g = level_ptrs(geom, list(cls), list(reg), list(iou))
+    p, B, dt, g = level_ptrs(geom, list(cls), list(reg), _as_list(iou))
     nbytes = _lib.lib().ia_get_bboxes_workspace_bytes(g.ref(), B)
     return g, B, _state_workspace(cls[0].device, nbytes, (g.key, g.layout, B, dt))
 
@@ -281,7 +303,7 @@ def get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_th
     also returns the workspace views (rowmax, cand_idx, boxes, scores_t,
     keep_count, keep_rows) for stage-level parity tests.
     """
-    cls, reg, iou = list(cls), list(reg), list(iou)
+    cls, reg, iou = list(cls), list(reg), _as_list(iou)
     if soft is not None:
         geom = geometry_for(geom, cls, reg, iou)
         if geom.R > _lib.IA_MAX_CANDIDATES or max_per_img > _lib.IA_MAX_PER_IMG:
@@ -401,7 +423,7 @@ class DecodeStage(object):
     current stream; `views()` are the stage's outputs inside the workspace."""
 
     def __init__(self, geom, cls, reg, iou, img_shapes, scale_factors, rescale):
-        cls, reg, iou = list(cls), list(reg), list(iou)
+        cls, reg, iou = list(cls), list(reg), _as_list(iou)
         self.p, self.B, self.dt, self.geom = level_ptrs(geom, cls, reg, iou)
         self.keep = (cls, reg, iou)
         dev = cls[0].device
@@ -439,13 +461,13 @@ def geometry_for(geom, cls, reg, iou):
     """the geometry object matching the memory order (NCHW / channels-last) of these head
     outputs: pass it to the stage wrappers so that select_topk reads the row maxima in the
     order decode_fuse_rowmax wrote them"""
-    return level_ptrs(geom, list(cls), list(reg), list(iou))[3]
+    return level_ptrs(geom, list(cls), list(reg), _as_list(iou))[3]
 
 
 def decode_fuse_rowmax(geom, cls, reg, iou, select_ws=None):
     """select_ws: a top-k workspace (select_workspace): the kernel then also leaves the group
     maxima / cleared counters select_topk(..., select_ws) starts from (ia_get_bboxes' chaining)"""
-    cls, reg, iou = list(cls), list(reg), list(iou)
+    cls, reg, iou = list(cls), list(reg), _as_list(iou)
     p, B, dt, geom = level_ptrs(geom, cls, reg, iou)
     out = torch.empty((B, geom.N), dtype=torch.float32, device=cls[0].device)
     if select_ws is None:
@@ -481,7 +503,7 @@ def select_topk(geom, rowmax, select_ws=None):
 
 
 def gather_decode(geom, cls, reg, iou, cand_idx, img_shapes, scale_factors, rescale):
-    cls, reg, iou = list(cls), list(reg), list(iou)
+    cls, reg, iou = list(cls), list(reg), _as_list(iou)
     p, B, dt, geom = level_ptrs(geom, cls, reg, iou)
     dev = cls[0].device
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
