@@ -83,8 +83,16 @@ typedef struct ia_head_geom {
      * anchor_head.py:364-450): no IoU branch, score_c = sigmoid(x_c), resp. softmax(x)_{c+1} with the
      * row maximum over the foreground columns; the ranking is by these values (equal scores from
      * different logits tie, lower index first).  Every p->iou[l] must be NULL with these kinds and
-     * non-NULL with the IoU-aware ones (IA_E_ARG otherwise).  Inference entries only: the fused
-     * head-loss entries (ia_head_loss_*) take IA_CLS_SIGMOID alone.                               */
+     * non-NULL with the IoU-aware ones (IA_E_ARG otherwise).
+     * The fused head-loss entries (ia_head_loss_*: a sigmoid focal loss) take IA_CLS_SIGMOID and
+     * IA_CLS_SIGMOID_NOIOU; both softmax kinds are IA_E_ARG there (workspace size 0).  With
+     * IA_CLS_SIGMOID_NOIOU the node is FocalLoss + SmoothL1Loss alone (anchor_head.py:234-299):
+     * p->iou[l] and grads->iou[l] must be NULL for every level (a non-NULL one is IA_E_ARG),
+     * strides->iou / grad_strides->iou and cfg->attach_iou_target are ignored, no IoU map is read and
+     * no IoU gradient written.  The result keeps its 3L + 4 layout: the losses_iou[L] entries and
+     * their total are written as 0.0f.  cfg->grad_rows_start_at_reg then describes a gradient row
+     * [reg 4A | padding]: the backward writes the zero gradient of the stride - 4A (<= 64) channels
+     * behind the reg slice.                                                                       */
     int32_t cls_activation;
 } ia_head_geom;
 
@@ -547,7 +555,9 @@ int ia_anchor_targets_ptrs(const ia_head_geom *g, const float *const *gt_boxes,
  * (iou_aware_retina_head.py:221-313 x L, :315-387): FocalLoss(gamma = 2) on the class logits,
  * SmoothL1Loss on the deltas, IoU target + BCE on the IoU logits; 4 + 2 kernel launches.
  * Head outputs NCHW (g->layout == IA_LAYOUT_NCHW), per-level targets as ia_anchor_targets
- * writes them.                                                                       */
+ * writes them.  With g->cls_activation == IA_CLS_SIGMOID_NOIOU (the plain RetinaHead,
+ * anchor_head.py:234-299) the same entries compute FocalLoss + SmoothL1Loss alone: NULL IoU
+ * pointers, losses_iou written as 0 (see ia_head_geom.cls_activation).                */
 typedef struct ia_head_targets {
     const int64_t *labels[IA_MAX_LEVELS];        /* (B, N_l) int64 in 0..C                 */
     const float *label_weights[IA_MAX_LEVELS];   /* (B, N_l)                               */

@@ -29,6 +29,11 @@
 // * k_headloss_finalize -- the 64 fp64 partial slots per (loss, level) -> fp32 losses
 //   (sum / avg_factor) * loss_weight, avg_factor = sum_b max(n_pos_b, 1) read from the
 //   assignment kernel's counts: the normaliser never visits the host.
+//
+// The plain RetinaHead (IA_CLS_SIGMOID_NOIOU, reference anchor_head.py:234-299) takes the same
+// entries: the box kernels carry the kind as a template parameter (IOU), and their IOU = false
+// instances are smooth-L1 alone -- no anchor, no decode, no IoU map read, no IoU gradient written;
+// the losses_iou entries of the result are 0.  Focal kernels, packed targets and slots are shared.
 #include <string.h>
 #include "ia_loss.hpp"
 
@@ -358,7 +363,7 @@ struct BoxMLArgs {
     int32_t attach;
 };
 
-template <typename T, bool BWD>
+template <typename T, bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
 {
     __shared__ double red[2][4];
@@ -380,27 +385,39 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
                                  load_f32<T>(bp + (size_t)2 * HW), load_f32<T>(bp + (size_t)3 * HW)};
             const float4 tq = reinterpret_cast<const float4 *>(a.bt[r.l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
-            const int y = p / W, x = p - y * W;
-            const float sx = (float)(x * a.lv.stride[r.l]), sy = (float)(y * a.lv.stride[r.l]);
-            const float *b4 = a.ba.v[r.l][r.an];
-            const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
-            const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
-            const float xl = load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e);
-            if (!BWD) {
+            if constexpr (IOU) {
+                const int y = p / W, x = p - y * W;
+                const float sx = (float)(x * a.lv.stride[r.l]), sy = (float)(y * a.lv.stride[r.l]);
+                const float *b4 = a.ba.v[r.l][r.an];
+                const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
+                const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
+                const float xl = load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e);
+                if (!BWD) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
+                    acc_l1 = (double)s;
+                    acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
+                } else {
+                    const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, r.l, a.lw_bbox);
+                    const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, r.l, a.lw_iou);
+                    g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
+                    float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
+                }
+            } else if (!BWD) {            // plain RetinaHead: smooth-L1 alone
                 float s = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
                 acc_l1 = (double)s;
-                acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
             } else {
                 const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, r.l, a.lw_bbox);
-                const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, r.l, a.lw_iou);
-                g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
-                float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
+                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1;
             }
         }
         if (BWD) {
@@ -409,7 +426,7 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
             go[(size_t)HW] = g_box[1];
             go[(size_t)2 * HW] = g_box[2];
             go[(size_t)3 * HW] = g_box[3];
-            a.g_iou[r.l][e] = g_iou;
+            if constexpr (IOU) a.g_iou[r.l][e] = g_iou;
         }
     }
     if (!BWD) {
@@ -420,7 +437,7 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
             const int w = threadIdx.x >> 6;
             if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
             __syncthreads();
-            if (threadIdx.x < 2) {
+            if (threadIdx.x < (IOU ? 2 : 1)) {
                 const double s = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) +
                                  red[threadIdx.x][3];
                 if (s != 0.0)
@@ -583,7 +600,7 @@ struct BoxNhwcArgs {
     int32_t g_pad[IA_MAX_LEVELS];         // bwd: zero-gradient channels behind d(iou) in the same pixel row
 };
 
-template <bool BWD>
+template <bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
 {
     __shared__ double red[2][4];
@@ -607,37 +624,55 @@ __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
             const float dp[4] = {d4.x, d4.y, d4.z, d4.w};
             const float4 tq = reinterpret_cast<const float4 *>(a.bt[l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
-            const int y = p / W, x = p - y * W;
-            const float sx = (float)(x * a.lv.stride[l]), sy = (float)(y * a.lv.stride[l]);
-            const float *b4 = a.ba.v[l][an];
-            const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
-            const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
-            const float xl = a.iou[l][pix * a.ps_iou[l] + an];
-            if (!BWD) {
+            if constexpr (IOU) {
+                const int y = p / W, x = p - y * W;
+                const float sx = (float)(x * a.lv.stride[l]), sy = (float)(y * a.lv.stride[l]);
+                const float *b4 = a.ba.v[l][an];
+                const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
+                const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
+                const float xl = a.iou[l][pix * a.ps_iou[l] + an];
+                if (!BWD) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
+                    acc_l1 = (double)s;
+                    acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
+                } else {
+                    const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, l, a.lw_bbox);
+                    const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, l, a.lw_iou);
+                    g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
+                    float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
+                }
+            } else if (!BWD) {            // plain RetinaHead: smooth-L1 alone
                 float s = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
                 acc_l1 = (double)s;
-                acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
             } else {
                 const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, l, a.lw_bbox);
-                const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, l, a.lw_iou);
-                g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
-                float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
+                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1;
             }
         }
         if (BWD) {
             *reinterpret_cast<float4 *>(a.g_reg[l] + pix * a.pg_reg[l] + 4 * an) =
                 make_float4(g_box[0], g_box[1], g_box[2], g_box[3]);
-            a.g_iou[l][pix * a.pg_iou[l] + an] = g_iou;
-            // d(reg) | d(iou) as slices of one wider tensor: its alignment channels behind the IoU
-            // slice get their zero gradient here (the last anchor's thread), not from a fill per level
-            if (an == A - 1)
-                for (int k = 0; k < a.g_pad[l]; ++k) a.g_iou[l][pix * a.pg_iou[l] + A + k] = 0.0f;
+            if constexpr (IOU) {
+                a.g_iou[l][pix * a.pg_iou[l] + an] = g_iou;
+                // d(reg) | d(iou) as slices of one wider tensor: its alignment channels behind the IoU
+                // slice get their zero gradient here (the last anchor's thread), not from a fill per level
+                if (an == A - 1)
+                    for (int k = 0; k < a.g_pad[l]; ++k) a.g_iou[l][pix * a.pg_iou[l] + A + k] = 0.0f;
+            } else {
+                // no IoU slice: the row is [reg 4A | padding], zeroed behind the reg slice
+                if (an == A - 1)
+                    for (int k = 0; k < a.g_pad[l]; ++k) a.g_reg[l][pix * a.pg_reg[l] + 4 * A + k] = 0.0f;
+            }
         }
     }
     if (!BWD) {
@@ -647,7 +682,7 @@ __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
             const int w = threadIdx.x >> 6;
             if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
             __syncthreads();
-            if (threadIdx.x < 2) {
+            if (threadIdx.x < (IOU ? 2 : 1)) {
                 const double s = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) +
                                  red[threadIdx.x][3];
                 if (s != 0.0)
@@ -696,13 +731,27 @@ __global__ void __launch_bounds__(64) k_headloss_finalize(FinArgs a)
     if (i == 0) a.res[kNumLoss * a.L + kNumLoss] = avg;
 }
 
+// the two kinds the node covers: sigmoid focal loss with (IoU-aware head) or without (plain
+// RetinaHead) the IoU term; the softmax kinds have no fused loss
+static bool sigmoid_kind(const ia_head_geom *g)
+{
+    return g->cls_activation == IA_CLS_SIGMOID || g->cls_activation == IA_CLS_SIGMOID_NOIOU;
+}
+// IoU maps (head outputs or gradients): all present with the IoU-aware kind, all NULL without it
+static bool iou_ptrs_ok(const ia_level_ptrs *p, int L, bool with_iou)
+{
+    for (int l = 0; l < L; ++l)
+        if ((p->iou[l] != nullptr) != with_iou) return false;
+    return true;
+}
+
 static int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
 {
     if (!g || B < 1) return IA_E_ARG;
     if (g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS) return IA_E_ARG;
     if (g->num_anchors < 1 || g->num_anchors > IA_MAX_ANCHORS || g->num_classes < 1) return IA_E_ARG;
     if (g->layout != IA_LAYOUT_NCHW) return IA_E_ARG;            // training kernels: NCHW only
-    if (g->cls_activation != IA_CLS_SIGMOID) return IA_E_ARG;    // sigmoid focal loss only
+    if (!sigmoid_kind(g)) return IA_E_ARG;                       // sigmoid focal loss only
     lv.L = g->num_levels; lv.B = B; lv.A = g->num_anchors; lv.C = g->num_classes;
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
         const bool on = l < lv.L;
@@ -782,6 +831,8 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
     if (rc) return rc;
     if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;      // other gammas: per-level path
     const int L = fa.lv.L;
+    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    if (!iou_ptrs_ok(p, L, with_iou)) return IA_E_ARG;
     BoxMLArgs ba;
     ba.lv = fa.lv;
     memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
@@ -797,7 +848,7 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
             (l < L ? batch * ((fa.lv.H[l] * fa.lv.W[l] + 255) / 256) : 0);
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
         const bool on = l < L;
-        if (on && (!p->cls[l] || !p->reg[l] || !p->iou[l] || !t->labels[l] || !t->label_weights[l] ||
+        if (on && (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
                    !t->bbox_targets[l] || !t->bbox_weights[l]))
             return IA_E_ARG;
         fa.cls[l] = on ? p->cls[l] : nullptr;
@@ -824,10 +875,12 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
     hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)pa.tile_off[L]), dim3(256), 0, s, pa);
     if (dtype == IA_F32) {
         hipLaunchKernelGGL((k_focal_ml<float, false>), dim3(fgrid), dim3(64), 0, s, fa);
-        hipLaunchKernelGGL((k_box_ml<float, false>), dim3(grid), dim3(256), 0, s, ba);
+        if (with_iou) hipLaunchKernelGGL((k_box_ml<float, false, true>), dim3(grid), dim3(256), 0, s, ba);
+        else hipLaunchKernelGGL((k_box_ml<float, false, false>), dim3(grid), dim3(256), 0, s, ba);
     } else if (dtype == IA_BF16) {
         hipLaunchKernelGGL((k_focal_ml<uint16_t, false>), dim3(fgrid), dim3(64), 0, s, fa);
-        hipLaunchKernelGGL((k_box_ml<uint16_t, false>), dim3(grid), dim3(256), 0, s, ba);
+        if (with_iou) hipLaunchKernelGGL((k_box_ml<uint16_t, false, true>), dim3(grid), dim3(256), 0, s, ba);
+        else hipLaunchKernelGGL((k_box_ml<uint16_t, false, false>), dim3(grid), dim3(256), 0, s, ba);
     } else return IA_E_ARG;
     FinArgs f;
     f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
@@ -850,14 +903,15 @@ int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
     if (rc) return rc;
     if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
     const int L = fa.lv.L;
+    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    if (!iou_ptrs_ok(p, L, with_iou) || !iou_ptrs_ok(grads, L, with_iou)) return IA_E_ARG;
     BoxMLArgs ba;
     ba.lv = fa.lv;
     memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
         const bool on = l < L;
-        if (on && (!p->cls[l] || !p->reg[l] || !p->iou[l] || !t->labels[l] || !t->label_weights[l] ||
-                   !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l] ||
-                   !grads->iou[l]))
+        if (on && (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
+                   !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l]))
             return IA_E_ARG;
         fa.cls[l] = on ? p->cls[l] : nullptr;
         fa.grad[l] = on ? (float *)grads->cls[l] : nullptr;
@@ -884,10 +938,12 @@ int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
     const unsigned grid = (unsigned)fa.lv.blk_off[L], fgrid = (unsigned)fa.lv.fblk_off[L];
     if (dtype == IA_F32) {
         hipLaunchKernelGGL((k_focal_ml<float, true>), dim3(fgrid), dim3(64), 0, s, fa);
-        hipLaunchKernelGGL((k_box_ml<float, true>), dim3(grid), dim3(256), 0, s, ba);
+        if (with_iou) hipLaunchKernelGGL((k_box_ml<float, true, true>), dim3(grid), dim3(256), 0, s, ba);
+        else hipLaunchKernelGGL((k_box_ml<float, true, false>), dim3(grid), dim3(256), 0, s, ba);
     } else if (dtype == IA_BF16) {
         hipLaunchKernelGGL((k_focal_ml<uint16_t, true>), dim3(fgrid), dim3(64), 0, s, fa);
-        hipLaunchKernelGGL((k_box_ml<uint16_t, true>), dim3(grid), dim3(256), 0, s, ba);
+        if (with_iou) hipLaunchKernelGGL((k_box_ml<uint16_t, true, true>), dim3(grid), dim3(256), 0, s, ba);
+        else hipLaunchKernelGGL((k_box_ml<uint16_t, true, false>), dim3(grid), dim3(256), 0, s, ba);
     } else return IA_E_ARG;
     return hip_status(hipGetLastError());
 }
@@ -901,7 +957,7 @@ static int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv)
     if (g->num_anchors < 1 || g->num_anchors > IA_MAX_ANCHORS || g->num_classes < 4 ||
         (g->num_classes & 3))
         return IA_E_ARG;                                  // class quads: C % 4 == 0
-    if (g->cls_activation != IA_CLS_SIGMOID) return IA_E_ARG;    // sigmoid focal loss only
+    if (!sigmoid_kind(g)) return IA_E_ARG;                       // sigmoid focal loss only
     if ((int64_t)g->num_anchors * (g->num_classes / 4) > 8192) return IA_E_ARG;   // float-reciprocal division
     lv.L = g->num_levels; lv.B = B; lv.A = g->num_anchors; lv.C = g->num_classes;
     int64_t foff = 0, boff = 0;
@@ -925,14 +981,15 @@ static int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv)
     return 0;
 }
 
-static int check_strides(const NhwcLevels &lv, const ia_level_pix_strides *st, const ia_level_ptrs *p)
+static int check_strides(const NhwcLevels &lv, const ia_level_pix_strides *st, const ia_level_ptrs *p,
+                         bool with_iou)
 {
     for (int l = 0; l < lv.L; ++l) {
-        if (st->cls[l] < (int64_t)lv.A * lv.C || st->reg[l] < (int64_t)lv.A * 4 || st->iou[l] < lv.A)
-            return IA_E_ARG;
+        if (st->cls[l] < (int64_t)lv.A * lv.C || st->reg[l] < (int64_t)lv.A * 4) return IA_E_ARG;
         if ((st->cls[l] & 3) || (st->reg[l] & 3)) return IA_E_ARG;          // 16-byte pieces
-        if (((uintptr_t)p->cls[l] & 15u) || ((uintptr_t)p->reg[l] & 15u) || ((uintptr_t)p->iou[l] & 3u))
-            return IA_E_ARG;
+        if (((uintptr_t)p->cls[l] & 15u) || ((uintptr_t)p->reg[l] & 15u)) return IA_E_ARG;
+        // the IoU strides are not looked at without the branch
+        if (with_iou && (st->iou[l] < lv.A || ((uintptr_t)p->iou[l] & 3u))) return IA_E_ARG;
     }
     return 0;
 }
@@ -952,11 +1009,13 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     const int L = fa.lv.L;
     if (workspace_bytes < sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS) return IA_E_WORKSPACE;
     if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
+    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    if (!iou_ptrs_ok(p, L, with_iou)) return IA_E_ARG;
     for (int l = 0; l < L; ++l)
-        if (!p->cls[l] || !p->reg[l] || !p->iou[l] || !t->labels[l] || !t->label_weights[l] ||
+        if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
             !t->bbox_targets[l] || !t->bbox_weights[l])
             return IA_E_ARG;
-    if ((rc = check_strides(fa.lv, strides, p))) return rc;
+    if ((rc = check_strides(fa.lv, strides, p, with_iou))) return rc;
     BoxNhwcArgs ba;
     ba.lv = fa.lv;
     memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
@@ -967,7 +1026,7 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
         fa.ps_cls[l] = on ? strides->cls[l] : 0; fa.ps_grad[l] = 0; fa.grad[l] = nullptr;
         fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
         ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
-        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = on ? strides->iou[l] : 0;
+        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
         ba.pg_reg[l] = ba.pg_iou[l] = 0;
         ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
         ba.g_reg[l] = ba.g_iou[l] = nullptr;
@@ -986,7 +1045,8 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((k_focal_nhwc<false>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
     for (int l = 0; l < IA_MAX_LEVELS; ++l) ba.g_pad[l] = 0;
-    hipLaunchKernelGGL((k_box_nhwc<false>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
+    if (with_iou) hipLaunchKernelGGL((k_box_nhwc<false, true>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
+    else hipLaunchKernelGGL((k_box_nhwc<false, false>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
     FinArgs f;
     f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
     if (!f.counts && !f.avg_dev && !(f.avg_host > 0.0f)) return IA_E_ARG;
@@ -1010,12 +1070,14 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     if (rc) return rc;
     const int L = fa.lv.L;
     if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
+    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    if (!iou_ptrs_ok(p, L, with_iou) || !iou_ptrs_ok(grads, L, with_iou)) return IA_E_ARG;
     for (int l = 0; l < L; ++l)
-        if (!p->cls[l] || !p->reg[l] || !p->iou[l] || !t->labels[l] || !t->label_weights[l] ||
-            !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l] ||
-            !grads->iou[l])
+        if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
+            !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l])
             return IA_E_ARG;
-    if ((rc = check_strides(fa.lv, strides, p)) || (rc = check_strides(fa.lv, grad_strides, grads)))
+    if ((rc = check_strides(fa.lv, strides, p, with_iou)) ||
+        (rc = check_strides(fa.lv, grad_strides, grads, with_iou)))
         return rc;
     BoxNhwcArgs ba;
     ba.lv = fa.lv;
@@ -1028,8 +1090,8 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
         fa.ps_grad[l] = on ? grad_strides->cls[l] : 0;
         fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
         ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
-        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = on ? strides->iou[l] : 0;
-        ba.pg_reg[l] = on ? grad_strides->reg[l] : 0; ba.pg_iou[l] = on ? grad_strides->iou[l] : 0;
+        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
+        ba.pg_reg[l] = on ? grad_strides->reg[l] : 0; ba.pg_iou[l] = (on && with_iou) ? grad_strides->iou[l] : 0;
         ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
         ba.g_reg[l] = on ? (float *)grads->reg[l] : nullptr;
         ba.g_iou[l] = on ? (float *)grads->iou[l] : nullptr;
@@ -1037,11 +1099,15 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
         // a row [X | reg | iou | pad] looks the same from here, and zero-filling behind iou would run into the
         // next pixel's X): the channels left up to the row's end get their zero gradient here
         ba.g_pad[l] = 0;
-        if (on && cfg->grad_rows_start_at_reg) {
+        if (on && cfg->grad_rows_start_at_reg && with_iou) {
             if (ba.g_iou[l] != ba.g_reg[l] + 4 * fa.lv.A || ba.pg_reg[l] != ba.pg_iou[l] ||
                 ba.pg_reg[l] < 5 * fa.lv.A || ba.pg_reg[l] - 5 * fa.lv.A > 64)
                 return IA_E_ARG;
             ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 5 * fa.lv.A);
+        } else if (on && cfg->grad_rows_start_at_reg) {
+            // without the IoU slice the row is [reg 4A | padding]
+            if (ba.pg_reg[l] - 4 * fa.lv.A > 64) return IA_E_ARG;          // (>= 4A: check_strides)
+            ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 4 * fa.lv.A);
         }
     }
     fa.sums = nullptr; fa.gin = grad_result; fa.res = result;
@@ -1055,7 +1121,8 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     ba.attach = cfg->attach_iou_target ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL((k_focal_nhwc<true>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
-    hipLaunchKernelGGL((k_box_nhwc<true>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
+    if (with_iou) hipLaunchKernelGGL((k_box_nhwc<true, true>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
+    else hipLaunchKernelGGL((k_box_nhwc<true, false>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
     return hip_status(hipGetLastError());
 }
 

@@ -156,6 +156,18 @@ class _RetinaHeadBase(AnchorHead):
             reg_feat = conv(reg_feat)
         return cls_feat, reg_feat
 
+    train_winograd = True                 # training: all-levels Winograd convolutions when usable
+
+    def forward(self, feats):
+        """multi_apply(forward_single) of the reference (anchor_head.py:102-103); in training on a
+        ROCm device every convolution runs once for all levels on the Winograd path with its own
+        backward (iouaware/winograd_train.py) -- same parameters, same outputs to fp32 rounding."""
+        if self.training and self.train_winograd:
+            from . import winograd_train
+            if winograd_train.usable(feats, self):
+                return winograd_train.head_forward(self, feats)
+        return super(_RetinaHeadBase, self).forward(feats)
+
     # ------------------------------------------------------------------ inference
     def _get_bboxes_batched(self, cls_scores, bbox_preds, iou_preds, img_metas, cfg, rescale):
         """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
@@ -188,6 +200,15 @@ class _RetinaHeadBase(AnchorHead):
         return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
 
     # ------------------------------------------------------------------ training
+    fuse_levels = True                    # all-levels loss kernels when the configuration allows
+
+    def _fused_loss_ok(self, cls_scores):
+        from .losses import FocalLoss, SmoothL1Loss
+        return (self.fuse_levels and type(self.loss_cls) is FocalLoss
+                and type(self.loss_bbox) is SmoothL1Loss and float(self.loss_cls.gamma) == 2.0
+                and self.use_sigmoid_cls and not self.sampling and cls_scores[0].is_cuda
+                and cls_scores[0].dtype in (torch.float32, torch.bfloat16))
+
     def _device_targets_ok(self, cfg, gt_bboxes, gt_bboxes_ignore, device):
         """the HIP assigner covers the IoU-aware configs' train_cfg (MaxIoUAssigner,
         gt_max_assign_all, allowed_border=-1, no ignore regions, no sampling); anything else
@@ -260,18 +281,6 @@ class IoUawareRetinaHead(_RetinaHeadBase):
         super(IoUawareRetinaHead, self).init_weights()
         normal_init(self.retina_iou, std=0.01)
 
-    train_winograd = True                 # training: all-levels Winograd convolutions when usable
-
-    def forward(self, feats):
-        """multi_apply(forward_single) of the reference (anchor_head.py:102-103); in training on a
-        ROCm device every convolution runs once for all levels on the Winograd path with its own
-        backward (iouaware/winograd_train.py) -- same parameters, same outputs to fp32 rounding."""
-        if self.training and self.train_winograd:
-            from . import winograd_train
-            if winograd_train.usable(feats, self):
-                return winograd_train.head_forward(self, feats)
-        return super(IoUawareRetinaHead, self).forward(feats)
-
     def forward_single(self, x):
         cls_feat, reg_feat = self._towers(x)
         return self.retina_cls(cls_feat), self.retina_reg(reg_feat), self.retina_iou(reg_feat)
@@ -323,15 +332,6 @@ class IoUawareRetinaHead(_RetinaHeadBase):
                                                    self.num_anchors, num_total_samples)
         return loss_cls, loss_bbox, loss_iou
 
-
-    fuse_levels = True                    # all-levels loss kernels when the configuration allows
-
-    def _fused_loss_ok(self, cls_scores):
-        from .losses import FocalLoss, SmoothL1Loss
-        return (self.fuse_levels and type(self.loss_cls) is FocalLoss
-                and type(self.loss_bbox) is SmoothL1Loss and float(self.loss_cls.gamma) == 2.0
-                and self.use_sigmoid_cls and not self.sampling and cls_scores[0].is_cuda
-                and cls_scores[0].dtype in (torch.float32, torch.bfloat16))
 
     def loss(self, cls_scores, bbox_preds, iou_preds, gt_bboxes, gt_labels, img_metas, cfg,
              gt_bboxes_ignore=None):
@@ -408,8 +408,10 @@ class RetinaHead(_RetinaHeadBase):
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, cfg,
              gt_bboxes_ignore=None):
         """-> dict(loss_cls, loss_bbox), each a list of per-level (1,) tensors, or None when an
-        image has no valid anchor (anchor_head.py:234-299): focal / cross-entropy and smooth-L1
-        per level on the HIP loss kernels."""
+        image has no valid anchor (anchor_head.py:234-299): focal loss (gamma = 2) and smooth-L1
+        of all levels in one autograd node (csrc/headloss.hip, the kind without the IoU term) when
+        `_fused_loss_ok`, else focal / cross-entropy and smooth-L1 per level on the HIP loss
+        kernels."""
         for lo in (self.loss_cls, self.loss_bbox):
             if type(lo).__name__ in ('IOUbalancedSigmoidFocalLoss', 'IoUbalancedSmoothL1Loss'):
                 raise NotImplementedError('%s on RetinaHead needs an IoU target without an IoU '
@@ -420,11 +422,21 @@ class RetinaHead(_RetinaHeadBase):
         for t in list(cls_scores) + list(bbox_preds):
             ops._require_gpu(t, 'head output')
         geom = self.geometry(featmap_sizes, -1)
+        fused = self._fused_loss_ok(cls_scores)
         targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
-                                gt_bboxes_ignore, cls_scores[0].device)
+                                gt_bboxes_ignore, cls_scores[0].device, counts_as_normaliser=fused)
         if targets is None:
             return None
-        labels, label_w, bbox_t, bbox_w, _, num_total_samples, _ = targets
+        labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts = targets
+        if fused:
+            on_dev = level_anchors[0] is None          # targets came from the HIP assigner
+            return ops.head_loss(
+                geom, cls_scores, bbox_preds, None, labels, label_w, bbox_t, bbox_w,
+                counts=counts if on_dev else None,
+                avg_factor=None if on_dev else num_total_samples,
+                gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
+                loss_weight_cls=self.loss_cls.loss_weight, beta=self.loss_bbox.beta,
+                loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=False)
         losses_cls, losses_bbox = [], []
         for l in range(len(featmap_sizes)):
             B, n_l = cls_scores[l].shape[0], geom.level_anchors[l]

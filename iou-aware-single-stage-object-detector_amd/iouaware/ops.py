@@ -1463,12 +1463,16 @@ def _zero1(dev):
 
 class _HeadLossFn(torch.autograd.Function):
     """the three losses of every level: 3 launches forward, 2 backward (csrc/headloss.hip).
-    Outputs: 3L per-level (1,) tensors and 3 totals, views of one result vector."""
+    Outputs: 3L per-level (1,) tensors and 3 totals, views of one result vector.  A geometry without
+    the IoU branch takes 2L head outputs (cls, reg): the IoU pointers stay NULL, the losses_iou
+    entries of the result are 0 and gradients come back for cls and reg only."""
 
     @staticmethod
     def forward(ctx, geom, targets, cfg, *outs):
         L = geom.L
-        cls, reg, iou = outs[:L], outs[L:2 * L], outs[2 * L:3 * L]
+        if len(outs) != (3 if geom.iou_branch else 2) * L:
+            raise AssertionError('expected %d head outputs' % ((3 if geom.iou_branch else 2) * L))
+        cls, reg, iou = outs[:L], outs[L:2 * L], outs[2 * L:]
         for t in outs:
             _require_gpu(t, 'head output')
         cls, reg, iou = [[t.contiguous() for t in x] for x in (cls, reg, iou)]
@@ -1477,7 +1481,8 @@ class _HeadLossFn(torch.autograd.Function):
             raise TypeError('head outputs must share one dtype')
         p = LevelPtrs()
         for l in range(L):
-            p.cls[l], p.reg[l], p.iou[l] = cls[l].data_ptr(), reg[l].data_ptr(), iou[l].data_ptr()
+            p.cls[l], p.reg[l] = cls[l].data_ptr(), reg[l].data_ptr()
+            p.iou[l] = iou[l].data_ptr() if iou else None
         labels, lw, bt, bw, counts, avg = targets
         labels = [t.contiguous().to(torch.int64) for t in labels]
         lw = [t.contiguous().to(torch.float32) for t in lw]
@@ -1524,8 +1529,8 @@ class _HeadLossFn(torch.autograd.Function):
         grads = [[torch.empty(t.shape, dtype=torch.float32, device=dev) for t in x]
                  for x in (cls, reg, iou)]
         for l in range(L):
-            gp.cls[l], gp.reg[l], gp.iou[l] = (grads[0][l].data_ptr(), grads[1][l].data_ptr(),
-                                               grads[2][l].data_ptr())
+            gp.cls[l], gp.reg[l] = grads[0][l].data_ptr(), grads[1][l].data_ptr()
+            gp.iou[l] = grads[2][l].data_ptr() if iou else None
         _lib.check(_lib.lib().ia_head_loss_bwd(ctx.geom.ref(), C.byref(p), ctx.dt, ctx.B,
                                                C.byref(ht), C.byref(ctx.cfg), _ptr(ctx.ws),
                                                _ptr(ctx.res), _ptr(gin), C.byref(gp), _stream()),
@@ -1552,8 +1557,17 @@ def _pix_stride(t):
 
 def _shared_base(r, i):
     """reg / iou as channel slices of ONE channels-last tensor (the training head's 48-channel
-    output): -> that tensor, else None"""
+    output): -> that tensor, else None.  i = None (a head without the IoU branch): the reg-only form,
+    reg as channels [0, 4A) of a wider channels-last tensor."""
     b = r._base
+    if i is None:
+        if b is None or b.dim() != 4 or b.dtype != torch.float32 \
+                or not b.is_contiguous(memory_format=torch.channels_last) \
+                or tuple(b.shape[2:]) != tuple(r.shape[2:]) or b.shape[0] != r.shape[0] \
+                or _pix_stride(r) != b.shape[1] or r.storage_offset() != b.storage_offset() \
+                or r.shape[1] > b.shape[1]:
+            return None
+        return b
     if b is None or b is not i._base or b.dim() != 4 or b.dtype != torch.float32 \
             or not b.is_contiguous(memory_format=torch.channels_last) \
             or tuple(b.shape[2:]) != tuple(r.shape[2:]) or b.shape[0] != r.shape[0]:
@@ -1574,7 +1588,8 @@ class _HeadLossNhwcFn(torch.autograd.Function):
     """the three losses of every level on channels-last head outputs (csrc/headloss.hip,
     k_focal_nhwc / k_box_nhwc): no layout copies, no packed targets.  Inputs: cls[L], then either
     reg[L] + iou[L], or (fused) the L wider tensors reg / iou are channel slices of -- their
-    gradient is then written in place into one tensor of that shape."""
+    gradient is then written in place into one tensor of that shape.  Without the IoU branch:
+    cls[L] + reg[L], or (fused) cls[L] + the wider tensors whose channels [0, 4A) are reg."""
 
     @staticmethod
     def forward(ctx, geom, targets, cfg, views, *outs):
@@ -1586,12 +1601,15 @@ class _HeadLossNhwcFn(torch.autograd.Function):
             reg, iou = views
         else:
             bases = None
-            reg, iou = list(outs[L:2 * L]), list(outs[2 * L:3 * L])
+            reg = list(outs[L:2 * L])
+            iou = list(outs[2 * L:3 * L]) if geom.iou_branch else None
         B, dev = cls[0].shape[0], cls[0].device
         p, st = LevelPtrs(), _lib.LevelPixStrides()
         for l in range(L):
-            p.cls[l], p.reg[l], p.iou[l] = cls[l].data_ptr(), reg[l].data_ptr(), iou[l].data_ptr()
-            st.cls[l], st.reg[l], st.iou[l] = _pix_stride(cls[l]), _pix_stride(reg[l]), _pix_stride(iou[l])
+            p.cls[l], p.reg[l] = cls[l].data_ptr(), reg[l].data_ptr()
+            st.cls[l], st.reg[l] = _pix_stride(cls[l]), _pix_stride(reg[l])
+            if iou is not None:
+                p.iou[l], st.iou[l] = iou[l].data_ptr(), _pix_stride(iou[l])
         labels, lw, bt, bw, counts, avg = targets
         labels = [t.contiguous().to(torch.int64) for t in labels]
         lw = [t.contiguous().to(torch.float32) for t in lw]
@@ -1639,22 +1657,27 @@ class _HeadLossNhwcFn(torch.autograd.Function):
             # rows with more than 64 padding channels are cleared here and the flag stays off)
             g_base = [torch.empty(b.shape, dtype=torch.float32, device=dev, memory_format=cl)
                       for b in bases]
-            in_kernel = all(b.shape[1] - (reg[l].shape[1] + iou[l].shape[1]) <= 64 for l, b in enumerate(bases))
+            used = [reg[l].shape[1] + (iou[l].shape[1] if iou is not None else 0) for l in range(L)]
+            in_kernel = all(b.shape[1] - used[l] <= 64 for l, b in enumerate(bases))
             ctx.cfg.grad_rows_start_at_reg = 1 if in_kernel else 0
             if not in_kernel:
                 for gb in g_base:
                     gb.zero_()
             for l in range(L):
                 gp.reg[l] = g_base[l].data_ptr() + (reg[l].data_ptr() - bases[l].data_ptr())
-                gp.iou[l] = g_base[l].data_ptr() + (iou[l].data_ptr() - bases[l].data_ptr())
-                gst.reg[l] = gst.iou[l] = bases[l].shape[1]
+                gst.reg[l] = bases[l].shape[1]
+                if iou is not None:
+                    gp.iou[l] = g_base[l].data_ptr() + (iou[l].data_ptr() - bases[l].data_ptr())
+                    gst.iou[l] = bases[l].shape[1]
             tail = g_base
         else:
             g_reg = [torch.empty(t.shape, dtype=torch.float32, device=dev, memory_format=cl) for t in reg]
-            g_iou = [torch.empty(t.shape, dtype=torch.float32, device=dev, memory_format=cl) for t in iou]
+            g_iou = [torch.empty(t.shape, dtype=torch.float32, device=dev, memory_format=cl)
+                     for t in (iou or [])]
             for l in range(L):
-                gp.reg[l], gp.iou[l] = g_reg[l].data_ptr(), g_iou[l].data_ptr()
-                gst.reg[l], gst.iou[l] = reg[l].shape[1], iou[l].shape[1]
+                gp.reg[l], gst.reg[l] = g_reg[l].data_ptr(), reg[l].shape[1]
+                if iou is not None:
+                    gp.iou[l], gst.iou[l] = g_iou[l].data_ptr(), iou[l].shape[1]
             tail = g_reg + g_iou
             ctx.cfg.grad_rows_start_at_reg = 0
         for l in range(L):
@@ -1667,17 +1690,18 @@ class _HeadLossNhwcFn(torch.autograd.Function):
 
 
 def _nhwc_route(geom, cls, reg, iou):
-    """-> (views or None, inputs) when every head output is channels-last-like fp32, else None"""
-    if geom.C % 4 or geom.A * (geom.C // 4) > 8192 \
-            or any(_pix_stride(t) is None for t in list(cls) + list(reg) + list(iou)):
+    """-> (views or None, inputs) when every head output is channels-last-like fp32, else None.
+    iou = None: a head without the IoU branch (views = (reg, None))"""
+    maps = list(cls) + list(reg) + (list(iou) if iou is not None else [])
+    if geom.C % 4 or geom.A * (geom.C // 4) > 8192 or any(_pix_stride(t) is None for t in maps):
         return None
     if any((_pix_stride(t) % 4) for t in list(cls) + list(reg)) \
             or any(t.data_ptr() % 16 for t in list(cls) + list(reg)):
         return None
-    bases = [_shared_base(r, i) for r, i in zip(reg, iou)]
+    bases = [_shared_base(r, i) for r, i in zip(reg, iou if iou is not None else [None] * len(reg))]
     if all(b is not None for b in bases):
-        return (list(reg), list(iou)), list(cls) + bases
-    return None, list(cls) + list(reg) + list(iou)
+        return (list(reg), list(iou) if iou is not None else None), list(cls) + bases
+    return None, maps
 
 
 def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_weights, counts=None,
@@ -1685,10 +1709,15 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
               loss_weight_bbox=1.0, attach_iou_target=True, exact_large_logits=False,
               channels_last=None):
     """FocalLoss(gamma=2) + SmoothL1Loss + IoU BCE of every pyramid level in one autograd node.
+    iou=None with a geometry built with iou_branch=False (the plain RetinaHead): FocalLoss +
+    SmoothL1Loss alone, -> dict(loss_cls, loss_bbox) (the reference's keys, anchor_head.py:299).
     channels_last: None = the channels-last kernels when every head output is channels-last(-like)
     fp32 (the training head's outputs are), else the NCHW kernels; True / False force a route.
     Normaliser: `counts` ((B,2) of anchor_targets: sum_b max(n_pos_b, 1), stays on the device), else
     `avg_factor` (python number or device scalar).  -> dict of three LevelLosses lists."""
+    if (iou is None) == geom.iou_branch:
+        raise ValueError('iou maps %s for a head %s the IoU branch'
+                         % (('missing', 'with') if iou is None else ('given', 'without')))
     if counts is None and avg_factor is None:
         raise ValueError('head_loss needs counts or avg_factor')
     if float(gamma) != 2.0:
@@ -1704,9 +1733,10 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
     elif channels_last is True:
         raise ValueError('channels_last=True needs channels-last fp32 head outputs, C % 4 == 0')
     else:
-        flat = _HeadLossFn.apply(geom, targets, cfg, *(list(cls) + list(reg) + list(iou)))
+        flat = _HeadLossFn.apply(geom, targets, cfg,
+                                 *(list(cls) + list(reg) + (list(iou) if iou is not None else [])))
     out = {}
-    for k, name in enumerate(('loss_cls', 'loss_bbox', 'losses_iou')):
+    for k, name in enumerate(('loss_cls', 'loss_bbox', 'losses_iou')[:3 if geom.iou_branch else 2]):
         lst = LevelLosses(flat[k * L:(k + 1) * L])
         lst.total = flat[3 * L + k]
         out[name] = lst

@@ -220,33 +220,44 @@ def _library_loads():
 
 def usable(feats, head):
     towers = list(head.cls_convs) + list(head.reg_convs)
+    outs = [head.retina_cls, head.retina_reg] + ([head.retina_iou] if head.iou_branch else [])
     return (torch.is_grad_enabled() and all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
                                             for x in feats)
             and head.in_channels % 4 == 0 and head.feat_channels % 4 == 0
             and (head.num_anchors * head.cls_out_channels) % 4 == 0
             and all(not m.with_norm and m.with_activatation and _plain_3x3(m.conv) for m in towers)
-            and all(_plain_3x3(c) for c in (head.retina_cls, head.retina_reg, head.retina_iou))
+            and all(_plain_3x3(c) for c in outs)
             and _library_loads())
 
 
 def head_forward(head, feats):
     """IoUawareRetinaHead.forward (multi_apply(forward_single), reference :171-219) with every
     convolution evaluated for all levels at once.  Returns (cls[L], reg[L], iou[L]); reg / iou are
-    channel slices of one 48-channel output (retina_reg | retina_iou | zero padding)."""
+    channel slices of one 48-channel output (retina_reg | retina_iou | zero padding).
+    A head without the IoU branch (RetinaHead.forward, retina_head.py:79-90): (cls[L], reg[L]),
+    retina_reg alone as the second output convolution -- its own tensor when 4A is a multiple of 4
+    (always, with integer A), else the leading slice of the zero-padded one."""
     cls_feat = reg_feat = [_cl(x) for x in feats]
     for conv in head.cls_convs:
         cls_feat = wino_conv_levels(cls_feat, conv.conv.weight, conv.conv.bias, relu=True)
     for conv in head.reg_convs:
         reg_feat = wino_conv_levels(reg_feat, conv.conv.weight, conv.conv.bias, relu=True)
     cls = wino_conv_levels(cls_feat, head.retina_cls.weight, head.retina_cls.bias)
-    n_reg, n_iou = head.retina_reg.out_channels, head.retina_iou.out_channels
+    convs = [head.retina_reg] + ([head.retina_iou] if head.iou_branch else [])
+    n_reg = head.retina_reg.out_channels
+    n_iou = head.retina_iou.out_channels if head.iou_branch else 0
     pad = (-(n_reg + n_iou)) % 4
-    w_ri = torch.cat([head.retina_reg.weight, head.retina_iou.weight] +
+    if len(convs) == 1 and not pad:
+        reg = wino_conv_levels(reg_feat, head.retina_reg.weight, head.retina_reg.bias)
+        return cls, reg
+    w_ri = torch.cat([c.weight for c in convs] +
                      ([head.retina_reg.weight.new_zeros((pad,) + tuple(head.retina_reg.weight.shape[1:]))]
                       if pad else []))
-    b_ri = torch.cat([head.retina_reg.bias, head.retina_iou.bias] +
+    b_ri = torch.cat([c.bias for c in convs] +
                      ([head.retina_reg.bias.new_zeros(pad)] if pad else []))
     ri = wino_conv_levels(reg_feat, w_ri, b_ri)
     reg = [t[:, :n_reg] for t in ri]
+    if not head.iou_branch:
+        return cls, reg
     iou = [t[:, n_reg:n_reg + n_iou] for t in ri]
     return cls, reg, iou

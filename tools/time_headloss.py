@@ -1,9 +1,14 @@
 """Loss part of one training iteration (BASELINE config 5 shapes: B images of 800x1344, fixed head
 outputs): device target assignment + the three losses of all levels forward + parse_losses +
 backward.  Prints wall per iteration (HIP events); under rocprofv3 the kernel trace is reduced by
-tools/summarize_trace.py with the marker `k_box_ml<float, true>` (last kernel of an iteration).
+tools/summarize_trace.py with the marker `k_box_ml<float, true` (last kernel of an iteration).
 
-    python tools/time_headloss.py [B] [per_level | nhwc]
+    python tools/time_headloss.py [B] [per_level | nhwc] [plain | --head {iou_aware,plain}] [--iters N]
+
+`plain` (or `--head plain`): the plain RetinaHead built from the same settings, the IoU maps
+dropped -- FocalLoss + SmoothL1Loss alone, on the same three routes (the all-levels node without
+the IoU term, the per-level kernels, the channels-last kernels with reg as its own tensor, as its
+training head produces it).  The focal part, and with it the algorithmic-bytes line, is shared.
 """
 import os
 import sys
@@ -14,25 +19,47 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import synth  # noqa: E402
 from iouaware.config import ConfigDict  # noqa: E402
-from iouaware.head import IoUawareRetinaHead  # noqa: E402
+from iouaware.head import IoUawareRetinaHead, RetinaHead  # noqa: E402
 from iouaware.train import parse_losses  # noqa: E402
 import bench  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-per_level = len(sys.argv) > 2 and sys.argv[2] == 'per_level'
-nhwc = len(sys.argv) > 2 and sys.argv[2] == 'nhwc'      # channels-last outputs, reg | iou as slices of one
+args = sys.argv[1:]
+plain = 'plain' in args
+if '--head' in args:
+    k = args.index('--head')
+    if k + 1 >= len(args) or args[k + 1] not in ('iou_aware', 'plain'):
+        sys.exit('--head takes iou_aware or plain')
+    plain = args[k + 1] == 'plain'
+    del args[k:k + 2]
+n = 20                                   # timed iterations (--iters: a longer window, less host noise)
+if '--iters' in args:
+    k = args.index('--iters')
+    n = int(args[k + 1])
+    del args[k:k + 2]
+args = [a for a in args if a != 'plain']
+B = int(args[0]) if args else 4
+per_level = len(args) > 1 and args[1] == 'per_level'
+nhwc = len(args) > 1 and args[1] == 'nhwc'              # channels-last outputs, reg | iou as slices of one
                                                          # 48-channel tensor: what the training head produces
 TRAIN_CFG = ConfigDict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg_iou_thr=0.4,
                                      min_pos_iou=0, ignore_iof_thr=-1), allowed_border=-1,
                        pos_weight=-1, debug=False)
 kw = dict(bench.MODEL['bbox_head'])
 kw.pop('type')
-head = IoUawareRetinaHead(**kw).cuda()
+if plain:
+    for k in ('loss_iou', 'attach_iou_target'):
+        kw.pop(k, None)
+head = (RetinaHead if plain else IoUawareRetinaHead)(**kw).cuda()
 head.fuse_levels = not per_level
 cls, reg, iou = synth.head_outputs(3, B, 800, 1344, 'A')
-outs = [[torch.from_numpy(t).cuda().requires_grad_(True) for t in x] for x in (cls, reg, iou)]
+outs = [[torch.from_numpy(t).cuda().requires_grad_(True) for t in x]
+        for x in ((cls, reg) if plain else (cls, reg, iou))]
 leaves = [t for x in outs for t in x]
-if nhwc:
+if nhwc and plain:
+    outs = [[t.detach().contiguous(memory_format=torch.channels_last).requires_grad_(True) for t in x]
+            for x in outs]
+    leaves = [t for x in outs for t in x]
+elif nhwc:
     cl = torch.channels_last
     c = [t.detach().contiguous(memory_format=cl).requires_grad_(True) for t in outs[0]]
     ri = [torch.cat([r.detach(), i.detach(), r.detach()[:, :3] * 0], 1).contiguous(memory_format=cl)
@@ -65,14 +92,14 @@ for _ in range(5):
     it()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 torch.cuda.synchronize()
-n = 20
 e0.record()
 for _ in range(n):
     it()
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / n
-print('B=%d %s: targets + losses fwd + bwd  %.3f ms per iteration' %
-      (B, 'per-level kernels' if per_level else 'all-levels kernels', ms))
+print('B=%d %s%s: targets + losses fwd + bwd  %.3f ms per iteration' %
+      (B, 'plain RetinaHead, ' if plain else '',
+       'per-level kernels' if per_level else 'all-levels kernels', ms))
 print('focal algorithmic bytes: fwd %.1f MB, bwd %.1f MB per iteration' %
       (66931200 * B / 1e6, 131443200 * B / 1e6))
