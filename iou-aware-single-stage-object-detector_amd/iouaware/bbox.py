@@ -109,3 +109,10 @@ def multi_apply(func, *args, **kwargs):
     from functools import partial
     f = partial(func, **kwargs) if kwargs else func
     return tuple(map(list, zip(*map(f, *args))))
+
+
+def per_image(dets, labels, rows, num):
+    """a head's batched device result (get_bboxes_batched) -> list over images of
+    (det_bboxes (k,5) fp32, det_labels (k,) int64), k <= max_per_img"""
+    counts = num.tolist()                                       # the one host sync per batch
+    return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]

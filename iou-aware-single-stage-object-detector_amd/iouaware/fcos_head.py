@@ -11,13 +11,17 @@ constructor kwargs, parameter names and method signatures.
   * loss: targets and the terms in torch ops on the device, the class term through the
     HIP sigmoid focal-loss op (integer targets, the reference CUDA op's semantics).
 There is no CPU fallback for get_bboxes / loss: they need tensors on a gfx950 device.
+
+Both heads are `_FCOSHeadBase` with the class attribute `iou_branch` (fcos_iou present or absent):
+layers, forward, targets, the loss body (`_loss`) and the decode call (`_get_bboxes_batched`) are
+written once; the two classes keep the reference's differing public signatures.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fcos_ops
-from .bbox import bbox_overlaps, distance2bbox, multi_apply
+from .bbox import bbox_overlaps, distance2bbox, multi_apply, per_image
 from .focal_op import sigmoid_focal_loss
 from .layers import ConvModule, Scale, bias_init_with_prob, normal_init
 from .losses import iou_loss
@@ -48,8 +52,11 @@ class _FCOSHeadBase(nn.Module):
         self.norm_cfg = norm_cfg
         self._init_layers()
 
-    def _init_towers(self):
-        """the GN towers and fcos_cls / fcos_centerness / fcos_reg, in the reference's order"""
+    iou_branch = False                    # IoUawareFCOSHead: fcos_iou on the reg tower
+
+    def _init_layers(self):
+        """the GN towers, fcos_cls / fcos_centerness / fcos_reg [/ fcos_iou] and the scales, in
+        the reference's order"""
         self.cls_convs = nn.ModuleList()
         self.reg_convs = nn.ModuleList()
         for i in range(self.stacked_convs):
@@ -61,8 +68,11 @@ class _FCOSHeadBase(nn.Module):
         self.fcos_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.fcos_centerness = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
         self.fcos_reg = nn.Conv2d(self.feat_channels, 4, 3, padding=1)
+        if self.iou_branch:
+            self.fcos_iou = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
 
-    def _init_tower_weights(self):
+    def init_weights(self):
         for m in self.cls_convs:
             normal_init(m.conv, std=0.01)
         for m in self.reg_convs:
@@ -70,6 +80,26 @@ class _FCOSHeadBase(nn.Module):
         normal_init(self.fcos_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.fcos_reg, std=0.01)
         normal_init(self.fcos_centerness, std=0.01)
+        if self.iou_branch:
+            normal_init(self.fcos_iou, std=0.01)
+
+    def forward(self, feats):
+        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L][, ious[L]])"""
+        return multi_apply(self.forward_single, feats, self.scales)
+
+    def forward_single(self, x, scale):
+        cls_feat = x
+        reg_feat = x
+        for cls_layer in self.cls_convs:
+            cls_feat = cls_layer(cls_feat)
+        cls_score = self.fcos_cls(cls_feat)
+        centerness = self.fcos_centerness(cls_feat)
+        for reg_layer in self.reg_convs:
+            reg_feat = reg_layer(reg_feat)
+        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
+        if not self.iou_branch:
+            return cls_score, bbox_pred, centerness
+        return cls_score, bbox_pred, centerness, self.fcos_iou(reg_feat)
 
     # ------------------------------------------------------------------ points / targets
     def get_points(self, featmap_sizes, dtype, device):
@@ -138,12 +168,18 @@ class _FCOSHeadBase(nn.Module):
         return torch.sqrt(c)
 
     # ------------------------------------------------------------------ training
-    def _flat_loss_inputs(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels):
-        """targets and the per-point flattened outputs of the batch (image-major inside a level)"""
+    def _loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, cfg):
+        """focal classification over (num_pos + num_imgs), the centerness-weighted IoU loss, the
+        centerness BCE and, with the IoU branch, the IoU BCE whose target is
+        NOT detached (as in the reference: its gradient reaches bbox_preds too)"""
+        maps = (cls_scores, bbox_preds, centernesses) + ((ious,) if self.iou_branch else ())
+        if len(set(len(m) for m in maps)) != 1:
+            raise AssertionError('level count mismatch')
         featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores]
         all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device)
         labels, bbox_targets = self.fcos_target(all_level_points, gt_bboxes, gt_labels)
         num_imgs = cls_scores[0].size(0)
+        # per-point flattened outputs of the batch (image-major inside a level)
         flat_cls = torch.cat([c.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
                               for c in cls_scores])
         flat_bbox = torch.cat([b.permute(0, 2, 3, 1).reshape(-1, 4) for b in bbox_preds])
@@ -151,7 +187,42 @@ class _FCOSHeadBase(nn.Module):
         flat_labels = torch.cat(labels)
         flat_bbox_targets = torch.cat(bbox_targets)
         flat_points = torch.cat([points.repeat(num_imgs, 1) for points in all_level_points])
-        return num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points
+        if self.iou_branch:
+            flat_iou = torch.cat([i.permute(0, 2, 3, 1).reshape(-1) for i in ious])
+
+        pos_inds = flat_labels.nonzero().reshape(-1)
+        num_pos = len(pos_inds)
+        loss_cls = sigmoid_focal_loss(flat_cls.contiguous(), flat_labels, cfg.gamma, cfg.alpha,
+                                      'none').sum()[None] / (num_pos + num_imgs)
+        pos_bbox_preds = flat_bbox[pos_inds]
+        pos_bbox_targets = flat_bbox_targets[pos_inds]
+        pos_centerness = flat_ctr[pos_inds]
+        if self.iou_branch:
+            pos_iou = flat_iou[pos_inds]
+        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
+        if num_pos > 0:
+            pos_points = flat_points[pos_inds]
+            pos_decoded_bbox_preds = distance2bbox(pos_points, pos_bbox_preds)
+            pos_decoded_target_preds = distance2bbox(pos_points, pos_bbox_targets)
+            loss_reg = ((iou_loss(pos_decoded_bbox_preds, pos_decoded_target_preds,
+                                  reduction='none') * pos_centerness_targets).sum() /
+                        pos_centerness_targets.sum())[None]
+            loss_centerness = F.binary_cross_entropy_with_logits(
+                pos_centerness, pos_centerness_targets, reduction='mean')[None]
+            if self.iou_branch:
+                pos_iou_target = bbox_overlaps(pos_decoded_target_preds, pos_decoded_bbox_preds,
+                                               is_aligned=True)
+                loss_iou = F.binary_cross_entropy_with_logits(pos_iou, pos_iou_target,
+                                                              reduction='mean')[None]
+        else:
+            loss_reg = pos_bbox_preds.sum()[None]
+            loss_centerness = pos_centerness.sum()[None]
+            if self.iou_branch:
+                loss_iou = pos_iou.sum()[None]
+        losses = dict(loss_cls=loss_cls, loss_reg=loss_reg, loss_centerness=loss_centerness)
+        if self.iou_branch:
+            losses['loss_iou'] = loss_iou
+        return losses
 
     # ------------------------------------------------------------------ inference
     def geometry(self, featmap_sizes, nms_pre=-1):
@@ -164,107 +235,50 @@ class _FCOSHeadBase(nn.Module):
                                                     self.score_alpha)
         return g
 
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, third, img_metas, cfg, rescale):
+        """third: the maps of the decode's third slot -- ious with the IoU branch (fused alpha
+        score), centernesses without (score = sigmoid(cls) * sigmoid(centerness))"""
+        if not len(cls_scores) == len(bbox_preds) == len(third) == len(self.strides):
+            raise AssertionError('level count mismatch')
+        nms_cfg = dict(cfg.nms)
+        nms_type = nms_cfg.pop('type', 'nms')
+        if nms_type != 'nms':
+            raise NotImplementedError('%s: test_cfg.nms.type %r (hard NMS only)'
+                                      % (type(self).__name__, nms_type))
+        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
+        shapes = [m['img_shape'] for m in img_metas]
+        factors = [m['scale_factor'] for m in img_metas]
+        entry = fcos_ops.point_get_bboxes if self.iou_branch else fcos_ops.point_ctr_get_bboxes
+        return entry(geom, [c.detach() for c in cls_scores], [b.detach() for b in bbox_preds],
+                     [t.detach() for t in third], shapes, factors, rescale, cfg.score_thr,
+                     nms_cfg['iou_thr'], cfg.max_per_img)
+
 
 @HEADS.register_module
 class IoUawareFCOSHead(_FCOSHeadBase):
     # score = sigmoid(cls) ** alpha * sigmoid(iou) ** (1 - alpha), hard-coded in the reference
     # (iou_aware_fcos_head.py:326)
     score_alpha = 0.3
-
-    def _init_layers(self):
-        self._init_towers()
-        self.fcos_iou = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
-        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
-
-    def init_weights(self):
-        self._init_tower_weights()
-        normal_init(self.fcos_iou, std=0.01)
-
-    def forward(self, feats):
-        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L], ious[L])"""
-        return multi_apply(self.forward_single, feats, self.scales)
-
-    def forward_single(self, x, scale):
-        cls_feat = x
-        reg_feat = x
-        for cls_layer in self.cls_convs:
-            cls_feat = cls_layer(cls_feat)
-        cls_score = self.fcos_cls(cls_feat)
-        centerness = self.fcos_centerness(cls_feat)
-        for reg_layer in self.reg_convs:
-            reg_feat = reg_layer(reg_feat)
-        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
-        iou = self.fcos_iou(reg_feat)
-        return cls_score, bbox_pred, centerness, iou
+    iou_branch = True
 
     def loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, img_metas,
              cfg, gt_bboxes_ignore=None):
-        """the reference's four terms (iou_aware_fcos_head.py:121-244); the IoU target is NOT
-        detached (as in the reference: its gradient reaches bbox_preds too)"""
-        if not len(cls_scores) == len(bbox_preds) == len(centernesses) == len(ious):
-            raise AssertionError('level count mismatch')
-        num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points = \
-            self._flat_loss_inputs(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels)
-        flat_iou = torch.cat([i.permute(0, 2, 3, 1).reshape(-1) for i in ious])
+        """the reference's four terms (iou_aware_fcos_head.py:121-244)"""
+        return self._loss(cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, cfg)
 
-        pos_inds = flat_labels.nonzero().reshape(-1)
-        num_pos = len(pos_inds)
-        loss_cls = sigmoid_focal_loss(flat_cls.contiguous(), flat_labels, cfg.gamma, cfg.alpha,
-                                      'none').sum()[None] / (num_pos + num_imgs)
-        pos_bbox_preds = flat_bbox[pos_inds]
-        pos_bbox_targets = flat_bbox_targets[pos_inds]
-        pos_centerness = flat_ctr[pos_inds]
-        pos_iou = flat_iou[pos_inds]
-        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
-        if num_pos > 0:
-            pos_points = flat_points[pos_inds]
-            pos_decoded_bbox_preds = distance2bbox(pos_points, pos_bbox_preds)
-            pos_decoded_target_preds = distance2bbox(pos_points, pos_bbox_targets)
-            loss_reg = ((iou_loss(pos_decoded_bbox_preds, pos_decoded_target_preds,
-                                  reduction='none') * pos_centerness_targets).sum() /
-                        pos_centerness_targets.sum())[None]
-            loss_centerness = F.binary_cross_entropy_with_logits(
-                pos_centerness, pos_centerness_targets, reduction='mean')[None]
-            pos_iou_target = bbox_overlaps(pos_decoded_target_preds, pos_decoded_bbox_preds,
-                                           is_aligned=True)
-            loss_iou = F.binary_cross_entropy_with_logits(pos_iou, pos_iou_target,
-                                                          reduction='mean')[None]
-        else:
-            loss_reg = pos_bbox_preds.sum()[None]
-            loss_centerness = pos_centerness.sum()[None]
-            loss_iou = pos_iou.sum()[None]
-        return dict(loss_cls=loss_cls, loss_reg=loss_reg, loss_centerness=loss_centerness,
-                    loss_iou=loss_iou)
-
-    # ------------------------------------------------------------------ inference
     def get_bboxes_batched(self, cls_scores, bbox_preds, centernesses, ious, img_metas, cfg,
                            rescale=False):
         """Device-side result of the whole batch: dets (B,max,5), labels (B,max) int32,
         rows (B,max) int32, num (B) int32 -- no host synchronisation.  Centerness is not used
         (the reference has its use commented out, iou_aware_fcos_head.py:350-370)."""
-        if not len(cls_scores) == len(bbox_preds) == len(ious) == len(self.strides):
-            raise AssertionError('level count mismatch')
-        nms_cfg = dict(cfg.nms)
-        nms_type = nms_cfg.pop('type', 'nms')
-        if nms_type != 'nms':
-            raise NotImplementedError('IoUawareFCOSHead: test_cfg.nms.type %r (hard NMS only)'
-                                      % nms_type)
-        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
-        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
-        shapes = [m['img_shape'] for m in img_metas]
-        factors = [m['scale_factor'] for m in img_metas]
-        return fcos_ops.point_get_bboxes(geom, [c.detach() for c in cls_scores],
-                                         [b.detach() for b in bbox_preds],
-                                         [i.detach() for i in ious], shapes, factors, rescale,
-                                         cfg.score_thr, nms_cfg['iou_thr'], cfg.max_per_img)
+        return self._get_bboxes_batched(cls_scores, bbox_preds, ious, img_metas, cfg, rescale)
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels,
                    img_metas, cfg, rescale=None):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64)"""
-        dets, labels, _, num = self.get_bboxes_batched(cls_scores, bbox_preds, centernesses, ious,
-                                                       img_metas, cfg, rescale)
-        counts = num.tolist()
-        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
+        return per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, centernesses, ious,
+                                                  img_metas, cfg, rescale))
 
 
 @HEADS.register_module
@@ -273,85 +287,20 @@ class FCOSHead(_FCOSHeadBase):
     inference the raw class score is thresholded and NMS ranks sigmoid(cls) * sigmoid(centerness)
     (multiclass_nms with score_factors, bbox_nms.py:37-48)"""
 
-    def _init_layers(self):
-        self._init_towers()
-        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
-
-    def init_weights(self):
-        self._init_tower_weights()
-
-    def forward(self, feats):
-        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L])"""
-        return multi_apply(self.forward_single, feats, self.scales)
-
-    def forward_single(self, x, scale):
-        cls_feat = x
-        reg_feat = x
-        for cls_layer in self.cls_convs:
-            cls_feat = cls_layer(cls_feat)
-        cls_score = self.fcos_cls(cls_feat)
-        centerness = self.fcos_centerness(cls_feat)
-        for reg_layer in self.reg_convs:
-            reg_feat = reg_layer(reg_feat)
-        bbox_pred = scale(self.fcos_reg(reg_feat)).exp()
-        return cls_score, bbox_pred, centerness
-
-    # ------------------------------------------------------------------ training
     def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, cfg,
              gt_bboxes_ignore=None):
-        """the reference's three terms (fcos_head.py:105-191): focal classification over
-        (num_pos + num_imgs), the centerness-weighted IoU loss, the centerness BCE"""
-        if not len(cls_scores) == len(bbox_preds) == len(centernesses):
-            raise AssertionError('level count mismatch')
-        num_imgs, flat_cls, flat_bbox, flat_ctr, flat_labels, flat_bbox_targets, flat_points = \
-            self._flat_loss_inputs(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels)
-        pos_inds = flat_labels.nonzero().reshape(-1)
-        num_pos = len(pos_inds)
-        loss_cls = sigmoid_focal_loss(flat_cls.contiguous(), flat_labels, cfg.gamma, cfg.alpha,
-                                      'none').sum()[None] / (num_pos + num_imgs)
-        pos_bbox_preds = flat_bbox[pos_inds]
-        pos_bbox_targets = flat_bbox_targets[pos_inds]
-        pos_centerness = flat_ctr[pos_inds]
-        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
-        if num_pos > 0:
-            pos_points = flat_points[pos_inds]
-            pos_decoded_bbox_preds = distance2bbox(pos_points, pos_bbox_preds)
-            pos_decoded_target_preds = distance2bbox(pos_points, pos_bbox_targets)
-            loss_reg = ((iou_loss(pos_decoded_bbox_preds, pos_decoded_target_preds,
-                                  reduction='none') * pos_centerness_targets).sum() /
-                        pos_centerness_targets.sum())[None]
-            loss_centerness = F.binary_cross_entropy_with_logits(
-                pos_centerness, pos_centerness_targets, reduction='mean')[None]
-        else:
-            loss_reg = pos_bbox_preds.sum()[None]
-            loss_centerness = pos_centerness.sum()[None]
-        return dict(loss_cls=loss_cls, loss_reg=loss_reg, loss_centerness=loss_centerness)
+        """the reference's three terms (fcos_head.py:105-191)"""
+        return self._loss(cls_scores, bbox_preds, centernesses, None, gt_bboxes, gt_labels, cfg)
 
-    # ------------------------------------------------------------------ inference
     def get_bboxes_batched(self, cls_scores, bbox_preds, centernesses, img_metas, cfg,
                            rescale=False):
         """Device-side result of the whole batch: dets (B,max,5) (score = sigmoid(cls) *
         sigmoid(centerness)), labels (B,max) int32, rows (B,max) int32, num (B) int32 -- no host
         synchronisation."""
-        if not len(cls_scores) == len(bbox_preds) == len(centernesses) == len(self.strides):
-            raise AssertionError('level count mismatch')
-        nms_cfg = dict(cfg.nms)
-        nms_type = nms_cfg.pop('type', 'nms')
-        if nms_type != 'nms':
-            raise NotImplementedError('FCOSHead: test_cfg.nms.type %r (hard NMS only)' % nms_type)
-        featmap_sizes = [tuple(c.shape[-2:]) for c in cls_scores]
-        geom = self.geometry(featmap_sizes, cfg.get('nms_pre', -1))
-        shapes = [m['img_shape'] for m in img_metas]
-        factors = [m['scale_factor'] for m in img_metas]
-        return fcos_ops.point_ctr_get_bboxes(geom, [c.detach() for c in cls_scores],
-                                             [b.detach() for b in bbox_preds],
-                                             [c.detach() for c in centernesses], shapes, factors,
-                                             rescale, cfg.score_thr, nms_cfg['iou_thr'],
-                                             cfg.max_per_img)
+        return self._get_bboxes_batched(cls_scores, bbox_preds, centernesses, img_metas, cfg,
+                                        rescale)
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale=None):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64)"""
-        dets, labels, _, num = self.get_bboxes_batched(cls_scores, bbox_preds, centernesses,
-                                                       img_metas, cfg, rescale)
-        counts = num.tolist()
-        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
+        return per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, centernesses, img_metas,
+                                                  cfg, rescale))

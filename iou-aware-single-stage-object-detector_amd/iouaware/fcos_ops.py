@@ -4,15 +4,16 @@ centerness map in the third slot) and the towers' GroupNorm + ReLU.
 Device tensors only, launched on the current torch stream, like ops.py."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LevelPtrs, PointHeadGeom, WinoGeom
-from .ops import _meta_tensors, _ptr, _require_gpu, _state_workspace, _stream, stream_id, to_nchw
+from ._lib import LevelPtrs, PointHeadGeom
+from . import winograd
+from .ops import (_LayoutTwin, _det_outputs, _meta_tensors, _ptr, _require_gpu, _state_workspace,
+                  _stream, _ws_views, stream_id, to_nchw)
 
 
-class PointGeometry(object):
+class PointGeometry(_LayoutTwin):
     """Static geometry of a point head for one set of feature-map sizes (ia_point_head_geom)."""
 
     def __init__(self, featmap_sizes, strides, num_classes, nms_pre=-1, score_alpha=0.3):
@@ -38,15 +39,6 @@ class PointGeometry(object):
 
     def ref(self):
         return C.byref(self.struct)
-
-    def with_layout(self, layout):
-        if layout == self.layout:
-            return self
-        import copy
-        t = copy.copy(self)
-        t.struct = PointHeadGeom.from_buffer_copy(self.struct)
-        t.struct.layout = t.layout = layout
-        return t
 
 
 def _point_ptrs(geom, cls, reg, iou, third='iou_pred'):
@@ -84,18 +76,7 @@ def _workspace(geom, B, dev):
 
 
 def _views(geom, B, ws):
-    off = (C.c_size_t * 8)()
-    _lib.check(_lib.lib().ia_point_workspace_layout(geom.ref(), B, C.byref(off)),
-               'ia_point_workspace_layout')
-
-    def view(i, dtype, shape):
-        n = int(np.prod(shape))
-        return ws[off[i]:off[i] + n * 4].view(dtype).view(*shape)
-    return dict(rowmax=view(0, torch.float32, (B, geom.N)),
-                cand_idx=view(1, torch.int32, (B, geom.R)),
-                boxes=view(2, torch.float32, (B, geom.R, 4)),
-                scores_t=view(3, torch.float32, (B, geom.C, geom.Rs)),
-                best_score=view(6, torch.float32, (B, geom.R)))
+    return _ws_views('ia_point_workspace_layout', geom, B, ws)
 
 
 def point_decode_stage(geom, cls, reg, iou, img_shapes, scale_factors, rescale):
@@ -136,10 +117,7 @@ def _get_bboxes(entry, third, geom, cls, reg, iou, img_shapes, scale_factors, re
     dev = cls[0].device
     nbytes, ws = _workspace(geom, B, dev)
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
-    dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     _lib.check(getattr(_lib.lib(), entry)(
         geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf), int(bool(rescale)), float(score_thr),
         float(iou_thr), int(max_per_img), 0 if lazy else -1, _ptr(ws), nbytes, _ptr(dets),
@@ -168,11 +146,7 @@ def point_ctr_get_bboxes(geom, cls, reg, ctr, img_shapes, scale_factors, rescale
 
 
 def _wino_geom(xs):
-    g = WinoGeom()
-    g.num_levels, g.batch = len(xs), int(xs[0].shape[0])
-    for l, x in enumerate(xs):
-        g.H[l], g.W[l] = int(x.shape[2]), int(x.shape[3])
-    return g
+    return winograd._wino_geom([x.shape[2:] for x in xs], xs[0].shape[0])
 
 
 _gn_ws = {}

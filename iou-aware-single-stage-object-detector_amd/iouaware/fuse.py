@@ -29,6 +29,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 from . import ops, train_fuse
 from .backbones import BasicBlock, Bottleneck, ResNet
 from .layers import ConvModule, Scale
+from .winograd import plain_3x3
 
 # channels per 16-byte vector of the fused elementwise kernels
 _VEC = {torch.float32: 4, torch.bfloat16: 8}
@@ -455,9 +456,7 @@ def _bf16_head_ok(feats):
 
 
 def _wino_ok(conv):
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1)
-            and conv.groups == 1 and conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0)
+    return plain_3x3(conv) and conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0
 
 
 def _im2col_ok(conv):

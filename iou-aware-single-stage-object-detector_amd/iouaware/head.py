@@ -14,6 +14,11 @@ convolution happens:
   * loss: targets from torch (targets.py), losses from the HIP kernels on the
     NCHW tensors directly.
 There is no CPU fallback: get_bboxes / loss need tensors on a gfx950 device.
+
+The two heads are `_RetinaHeadBase` with the class attribute `iou_branch`: towers, decode
+(`_get_bboxes_batched`), targets and the front of loss() (`_loss`: up to and including the fused
+all-levels head loss) are written once; a head adds its output convolutions, the reference's
+public signatures and the per-level loss fallback (`_loss_levels`).
 """
 import numpy as np
 import torch
@@ -21,7 +26,7 @@ import torch.nn as nn
 
 from . import ops
 from .anchors import AnchorGenerator
-from .bbox import multi_apply
+from .bbox import multi_apply, per_image
 from .layers import ConvModule, bias_init_with_prob, normal_init
 from .registry import HEADS, build_loss
 from .targets import anchor_target
@@ -193,12 +198,6 @@ class _RetinaHeadBase(AnchorHead):
         return ops.get_bboxes(geom, cls_scores, bbox_preds, iou_preds, shapes, factors, rescale,
                               cfg.score_thr, iou_thr, cfg.max_per_img, soft=soft)
 
-    @staticmethod
-    def _per_image(dets, labels, rows, num):
-        """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64), k <= max_per_img"""
-        counts = num.tolist()                                   # the one host sync per batch
-        return [(dets[b, :k], labels[b, :k].to(torch.long)) for b, k in enumerate(counts)]
-
     # ------------------------------------------------------------------ training
     fuse_levels = True                    # all-levels loss kernels when the configuration allows
 
@@ -250,6 +249,38 @@ class _RetinaHeadBase(AnchorHead):
         num_total_samples = n_pos + n_neg if self.sampling else n_pos
         return labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, None
 
+    def _loss(self, cls_scores, bbox_preds, iou_preds, gt_bboxes, gt_labels, img_metas, cfg,
+              gt_bboxes_ignore):
+        """loss() of both heads (iou_preds None without the IoU branch): targets, then all levels
+        and all losses in one autograd node (csrc/headloss.hip: 3 + 2 kernel launches) when
+        `_fused_loss_ok`, else the subclass's per-level losses (`_loss_levels`: the other loss
+        types).  None when an image has no valid anchor."""
+        featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
+        if len(featmap_sizes) != len(self.anchor_generators):
+            raise AssertionError('level count mismatch')
+        if not self.iou_branch:
+            for t in list(cls_scores) + list(bbox_preds):
+                ops._require_gpu(t, 'head output')
+        geom = self.geometry(featmap_sizes, -1)
+        fused = self._fused_loss_ok(cls_scores)
+        targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
+                                gt_bboxes_ignore, cls_scores[0].device, counts_as_normaliser=fused)
+        if targets is None:
+            return None
+        labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts = targets
+        if not fused:
+            return self._loss_levels(geom, cls_scores, bbox_preds, iou_preds, labels, label_w,
+                                     bbox_t, bbox_w, level_anchors, num_total_samples, gt_bboxes,
+                                     cfg)
+        on_dev = level_anchors[0] is None          # targets came from the HIP assigner
+        return ops.head_loss(
+            geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
+            counts=counts if on_dev else None,
+            avg_factor=None if on_dev else num_total_samples,
+            gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
+            loss_weight_cls=self.loss_cls.loss_weight, beta=self.loss_bbox.beta,
+            loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=self.attach_iou_target)
+
 
 @HEADS.register_module
 class IoUawareRetinaHead(_RetinaHeadBase):
@@ -296,8 +327,8 @@ class IoUawareRetinaHead(_RetinaHeadBase):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64), k <= max_per_img.
         gt_bboxes / gt_labels are accepted positionally like the fork's signature (:390-398);
         they only feed dead code there (:517-524) and are unused."""
-        return self._per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, iou_preds,
-                                                        img_metas, cfg, rescale))
+        return per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, iou_preds, img_metas,
+                                                  cfg, rescale))
 
     # ------------------------------------------------------------------ training
     def loss_single(self, cls_score, bbox_pred, iou_pred, labels, label_weights, bbox_targets,
@@ -332,38 +363,20 @@ class IoUawareRetinaHead(_RetinaHeadBase):
                                                    self.num_anchors, num_total_samples)
         return loss_cls, loss_bbox, loss_iou
 
-
     def loss(self, cls_scores, bbox_preds, iou_preds, gt_bboxes, gt_labels, img_metas, cfg,
              gt_bboxes_ignore=None):
         """-> dict(loss_cls, loss_bbox, losses_iou), each a list of per-level (1,) tensors, or
         None when an image has no valid anchor (reference :315-387; the key really is
         'losses_iou', :387)."""
-        featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
-        if len(featmap_sizes) != len(self.anchor_generators):
-            raise AssertionError('level count mismatch')
-        geom = self.geometry(featmap_sizes, -1)
-        fused = self._fused_loss_ok(cls_scores)
-        targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
-                                gt_bboxes_ignore, cls_scores[0].device, counts_as_normaliser=fused)
-        if targets is None:
-            return None
-        labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts = targets
-        if fused:
-            # all levels, all three losses: one autograd node, 3 + 2 kernel launches
-            # (csrc/headloss.hip); the per-level path below stays for the other loss types
-            on_dev = level_anchors[0] is None          # targets came from the HIP assigner
-            return ops.head_loss(
-                geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
-                counts=counts if on_dev else None,
-                avg_factor=None if on_dev else num_total_samples,
-                gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
-                loss_weight_cls=self.loss_cls.loss_weight, beta=self.loss_bbox.beta,
-                loss_weight_bbox=self.loss_bbox.loss_weight,
-                attach_iou_target=self.attach_iou_target)
+        return self._loss(cls_scores, bbox_preds, iou_preds, gt_bboxes, gt_labels, img_metas, cfg,
+                          gt_bboxes_ignore)
+
+    def _loss_levels(self, geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
+                     level_anchors, num_total_samples, gt_bboxes, cfg):
         out = [self.loss_single(cls_scores[l], bbox_preds[l], iou_preds[l], labels[l], label_w[l],
                                 bbox_t[l], bbox_w[l], level_anchors[l], num_total_samples,
                                 gt_bboxes, cfg, level=l, geom=geom)
-               for l in range(len(featmap_sizes))]
+               for l in range(geom.L)]
         losses_cls, losses_bbox, losses_iou = map(list, zip(*out))
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, losses_iou=losses_iou)
 
@@ -376,6 +389,7 @@ class RetinaHead(_RetinaHeadBase):
     IoU-aware head with the IA_CLS_*_NOIOU score kind (anchor_head.py:364-450)."""
 
     iou_branch = False
+    attach_iou_target = False             # no IoU map to attach a target to (head_loss's cfg)
 
     def __init__(self, num_classes, in_channels, stacked_convs=4, octave_base_scale=4,
                  scales_per_octave=3, conv_cfg=None, norm_cfg=None, **kwargs):
@@ -401,8 +415,7 @@ class RetinaHead(_RetinaHeadBase):
                    rescale=False):
         """-> list over images of (det_bboxes (k,5) fp32, det_labels (k,) int64).  The fork's
         signature (anchor_head.py:301-308): gt_bboxes / gt_labels are positional and unused."""
-        return self._per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg,
-                                                        rescale))
+        return per_image(*self.get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale))
 
     # ------------------------------------------------------------------ training
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, cfg,
@@ -416,29 +429,13 @@ class RetinaHead(_RetinaHeadBase):
             if type(lo).__name__ in ('IOUbalancedSigmoidFocalLoss', 'IoUbalancedSmoothL1Loss'):
                 raise NotImplementedError('%s on RetinaHead needs an IoU target without an IoU '
                                           'map; not supported' % type(lo).__name__)
-        featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
-        if len(featmap_sizes) != len(self.anchor_generators):
-            raise AssertionError('level count mismatch')
-        for t in list(cls_scores) + list(bbox_preds):
-            ops._require_gpu(t, 'head output')
-        geom = self.geometry(featmap_sizes, -1)
-        fused = self._fused_loss_ok(cls_scores)
-        targets = self._targets(featmap_sizes, geom, gt_bboxes, gt_labels, img_metas, cfg,
-                                gt_bboxes_ignore, cls_scores[0].device, counts_as_normaliser=fused)
-        if targets is None:
-            return None
-        labels, label_w, bbox_t, bbox_w, level_anchors, num_total_samples, counts = targets
-        if fused:
-            on_dev = level_anchors[0] is None          # targets came from the HIP assigner
-            return ops.head_loss(
-                geom, cls_scores, bbox_preds, None, labels, label_w, bbox_t, bbox_w,
-                counts=counts if on_dev else None,
-                avg_factor=None if on_dev else num_total_samples,
-                gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
-                loss_weight_cls=self.loss_cls.loss_weight, beta=self.loss_bbox.beta,
-                loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=False)
+        return self._loss(cls_scores, bbox_preds, None, gt_bboxes, gt_labels, img_metas, cfg,
+                          gt_bboxes_ignore)
+
+    def _loss_levels(self, geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
+                     level_anchors, num_total_samples, gt_bboxes, cfg):
         losses_cls, losses_bbox = [], []
-        for l in range(len(featmap_sizes)):
+        for l in range(geom.L):
             B, n_l = cls_scores[l].shape[0], geom.level_anchors[l]
             losses_cls.append(self.loss_cls.forward_level(
                 cls_scores[l], labels[l].reshape(B, n_l), label_w[l].reshape(B, n_l),

@@ -52,7 +52,25 @@ def _require_gpu(t, name):
             'fallback' % (name, t.device))
 
 
-class HeadGeometry(object):
+class _LayoutTwin(object):
+    """with_layout of the geometry classes (HeadGeometry, fcos_ops.PointGeometry: `struct` with a
+    `layout` field, `layout`)"""
+    _twin = None
+
+    def with_layout(self, layout):
+        """the same geometry for head outputs stored in the other memory order (made once)"""
+        if layout == self.layout:
+            return self
+        if self._twin is None:
+            import copy
+            t = copy.copy(self)
+            t.struct = type(self.struct).from_buffer_copy(self.struct)
+            t.struct.layout = t.layout = layout
+            t._twin, self._twin = self, t
+        return self._twin
+
+
+class HeadGeometry(_LayoutTwin):
     """Static geometry of an anchor head for one set of feature-map sizes
     (fills the C struct ia_head_geom)."""
 
@@ -96,26 +114,12 @@ class HeadGeometry(object):
         self.level_anchors = [h * w * A for (h, w) in self.featmap_sizes]
         self.level_cands = [min(nms_pre, n_) if nms_pre > 0 else n_ for n_ in self.level_anchors]
         self.layout = _lib.IA_LAYOUT_NCHW
-        self._twin = None
         # what the workspace carve-up depends on (besides batch, layout and dtype)
         self.key = (tuple(self.featmap_sizes), A, int(num_classes), int(nms_pre), bool(softmax),
                     bool(iou_branch))
 
     def ref(self):
         return C.byref(self.struct)
-
-    def with_layout(self, layout):
-        """the same geometry for head outputs stored in the other memory order"""
-        if layout == self.layout:
-            return self
-        if self._twin is None:
-            import copy
-            t = copy.copy(self)
-            t.struct = HeadGeom.from_buffer_copy(self.struct)
-            t.struct.layout = layout
-            t.layout, t._twin = layout, self
-            self._twin = t
-        return self._twin
 
 
 def to_nchw(t):
@@ -288,6 +292,37 @@ def _meta_tensors(img_shapes, scale_factors, device):
     return hit
 
 
+def _det_outputs(B, max_per_img, dev, fill=False):
+    """-> dets (B,max,5) f32, labels (B,max) i32, rows (B,max) i32, num (B) i32, uninitialised;
+    fill=True for a caller that leaves rows unwritten: dets / num 0, labels / rows -1"""
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    if fill:
+        return (torch.zeros((B, max_per_img, 5), **f32), torch.full((B, max_per_img), -1, **i32),
+                torch.full((B, max_per_img), -1, **i32), torch.zeros((B,), **i32))
+    return (torch.empty((B, max_per_img, 5), **f32), torch.empty((B, max_per_img), **i32),
+            torch.empty((B, max_per_img), **i32), torch.empty((B,), **i32))
+
+
+_STAGE_VIEWS = ('rowmax', 'cand_idx', 'boxes', 'scores_t', 'best_score')
+
+
+def _ws_views(layout_entry, geom, B, ws, names=_STAGE_VIEWS):
+    """dict of views into the workspace `ws` of a post-conv entry, carved up as `layout_entry`
+    (ia_get_bboxes_workspace_layout / ia_point_workspace_layout) says"""
+    off = (C.c_size_t * 8)()
+    _lib.check(getattr(_lib.lib(), layout_entry)(geom.ref(), B, C.byref(off)), layout_entry)
+    f32, i32 = torch.float32, torch.int32
+    slots = dict(rowmax=(0, f32, (B, geom.N)), cand_idx=(1, i32, (B, geom.R)),
+                 boxes=(2, f32, (B, geom.R, 4)), scores_t=(3, f32, (B, geom.C, geom.Rs)),
+                 keep_count=(4, i32, (B, geom.C)), keep_rows=(5, i32, (B, geom.C, geom.Rs)),
+                 best_score=(6, f32, (B, geom.R)))
+    out = {}
+    for name in names:
+        i, dtype, shape = slots[name]
+        out[name] = ws[off[i]:off[i] + int(np.prod(shape)) * 4].view(dtype).view(*shape)
+    return out
+
+
 def get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_thr, iou_thr,
                max_per_img, debug=False, soft=None, lazy=True, lazy_candidates=0):
     """Whole post-conv inference path for a batch.
@@ -330,10 +365,7 @@ def get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_th
         raise _lib.IouAwareLibraryError('unsupported geometry / batch for ia_get_bboxes')
     ws = _state_workspace(dev, nbytes, (geom.key, geom.layout, B, dt))
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
-    dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     if lazy and not debug:
         rc = L.ia_get_bboxes_lazy(geom.ref(), C.byref(p), B, dt, _ptr(hw), _ptr(sf),
                                   int(bool(rescale)), float(score_thr), float(iou_thr),
@@ -346,19 +378,9 @@ def get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_th
     _lib.check(rc, 'ia_get_bboxes')
     if not debug:
         return dets, labels, rows, num
-    off = (C.c_size_t * 8)()
-    _lib.check(L.ia_get_bboxes_workspace_layout(geom.ref(), B, C.byref(off)), 'workspace_layout')
-
-    def view(i, dtype, shape):
-        n = int(np.prod(shape))
-        return ws[off[i]:off[i] + n * 4].view(dtype).view(*shape)
-    dbg = dict(rowmax=view(0, torch.float32, (B, geom.N)),
-               cand_idx=view(1, torch.int32, (B, geom.R)),
-               boxes=view(2, torch.float32, (B, geom.R, 4)),
-               scores_t=view(3, torch.float32, (B, geom.C, geom.Rs)),
-               keep_count=view(4, torch.int32, (B, geom.C)),
-               keep_rows=view(5, torch.int32, (B, geom.C, geom.Rs)),
-               fused_fallbacks=torch.tensor(get_bboxes_status(geom, B, ws)[1]))
+    dbg = _ws_views('ia_get_bboxes_workspace_layout', geom, B, ws,
+                    ('rowmax', 'cand_idx', 'boxes', 'scores_t', 'keep_count', 'keep_rows'))
+    dbg['fused_fallbacks'] = torch.tensor(get_bboxes_status(geom, B, ws)[1])
     return dets, labels, rows, num, dbg
 
 
@@ -380,10 +402,7 @@ def _get_bboxes_per_class(geom, cls, reg, iou, img_shapes, scale_factors, rescal
     cand = select_topk(geom, rowmax)
     boxes, scores_t, _ = gather_decode(geom, cls, reg, iou, cand, img_shapes, scale_factors, rescale)
     B, R, Cn, dev = boxes.shape[0], geom.R, geom.C, boxes.device
-    dets = torch.zeros((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.full((B, max_per_img), -1, dtype=torch.int32, device=dev)
-    rows = torch.full((B, max_per_img), -1, dtype=torch.int32, device=dev)
-    num = torch.zeros((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev, fill=True)
     kc = torch.zeros((B, Cn), dtype=torch.int32, device=dev)
     kr = torch.zeros((B, Cn, geom.Rs), dtype=torch.int32, device=dev) if debug else None
     for b in range(B):
@@ -442,18 +461,7 @@ class DecodeStage(object):
                    'ia_decode_stage')
 
     def views(self):
-        off = (C.c_size_t * 8)()
-        _lib.check(_lib.lib().ia_get_bboxes_workspace_layout(self.geom.ref(), self.B, C.byref(off)),
-                   'workspace_layout')
-        g, B = self.geom, self.B
-
-        def view(i, dtype, shape):
-            n = int(np.prod(shape))
-            return self.ws[off[i]:off[i] + n * 4].view(dtype).view(*shape)
-        return dict(rowmax=view(0, torch.float32, (B, g.N)), cand_idx=view(1, torch.int32, (B, g.R)),
-                    boxes=view(2, torch.float32, (B, g.R, 4)),
-                    scores_t=view(3, torch.float32, (B, g.C, g.Rs)),
-                    best_score=view(6, torch.float32, (B, g.R)))
+        return _ws_views('ia_get_bboxes_workspace_layout', self.geom, self.B, self.ws)
 
 
 # ----------------------------------------------------------------- stage wrappers
@@ -522,10 +530,7 @@ def multiclass_nms(boxes, scores_t, R, score_thr, iou_thr, max_per_img, best_sco
     _require_gpu(boxes, 'boxes')
     B, Cn, Rs = scores_t.shape
     dev = boxes.device
-    dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     kc = torch.empty((B, Cn), dtype=torch.int32, device=dev)
     kr = torch.empty((B, Cn, Rs), dtype=torch.int32, device=dev)
     nbytes = _lib.lib().ia_multiclass_nms_workspace_bytes(B, int(R), Cn)
@@ -544,10 +549,7 @@ def multiclass_nms_lazy(boxes, scores_t, R, score_thr, iou_thr, max_per_img, bes
     _require_gpu(boxes, 'boxes')
     B, Cn, Rs = scores_t.shape
     dev = boxes.device
-    dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     nbytes = _lib.lib().ia_multiclass_nms_lazy_workspace_bytes(B, int(R), Cn)
     ws = _workspace(dev, nbytes)
     _lib.check(_lib.lib().ia_multiclass_nms_lazy(
@@ -573,10 +575,7 @@ def multiclass_soft_nms(boxes, scores_t, R, score_thr, iou_thr, max_per_img, met
     _require_gpu(boxes, 'boxes')
     B, Cn, Rs = scores_t.shape
     dev = boxes.device
-    dets = torch.empty((B, max_per_img, 5), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, max_per_img), dtype=torch.int32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     kc = torch.empty((B, Cn), dtype=torch.int32, device=dev)
     kr = torch.empty((B, Cn, Rs), dtype=torch.int32, device=dev)
     nbytes = _lib.lib().ia_multiclass_soft_nms_workspace_bytes(B, int(R), Cn)
@@ -1461,6 +1460,37 @@ def _zero1(dev):
     return z
 
 
+def _pack_head_targets(targets, L):
+    """(labels[L], label_w[L], bbox_t[L], bbox_w[L], counts, avg) -> (ia_head_targets, kept).
+    The struct holds bare device pointers: `kept` are the tensors behind them (the contiguous
+    copies, counts, the device normaliser), and a node whose backward passes the struct again must
+    reference both from its ctx until then."""
+    labels, lw, bt, bw, counts, avg = targets
+    labels = [t.contiguous().to(torch.int64) for t in labels]
+    lw = [t.contiguous().to(torch.float32) for t in lw]
+    bt = [t.contiguous().to(torch.float32) for t in bt]
+    bw = [t.contiguous().to(torch.float32) for t in bw]
+    ht = _lib.HeadTargets()
+    for l in range(L):
+        ht.labels[l], ht.label_weights[l] = labels[l].data_ptr(), lw[l].data_ptr()
+        ht.bbox_targets[l], ht.bbox_weights[l] = bt[l].data_ptr(), bw[l].data_ptr()
+    avg_dev = None
+    if counts is not None:
+        ht.counts = counts.data_ptr()
+    elif torch.is_tensor(avg):
+        avg_dev = avg.detach().reshape(-1)[:1].to(torch.float32).contiguous()
+        ht.avg_factor_dev = avg_dev.data_ptr()
+    else:
+        ht.avg_factor = float(avg)
+    return ht, (labels, lw, bt, bw, counts, avg_dev)
+
+
+def _head_loss_gin(gs, dev):
+    """the 3L + 3 incoming gradients of a head-loss node as one device vector (None -> 0)"""
+    z = _zero1(dev)
+    return torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
+
+
 class _HeadLossFn(torch.autograd.Function):
     """the three losses of every level: 3 launches forward, 2 backward (csrc/headloss.hip).
     Outputs: 3L per-level (1,) tensors and 3 totals, views of one result vector.  A geometry without
@@ -1483,23 +1513,7 @@ class _HeadLossFn(torch.autograd.Function):
         for l in range(L):
             p.cls[l], p.reg[l] = cls[l].data_ptr(), reg[l].data_ptr()
             p.iou[l] = iou[l].data_ptr() if iou else None
-        labels, lw, bt, bw, counts, avg = targets
-        labels = [t.contiguous().to(torch.int64) for t in labels]
-        lw = [t.contiguous().to(torch.float32) for t in lw]
-        bt = [t.contiguous().to(torch.float32) for t in bt]
-        bw = [t.contiguous().to(torch.float32) for t in bw]
-        ht = _lib.HeadTargets()
-        for l in range(L):
-            ht.labels[l], ht.label_weights[l] = labels[l].data_ptr(), lw[l].data_ptr()
-            ht.bbox_targets[l], ht.bbox_weights[l] = bt[l].data_ptr(), bw[l].data_ptr()
-        avg_dev = None
-        if counts is not None:
-            ht.counts = counts.data_ptr()
-        elif torch.is_tensor(avg):
-            avg_dev = avg.detach().reshape(-1)[:1].to(torch.float32).contiguous()
-            ht.avg_factor_dev = avg_dev.data_ptr()
-        else:
-            ht.avg_factor = float(avg)
+        ht, kept = _pack_head_targets(targets, L)
         hc = _lib.HeadLossCfg(*cfg)
         res = torch.empty(3 * L + 4, dtype=torch.float32, device=dev)
         g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
@@ -1514,17 +1528,16 @@ class _HeadLossFn(torch.autograd.Function):
                                                _stream()), 'ia_head_loss_fwd')
         ctx.ws = ws
         ctx.geom, ctx.cfg, ctx.B, ctx.dt = g, hc, B, dt
-        ctx.keep = (cls, reg, iou, labels, lw, bt, bw, counts, avg_dev, p, ht)
+        ctx.keep = (cls, reg, iou, p, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
         return tuple(res[:3 * L + 3].view(3 * L + 3, 1).unbind(0))
 
     @staticmethod
     def backward(ctx, *gs):
-        cls, reg, iou, labels, lw, bt, bw, counts, avg_dev, p, ht = ctx.keep
+        cls, reg, iou, p, ht, _ = ctx.keep
         L, dev = ctx.geom.L, cls[0].device
-        z = _zero1(dev)
-        gin = torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
+        gin = _head_loss_gin(gs, dev)
         gp = LevelPtrs()
         grads = [[torch.empty(t.shape, dtype=torch.float32, device=dev) for t in x]
                  for x in (cls, reg, iou)]
@@ -1610,23 +1623,7 @@ class _HeadLossNhwcFn(torch.autograd.Function):
             st.cls[l], st.reg[l] = _pix_stride(cls[l]), _pix_stride(reg[l])
             if iou is not None:
                 p.iou[l], st.iou[l] = iou[l].data_ptr(), _pix_stride(iou[l])
-        labels, lw, bt, bw, counts, avg = targets
-        labels = [t.contiguous().to(torch.int64) for t in labels]
-        lw = [t.contiguous().to(torch.float32) for t in lw]
-        bt = [t.contiguous().to(torch.float32) for t in bt]
-        bw = [t.contiguous().to(torch.float32) for t in bw]
-        ht = _lib.HeadTargets()
-        for l in range(L):
-            ht.labels[l], ht.label_weights[l] = labels[l].data_ptr(), lw[l].data_ptr()
-            ht.bbox_targets[l], ht.bbox_weights[l] = bt[l].data_ptr(), bw[l].data_ptr()
-        avg_dev = None
-        if counts is not None:
-            ht.counts = counts.data_ptr()
-        elif torch.is_tensor(avg):
-            avg_dev = avg.detach().reshape(-1)[:1].to(torch.float32).contiguous()
-            ht.avg_factor_dev = avg_dev.data_ptr()
-        else:
-            ht.avg_factor = float(avg)
+        ht, kept = _pack_head_targets(targets, L)
         hc = _lib.HeadLossCfg(*cfg)
         res = torch.empty(3 * L + 4, dtype=torch.float32, device=dev)
         nbytes = 8 * 3 * L * _lib.IA_LOSS_SLOTS
@@ -1635,17 +1632,16 @@ class _HeadLossNhwcFn(torch.autograd.Function):
                                                     C.byref(ht), C.byref(hc), _ptr(ws), nbytes,
                                                     _ptr(res), _stream()), 'ia_head_loss_fwd_nhwc')
         ctx.geom, ctx.cfg, ctx.B, ctx.fused = geom, hc, B, fused
-        ctx.keep = (cls, reg, iou, bases, labels, lw, bt, bw, counts, avg_dev, p, st, ht)
+        ctx.keep = (cls, reg, iou, bases, p, st, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
         return tuple(res[:3 * L + 3].view(3 * L + 3, 1).unbind(0))
 
     @staticmethod
     def backward(ctx, *gs):
-        cls, reg, iou, bases, labels, lw, bt, bw, counts, avg_dev, p, st, ht = ctx.keep
+        cls, reg, iou, bases, p, st, ht, _ = ctx.keep
         L, dev = ctx.geom.L, cls[0].device
-        z = _zero1(dev)
-        gin = torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
+        gin = _head_loss_gin(gs, dev)
         gp, gst = LevelPtrs(), _lib.LevelPixStrides()
         cl = torch.channels_last
         g_cls = [torch.empty(t.shape, dtype=torch.float32, device=dev, memory_format=cl) for t in cls]

@@ -9,7 +9,10 @@ retina_reg, retina_iou) and of the FPN output convolutions (fpn.py:124-127).
 The head's weights are shared by the pyramid levels, so every layer is ONE batched GEMM over the
 tiles of all levels; the two towers run side by side (first layer: one GEMM with 512 output
 columns on the shared input, later layers: 72 matrices).  36 multiplications per 4x4 output tile
-instead of 144: these convolutions are 63 % of the network's multiply-adds.
+instead of 144: these convolutions are 63 % of the network's multiply-adds.  That tower program is
+`_WinogradTowers`; `WinogradHead` (RetinaNet: bias + ReLU inside the output transform) and
+`WinogradFCOSHead` (FCOS: GroupNorm + ReLU behind it) add the layer epilogue and their output
+convolutions.
 
 Numerics: fp32 throughout; the Winograd transforms reassociate the sums, outputs agree with a
 direct convolution to ~1e-5 of the activation scale (tests/test_gpu_winograd.py).  The weights are
@@ -44,13 +47,18 @@ def transform_weight(w):
 
 
 def _wino_geom(sizes, batch):
+    """ia_wino_geom of per-level (H, W) feature maps (also the GroupNorm kernels' geometry)"""
     g = _lib.WinoGeom()
     g.num_levels, g.batch = len(sizes), int(batch)
     for l, (h, w) in enumerate(sizes):
         g.H[l], g.W[l] = int(h), int(w)
+    return g
+
+
+def _wino_tiles(g):
     tiles = C.c_int32()
     _lib.check(_lib.lib().ia_wino_tiles(C.byref(g), C.byref(tiles)), 'ia_wino_tiles')
-    return g, tiles.value
+    return tiles.value
 
 
 def _usable(x):
@@ -97,7 +105,8 @@ class _Plan(object):
 
     def __init__(self, sizes, batch, device):
         self.sizes, self.batch = list(sizes), batch
-        self.geom, self.T = _wino_geom(sizes, batch)
+        self.geom = _wino_geom(sizes, batch)
+        self.T = _wino_tiles(self.geom)
         self.device = device
         self._bufs = {}
 
@@ -223,97 +232,132 @@ class WinogradConv3x3(object):
         return y
 
 
-class WinogradHead(object):
-    """the conv towers and output convolutions of an IoUawareRetinaHead, all levels at once."""
+def plain_3x3(conv):
+    """3x3 / stride 1 / pad 1 / dilation 1 / groups 1: what F(4x4,3x3) computes.  The callers
+    conjoin what else their route needs (channel multiples, bias, module type, padding mode)."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1)
+
+
+def _pair(a, b, F, granule):
+    """one or two output convolutions on one tower: (U (36, F, n_pad), bias (n_pad,), n_a, n_b);
+    b None: n_b = 0.  n_pad = n_a + n_b rounded up to `granule`: the caller's, because N selects
+    the GEMM kernel from the committed table."""
+    na, nb = a.out_channels, (0 if b is None else b.out_channels)
+    n_pad = (na + nb + granule - 1) // granule * granule
+    dev = a.weight.device
+    u = torch.zeros((36, F, n_pad), dtype=torch.float32, device=dev)
+    u[:, :, :na] = transform_weight(a.weight)
+    bias = torch.zeros(n_pad, dtype=torch.float32, device=dev)
+    bias[:na] = a.bias.detach().float()
+    if b is not None:
+        u[:, :, na:na + nb] = transform_weight(b.weight)
+        bias[na:na + nb] = b.bias.detach().float()
+    return u.contiguous(), bias.contiguous(), na, nb
+
+
+class _WinogradTowers(object):
+    """the two conv towers of a head, all levels at once: layer 0 one GEMM with 2F output columns
+    on the shared input, layers 1..n-1 72 matrices (cls tower = channels [0,F), reg tower =
+    [F,2F)), activations ping-pong between the plan's 'a' / 'b' sets.  A subclass supplies the
+    layer epilogue (`_layer_out`) and the output convolutions behind `_towers`."""
 
     def __init__(self, head):
         convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
-        if any(m.with_norm or not m.with_activatation for m in convs_c + convs_r):
-            raise NotImplementedError('towers with norm layers / without ReLU')
         self.n_layers = len(convs_c)
         F = head.feat_channels
         if head.in_channels % 4 or F % 4:
             raise ValueError('channel counts must be multiples of 4')
         self.F, self.cin = F, head.in_channels
-
-        def wb(m):
-            conv = m.conv
-            b = conv.bias if conv.bias is not None else torch.zeros(conv.out_channels,
-                                                                     device=conv.weight.device)
-            return transform_weight(conv.weight), b.detach().float()
-
-        # layer 0: both towers read the FPN feature -> one GEMM with 2F output columns
-        (uc, bc), (ur, br) = wb(convs_c[0]), wb(convs_r[0])
-        self.u0 = torch.cat([uc, ur], dim=2).contiguous()               # (36, Cin, 2F)
-        self.b0 = torch.cat([bc, br]).contiguous()
-        # layers 1..: two groups side by side -> 72 matrices
-        self.u, self.b = [], []
-        for i in range(1, self.n_layers):
-            (uc, bc), (ur, br) = wb(convs_c[i]), wb(convs_r[i])
-            self.u.append(torch.cat([uc, ur], dim=0).contiguous())       # (72, F, F)
-            self.b.append(torch.cat([bc, br]).contiguous())
-        # outputs: retina_cls on the cls tower; retina_reg | retina_iou on the reg tower
-        self.c_cls = head.retina_cls.out_channels
-        self.c_reg, self.c_iou = head.retina_reg.out_channels, head.retina_iou.out_channels
-        if self.c_cls % 4:
-            raise ValueError('A*C must be a multiple of 4')
-        self.u_cls = transform_weight(head.retina_cls.weight)
-        self.b_cls = head.retina_cls.bias.detach().float().contiguous()
-        n_ri = self.c_reg + self.c_iou
-        self.n_ri_pad = (n_ri + 15) // 16 * 16
-        u_ri = torch.zeros((36, F, self.n_ri_pad), dtype=torch.float32, device=self.u_cls.device)
-        u_ri[:, :, :self.c_reg] = transform_weight(head.retina_reg.weight)
-        u_ri[:, :, self.c_reg:n_ri] = transform_weight(head.retina_iou.weight)
-        self.u_ri = u_ri.contiguous()
-        b_ri = torch.zeros(self.n_ri_pad, dtype=torch.float32, device=self.u_cls.device)
-        b_ri[:self.c_reg] = head.retina_reg.bias.detach().float()
-        b_ri[self.c_reg:n_ri] = head.retina_iou.bias.detach().float()
-        self.b_ri = b_ri.contiguous()
+        self.u0 = torch.cat([transform_weight(convs_c[0].conv.weight),
+                             transform_weight(convs_r[0].conv.weight)], dim=2).contiguous()  # (36, Cin, 2F)
+        self.u = [torch.cat([transform_weight(convs_c[i].conv.weight),
+                             transform_weight(convs_r[i].conv.weight)], dim=0).contiguous()  # (72, F, F)
+                  for i in range(1, self.n_layers)]
         self._plans = collections.OrderedDict()
 
     def usable(self, feats):
         return all(_usable(x) and x.shape[1] == self.cin for x in feats) \
             and not torch.is_grad_enabled()
 
-    def __call__(self, feats):
-        """feats: per-level (B, Cin, H, W) channels-last fp32 -> (cls[L], reg[L], iou[L])"""
-        B = feats[0].shape[0]
+    def _towers(self, feats):
+        """-> (plan, V of the towers' last activations (72, T, F): [:36] cls, [36:] reg, new);
+        new(c): per-level channels-last (B, c, H, W) output tensors"""
+        B, dev = feats[0].shape[0], feats[0].device
         sizes = [tuple(x.shape[-2:]) for x in feats]
-        key = (B, tuple(sizes), feats[0].device, stream_id())
-        plan = _plan_for(self._plans, key, lambda: _Plan(sizes, B, feats[0].device))
+        key = (B, tuple(sizes), dev, stream_id())
+        plan = _plan_for(self._plans, key, lambda: _Plan(sizes, B, dev))
         T, F = plan.T, self.F
         # layer 0
         v = input_transform(plan, feats, 1, plan.buf('v', (36, T, self.cin)))
         m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)))
         acts = plan.acts('a', 2 * F)
-        output_transform(plan, m, 2 * F, 1, self.b0, True, [(0, 2 * F, acts, 0)])
-        # layers 1..n-1: groups = 2 (cls tower = channels [0,F), reg tower = [F,2F))
-        for u, b in zip(self.u, self.b):
+        self._layer_out(plan, m, 1, 0, acts)
+        # layers 1..n-1: groups = 2
+        for i, u in enumerate(self.u):
             v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
             m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
             nxt = plan.acts('b' if acts is plan.acts('a', 2 * F) else 'a', 2 * F)
-            output_transform(plan, m, 2 * F, 2, b, True, [(0, 2 * F, nxt, 0)])
+            self._layer_out(plan, m, 2, i + 1, nxt)
             acts = nxt
-        # outputs
         v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
-        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=feats[0].device,  # noqa: E731
+        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=dev,  # noqa: E731
                                      memory_format=torch.channels_last) for (h, w) in sizes]
+        return plan, v, new
+
+    @staticmethod
+    def _out_conv(plan, v, name, u, bias, segments):
+        """one tower's output convolutions: a GEMM with u.shape[2] columns, scattered to `segments`"""
+        n = u.shape[2]
+        m = batched_gemm(v, u, plan.buf(name, (36, plan.T, n)))
+        output_transform(plan, m, n, 1, bias, False, segments)
+
+
+class WinogradHead(_WinogradTowers):
+    """the conv towers (bias + ReLU inside the output transform) and output convolutions of an
+    IoUawareRetinaHead: retina_cls on the cls tower, retina_reg | retina_iou on the reg tower."""
+
+    def __init__(self, head):
+        convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
+        if any(m.with_norm or not m.with_activatation for m in convs_c + convs_r):
+            raise NotImplementedError('towers with norm layers / without ReLU')
+        super(WinogradHead, self).__init__(head)
+
+        def bias(m):
+            conv = m.conv
+            b = conv.bias if conv.bias is not None else torch.zeros(conv.out_channels,
+                                                                     device=conv.weight.device)
+            return b.detach().float()
+
+        # per layer: the two towers' biases side by side (2F,)
+        self.b = [torch.cat([bias(mc), bias(mr)]).contiguous() for mc, mr in zip(convs_c, convs_r)]
+        if head.retina_cls.out_channels % 4:
+            raise ValueError('A*C must be a multiple of 4')
+        # retina_cls goes in unpadded, reg | iou padded to 16 columns
+        self.u_cls, self.b_cls, self.c_cls, _ = _pair(head.retina_cls, None, self.F, 1)
+        self.u_ri, self.b_ri, self.c_reg, self.c_iou = _pair(head.retina_reg, head.retina_iou,
+                                                             self.F, 16)
+
+    def _layer_out(self, plan, m, groups, i, acts):
+        output_transform(plan, m, 2 * self.F, groups, self.b[i], True, [(0, 2 * self.F, acts, 0)])
+
+    def __call__(self, feats):
+        """feats: per-level (B, Cin, H, W) channels-last fp32 -> (cls[L], reg[L], iou[L])"""
+        plan, v, new = self._towers(feats)
         cls, reg, iou = new(self.c_cls), new(self.c_reg), new(self.c_iou)
         # the 548 MB class logits are written FIRST: the (MFMA-bound) reg / iou GEMM behind them
         # gives their write-back time to drain before the row-max kernel streams them back in
         # (round 6, measured again in bench steps, 2 x 20 steps each: class logits LAST -> decode stage 0.133 ms
         # in-step against 0.120-0.121 this way; gpurun_out/r06_ab_clslast.txt)
-        m_cls = batched_gemm(v[:36], self.u_cls, plan.buf('mc', (36, T, self.c_cls)))
-        output_transform(plan, m_cls, self.c_cls, 1, self.b_cls, False, [(0, self.c_cls, cls, 0)])
-        m_ri = batched_gemm(v[36:], self.u_ri, plan.buf('mr', (36, T, self.n_ri_pad)))
-        output_transform(plan, m_ri, self.n_ri_pad, 1, self.b_ri, False,
-                         [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
+        self._out_conv(plan, v[:36], 'mc', self.u_cls, self.b_cls, [(0, self.c_cls, cls, 0)])
+        self._out_conv(plan, v[36:], 'mr', self.u_ri, self.b_ri,
+                       [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
         return cls, reg, iou
 
 
-class WinogradFCOSHead(object):
-    """the GN conv towers and output convolutions of an IoUawareFCOSHead or a plain FCOSHead, all
-    levels at once: every tower layer is a Winograd convolution without bias / ReLU followed by the
+class WinogradFCOSHead(_WinogradTowers):
+    """the GN conv towers and output convolutions of an IoUawareFCOSHead or a plain FCOSHead:
+    every tower layer is a Winograd convolution without bias / ReLU followed by the
     HIP GroupNorm + ReLU over both towers (csrc/groupnorm.hip: 2 x num_groups groups, the two
     towers' affine parameters side by side); outputs fcos_cls | fcos_centerness on the cls tower,
     fcos_reg | fcos_iou (plain head: fcos_reg alone) on the reg tower, then exp(scale_l * reg) per
@@ -323,101 +367,50 @@ class WinogradFCOSHead(object):
         convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
         for m in convs_c + convs_r:
             if not (m.with_norm and m.norm_cfg.get('type') == 'GN' and m.with_activatation
-                    and m.conv.bias is None and m.activate_last and _wino_ok_conv(m.conv)):
+                    and m.conv.bias is None and m.activate_last and plain_3x3(m.conv)):
                 raise NotImplementedError('FCOS towers other than 3x3 conv (no bias) + GN + ReLU')
-        self.n_layers = len(convs_c)
-        F = head.feat_channels
-        if head.in_channels % 4 or F % 4:
-            raise ValueError('channel counts must be multiples of 4')
-        self.F, self.cin = F, head.in_channels
+        super(WinogradFCOSHead, self).__init__(head)
         self.groups = 2 * int(convs_c[0].norm.num_groups)
         self.eps = float(convs_c[0].norm.eps)
         if any(float(m.norm.eps) != self.eps or 2 * int(m.norm.num_groups) != self.groups
                for m in convs_c + convs_r):
             raise NotImplementedError('towers with different GroupNorm settings')
-
-        def affine(mc, mr):
-            g = torch.cat([mc.norm.weight.detach(), mr.norm.weight.detach()]).float().contiguous()
-            b = torch.cat([mc.norm.bias.detach(), mr.norm.bias.detach()]).float().contiguous()
-            return g, b
-
-        self.u0 = torch.cat([transform_weight(convs_c[0].conv.weight),
-                             transform_weight(convs_r[0].conv.weight)], dim=2).contiguous()
-        self.gn = [affine(convs_c[0], convs_r[0])]
-        self.u = []
-        for i in range(1, self.n_layers):
-            self.u.append(torch.cat([transform_weight(convs_c[i].conv.weight),
-                                     transform_weight(convs_r[i].conv.weight)], dim=0).contiguous())
-            self.gn.append(affine(convs_c[i], convs_r[i]))
-        dev = self.u0.device
-
-        def pair(a, b):
-            """one or two output convolutions on one tower: (U (36, F, n_pad), bias (n_pad,),
-            n_a, n_b); b None: n_b = 0"""
-            na, nb = a.out_channels, (0 if b is None else b.out_channels)
-            n_pad = (na + nb + 15) // 16 * 16
-            u = torch.zeros((36, F, n_pad), dtype=torch.float32, device=dev)
-            u[:, :, :na] = transform_weight(a.weight)
-            bias = torch.zeros(n_pad, dtype=torch.float32, device=dev)
-            bias[:na] = a.bias.detach().float()
-            if b is not None:
-                u[:, :, na:na + nb] = transform_weight(b.weight)
-                bias[na:na + nb] = b.bias.detach().float()
-            return u.contiguous(), bias.contiguous(), na, nb
-
-        self.u_cc, self.b_cc, self.c_cls, self.c_ctr = pair(head.fcos_cls, head.fcos_centerness)
+        # per layer: the two towers' affine parameters side by side (2F,)
+        self.gn = [(torch.cat([mc.norm.weight.detach(), mr.norm.weight.detach()]).float().contiguous(),
+                    torch.cat([mc.norm.bias.detach(), mr.norm.bias.detach()]).float().contiguous())
+                   for mc, mr in zip(convs_c, convs_r)]
+        self.u_cc, self.b_cc, self.c_cls, self.c_ctr = _pair(head.fcos_cls, head.fcos_centerness,
+                                                             self.F, 16)
         # the plain FCOSHead has no IoU branch: its reg tower feeds fcos_reg alone (c_iou = 0)
-        self.u_ri, self.b_ri, self.c_reg, self.c_iou = pair(head.fcos_reg,
-                                                            getattr(head, 'fcos_iou', None))
+        self.u_ri, self.b_ri, self.c_reg, self.c_iou = _pair(head.fcos_reg,
+                                                             getattr(head, 'fcos_iou', None),
+                                                             self.F, 16)
         if self.c_reg % 4:
             raise ValueError('the regression output needs a multiple of 4 channels')
         self.scales = torch.stack([s.scale.detach().float() for s in head.scales]).contiguous()
-        self._plans = collections.OrderedDict()
         self.calls = 0                        # forwards served (tests: the route was taken)
 
     def usable(self, feats):
-        return len(feats) <= self.scales.numel() and \
-            all(_usable(x) and x.shape[1] == self.cin for x in feats) and not torch.is_grad_enabled()
+        return len(feats) <= self.scales.numel() and super(WinogradFCOSHead, self).usable(feats)
 
-    def _gn(self, acts, i):
+    def _layer_out(self, plan, m, groups, i, acts):
         from .fcos_ops import groupnorm_relu_
+        output_transform(plan, m, 2 * self.F, groups, None, False, [(0, 2 * self.F, acts, 0)])
         g, b = self.gn[i]
         groupnorm_relu_(acts, g, b, self.groups, self.eps, relu=True)
 
     def __call__(self, feats):
         """feats: per-level (B, Cin, H, W) channels-last fp32 -> (cls[L], bbox[L], centerness[L],
         iou[L]) (plain head: (cls[L], bbox[L], centerness[L])), channels-last"""
-        B = feats[0].shape[0]
-        sizes = [tuple(x.shape[-2:]) for x in feats]
-        key = (B, tuple(sizes), feats[0].device, stream_id())
-        plan = _plan_for(self._plans, key, lambda: _Plan(sizes, B, feats[0].device))
-        T, F = plan.T, self.F
-        v = input_transform(plan, feats, 1, plan.buf('v', (36, T, self.cin)))
-        m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)))
-        acts = plan.acts('a', 2 * F)
-        output_transform(plan, m, 2 * F, 1, None, False, [(0, 2 * F, acts, 0)])
-        self._gn(acts, 0)
-        for i, u in enumerate(self.u):
-            v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
-            m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
-            nxt = plan.acts('b' if acts is plan.acts('a', 2 * F) else 'a', 2 * F)
-            output_transform(plan, m, 2 * F, 2, None, False, [(0, 2 * F, nxt, 0)])
-            self._gn(nxt, i + 1)
-            acts = nxt
-        v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
-        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=feats[0].device,  # noqa: E731
-                                     memory_format=torch.channels_last) for (h, w) in sizes]
+        plan, v, new = self._towers(feats)
         cls, ctr, reg = new(self.c_cls), new(self.c_ctr), new(self.c_reg)
         iou = new(self.c_iou) if self.c_iou else None
-        n_cc, n_ri = self.u_cc.shape[2], self.u_ri.shape[2]
-        m_cc = batched_gemm(v[:36], self.u_cc, plan.buf('mc', (36, T, n_cc)))
-        output_transform(plan, m_cc, n_cc, 1, self.b_cc, False,
-                         [(0, self.c_cls, cls, 0), (self.c_cls, self.c_ctr, ctr, 0)])
-        m_ri = batched_gemm(v[36:], self.u_ri, plan.buf('mr', (36, T, n_ri)))
+        self._out_conv(plan, v[:36], 'mc', self.u_cc, self.b_cc,
+                       [(0, self.c_cls, cls, 0), (self.c_cls, self.c_ctr, ctr, 0)])
         segs = [(0, self.c_reg, reg, 0)]
         if iou is not None:
             segs.append((self.c_reg, self.c_iou, iou, 0))
-        output_transform(plan, m_ri, n_ri, 1, self.b_ri, False, segs)
+        self._out_conv(plan, v[36:], 'mr', self.u_ri, self.b_ri, segs)
         ptrs = (C.c_void_p * len(reg))(*[t.data_ptr() for t in reg])
         _lib.check(_lib.lib().ia_scale_exp_levels(C.byref(plan.geom), ptrs, self.c_reg,
                                                   _ptr(self.scales), _stream()),
@@ -426,8 +419,3 @@ class WinogradFCOSHead(object):
         if iou is None:
             return cls, reg, ctr
         return cls, reg, ctr, iou
-
-
-def _wino_ok_conv(conv):
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1)

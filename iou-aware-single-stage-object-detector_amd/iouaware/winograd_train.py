@@ -203,9 +203,7 @@ def wino_conv_levels(xs, weight, bias=None, relu=False):
 
 def _plain_3x3(conv):
     """3x3 / stride 1 / pad 1 / dilation 1 / groups 1 nn.Conv2d -- what the Winograd route computes"""
-    return (type(conv) is torch.nn.Conv2d and tuple(conv.kernel_size) == (3, 3)
-            and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.bias is not None
+    return (type(conv) is torch.nn.Conv2d and W.plain_3x3(conv) and conv.bias is not None
             and conv.padding_mode == 'zeros')
 
 
