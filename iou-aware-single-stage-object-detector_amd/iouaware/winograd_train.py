@@ -139,6 +139,36 @@ def relu_bwd_bias_grad(dy, y=None, bias_grad=True):
 
 
 DU = 'lt'             # 'lt': ops.gemm_tn (library candidates timed per shape); 'bmm': torch.bmm
+DU_ROWS = 1024        # longest run of tiles that one product of the weight gradient accumulates
+
+
+def _du_slices(tiles):
+    """The library's fp32 GEMMs add the terms of a dot product one after the other: over the 5 720
+    tiles of a training batch the rounding error of dU = V^T dM is 6-10 x that of a blocked sum
+    (2-4e-6 against 3e-7 of the maximum), and G^T dU G, which cancels most of dU, turns it into
+    2.5-4.3e-5 of dW -- 4-7 x what a plain fp32 evaluation of F(4x4,3x3) loses
+    (tests/test_gpu_wino_fp64.py).  So the tiles are cut into equal slices of at most about DU_ROWS,
+    each its own matrix of the batched product (a view: slices = a divisor of the tile count), and
+    the partial results are added.  -> the number of slices (1: no divisor in reach)"""
+    want = -(-tiles // DU_ROWS)
+    if want > 1:
+        for n in range(want, 4 * want + 1):
+            if tiles % n == 0:
+                return n
+    return 1
+
+
+def weight_grad_product(v, dm):
+    """dU[k] = V[k]^T dM[k]: (36, T, Cin), (36, T, Cout) -> (36, Cin, Cout)"""
+    from . import ops
+    if DU != 'lt':
+        return torch.bmm(v.transpose(1, 2), dm)
+    n = _du_slices(v.shape[1])
+    if n == 1:
+        return ops.gemm_tn(v, dm)
+    rows = v.shape[1] // n
+    du = ops.gemm_tn(v.view(36 * n, rows, v.shape[2]), dm.view(36 * n, rows, dm.shape[2]))
+    return du.view(36, n, v.shape[2], dm.shape[2]).sum(1)
 
 
 class _WinoConvLevels(torch.autograd.Function):
@@ -189,9 +219,7 @@ class _WinoConvLevels(torch.autograd.Function):
             if ctx.needs_input_grad[0] and v is not None:
                 cout = weight.shape[0]
                 dm = grad_output_transform(plan, dys, plan.buf('tdm', (36, plan.T, cout)))
-                from .ops import gemm_tn
-                du = gemm_tn(v, dm) if DU == 'lt' else torch.bmm(v.transpose(1, 2), dm)   # (36, Cin, Cout)
-                dw = untransform_weight_grad(du, like=weight)
+                dw = untransform_weight_grad(weight_grad_product(v, dm), like=weight)
         return (dw, db, None) + tuple(dxs)
 
 
