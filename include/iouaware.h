@@ -836,6 +836,81 @@ int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p,
                             void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                             int32_t *rows, int32_t *num, void *stream);
 
+/* ------------------------------------------------------------------ FCOS training: point targets
+ * fcos_target / fcos_target_single of fcos_head.py and iou_aware_fcos_head.py for a whole batch in
+ * one launch.  Point (x * stride + stride / 2, y * stride + stride / 2) of level l; for gt g
+ * left = px - x1, top = py - y1, right = x2 - px, bottom = y2 - py; g is a candidate iff
+ * min(l,t,r,b) > 0 and lo_l <= max(l,t,r,b) <= hi_l (regress_ranges: HOST (L,2) fp32, both ends
+ * inclusive); the candidate of minimal area (x2 - x1 + 1) * (y2 - y1 + 1) wins, equal areas: the
+ * lowest gt index; an area >= 1e8 counts as no candidate (the reference's INF sentinel).  Every
+ * quantity is one IEEE fp32 operation on fp32 inputs (no contraction): labels and targets are
+ * bit-identical to the torch evaluation on the CPU.
+ * gt_boxes / gt_labels / num_gt as ia_anchor_targets_ptrs: HOST arrays of per-image DEVICE
+ * pointers (boxes 16-byte aligned), host num_gt[b] in 1..512, batch <= IA_MAX_TARGET_BATCH.
+ * Geometry: ia_point_head_geom (nms_pre, layout, score_alpha ignored).
+ * Outputs, level-major as ia_anchor_targets (level l a (B, N_l[,4]) block at element offset
+ * B * point_off_l): labels int64 (0 = background, else gt_labels[g]); bbox_targets (l,t,r,b) of the
+ * chosen gt, of gt 0 for a background point; counts (B) int32 positives per image.
+ * packed (optional, ia_point_packed_labels_elems int32 elements, 16-byte aligned): the int32 copy of
+ * the labels followed by fp32 weights of 1 that ia_point_head_loss_* read -- written here, the loss
+ * needs no pack launch.                                                                       */
+size_t ia_point_packed_labels_elems(const ia_point_head_geom *g, int batch);
+int ia_point_targets_ptrs(const ia_point_head_geom *g, const float *const *gt_boxes,
+                          const int64_t *const *gt_labels, const int32_t *num_gt, int batch,
+                          const float *regress_ranges, int64_t *labels, float *bbox_targets,
+                          int32_t *packed, int32_t *counts, void *stream);
+
+/* ------------------------------------------------------------------ FCOS training: loss, all levels
+ * The loss of IoUawareFCOSHead / FCOSHead (iou_aware_fcos_head.py:139-226, fcos_head.py:105-191)
+ * for every level in <= 4 launches forward and 2 backward.  fp32 NCHW head outputs: cls
+ * (B,C,H,W), reg (B,4,H,W) = the exponentiated distances, ctr (B,1,H,W), iou (B,1,H,W) or -- plain
+ * FCOS -- every iou pointer NULL (mixed: IA_E_ARG).  With P the positive points (label > 0),
+ * n = |P|, c_p = sqrt(min(l,r)/max(l,r) * min(t,b)/max(t,b)) of the target distances and u_p the
+ * aligned (+1) IoU of distance2bbox(point, pred) and distance2bbox(point, target):
+ *   loss_cls        = sum of the sigmoid focal loss (gamma = 2, class label - 1 positive) / (n + B)
+ *   loss_reg        = sum_P -log(u_p) c_p / sum_P c_p
+ *   loss_centerness = sum_P BCE_logits(ctr_p, c_p) / n
+ *   loss_iou        = sum_P BCE_logits(iou_p, u_p) / n, u_p attached (cfg->attach_iou_target): its
+ *                     gradient reaches reg
+ * n = 0: the three positive-only terms are 0 with zero gradients, loss_cls = sum / B.
+ * result: 6 fp32 = loss_cls | loss_reg | loss_centerness | loss_iou (0 without the branch) | n |
+ * sum_P c_p.  Class logits > 60: as ia_head_loss_cfg.exact_large_logits.                    */
+typedef struct ia_point_level_ptrs {
+    const void *cls[IA_MAX_LEVELS];
+    const void *reg[IA_MAX_LEVELS];
+    const void *ctr[IA_MAX_LEVELS];
+    const void *iou[IA_MAX_LEVELS];     /* all set (IoU-aware FCOS) or all NULL (plain FCOS) */
+} ia_point_level_ptrs;
+
+typedef struct ia_point_targets {
+    const int64_t *labels[IA_MAX_LEVELS];        /* (B, N_l) int64 in 0..C, as ia_point_targets_ptrs */
+    const float *bbox_targets[IA_MAX_LEVELS];    /* (B, N_l, 4), 16-byte aligned                    */
+    const int32_t *packed;                       /* of ia_point_targets_ptrs for the same geometry and
+                                                    batch, or NULL: the forward call packs the labels
+                                                    into its workspace (one more launch)             */
+    const int32_t *counts;                       /* (B) positives per image, or NULL: counted        */
+} ia_point_targets;
+
+typedef struct ia_point_loss_cfg {
+    float gamma, alpha;                          /* focal loss; gamma must be 2                       */
+    int32_t attach_iou_target;                   /* gradient of loss_iou through u_p (reference: yes) */
+    int32_t exact_large_logits;                  /* as ia_head_loss_cfg                               */
+} ia_point_loss_cfg;
+
+/* workspace (256-byte aligned): fp64 partial sums, the focal kernel's normaliser / upstream
+ * vector and (when t->packed is NULL) the packed labels; the forward call writes it, the backward
+ * call reads it -- keep it alive and untouched between the two.  0: unsupported geometry / batch. */
+size_t ia_point_head_loss_workspace_bytes(const ia_point_head_geom *g, int batch);
+int ia_point_head_loss_fwd(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
+                           const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                           void *workspace, size_t workspace_bytes, float *result, void *stream);
+/* grad_result: 4 fp32 on the device, the upstream gradients of the four losses; grads: fp32 tensors
+ * shaped like the head outputs, every element written (zeros at background points).          */
+int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
+                           const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                           void *workspace, const float *result, const float *grad_result,
+                           const ia_point_level_ptrs *grads, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

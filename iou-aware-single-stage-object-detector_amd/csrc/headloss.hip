@@ -36,20 +36,9 @@
 // the losses_iou entries of the result are 0.  Focal kernels, packed targets and slots are shared.
 #include <string.h>
 #include "ia_loss.hpp"
+#include "ia_headloss.hpp"
 
 namespace ia {
-
-struct HLLevels {
-    int32_t L, B, A, C;
-    int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
-    int32_t blk_off[IA_MAX_LEVELS + 1];   // prefix over launch order o (level = L-1-o) of B*A*tiles
-    // focal kernel: the class range of the small levels is cut into csplit chunks of cchunk classes
-    // (a lone wavefront per (image, anchor, tile) would run 80 dependent class steps while the
-    // big level streams: the small levels' chains, not HBM, would set the kernel's duration)
-    int32_t csplit[IA_MAX_LEVELS], cchunk[IA_MAX_LEVELS];
-    int32_t fblk_off[IA_MAX_LEVELS + 1];  // prefix of B*A*csplit*tiles
-    int32_t pack_off[IA_MAX_LEVELS + 1];  // prefix of B*A*HW: element offset of a level in the packed targets
-};
 
 struct BlockRef { int l, b, an, p0, chunk; };
 
@@ -84,18 +73,6 @@ __device__ __forceinline__ float upstream(const float *gin, const float *res, in
 }
 
 // ------------------------------------------------------------------ focal, all levels
-struct FocalMLArgs {
-    HLLevels lv;
-    const void *cls[IA_MAX_LEVELS];
-    const int32_t *lab_am;                // packed targets: anchor-major labels / weights,
-    const float *w_am;                    // level l at pack_off[l], then (B, A, HW)
-    float *grad[IA_MAX_LEVELS];
-    double *sums;                         // fwd: [3][L][IA_LOSS_SLOTS]
-    const float *gin, *res;               // bwd
-    float alpha_pos, alpha_neg, loss_weight;
-    int32_t big_logits;                   // evaluate the exact tail for logits > kXMax (fwd)
-};
-
 // ---- element math.  With t = exp(x), s = 1 + t:   sigmoid(x) = t/s,  1 - sigmoid(x) = 1/s,
 // BCE(x, 0) = softplus(x) = log(s),  BCE(x, 1) = softplus(-x) = log(s) - x.
 // One v_exp_f32, one v_rcp_f32, one v_log_f32 per element (the transcendental unit issues at an
@@ -745,7 +722,7 @@ static bool iou_ptrs_ok(const ia_level_ptrs *p, int L, bool with_iou)
     return true;
 }
 
-static int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
+int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
 {
     if (!g || B < 1) return IA_E_ARG;
     if (g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS) return IA_E_ARG;
@@ -786,6 +763,15 @@ static int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
         lv.fblk_off[o + 1] = (int32_t)foff;
     }
     return 0;
+}
+
+
+int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s)
+{
+    const unsigned fgrid = (unsigned)fa.lv.fblk_off[fa.lv.L];
+    if (bwd) hipLaunchKernelGGL((k_focal_ml<float, true>), dim3(fgrid), dim3(64), 0, s, fa);
+    else hipLaunchKernelGGL((k_focal_ml<float, false>), dim3(fgrid), dim3(64), 0, s, fa);
+    return hip_status(hipGetLastError());
 }
 
 }  // namespace ia

@@ -1,0 +1,39 @@
+// What the all-levels head-loss kernels of headloss.hip share with the point-head loss
+// (pointloss.hip): the level / launch-order table, the focal kernel's arguments and its launcher.
+// The kernels themselves stay in headloss.hip (one translation unit owns their device code);
+// pointloss.hip runs the focal kernel through launch_focal_ml_f32 with A = 1.
+#pragma once
+#include "ia_internal.hpp"
+
+namespace ia {
+
+struct HLLevels {
+    int32_t L, B, A, C;
+    int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
+    int32_t blk_off[IA_MAX_LEVELS + 1];   // prefix over launch order o (level = L-1-o) of B*A*tiles
+    // focal kernel: the class range of the small levels is cut into csplit chunks of cchunk classes
+    // (a lone wavefront per (image, anchor, tile) would run 80 dependent class steps while the
+    // big level streams: the small levels' chains, not HBM, would set the kernel's duration)
+    int32_t csplit[IA_MAX_LEVELS], cchunk[IA_MAX_LEVELS];
+    int32_t fblk_off[IA_MAX_LEVELS + 1];  // prefix of B*A*csplit*tiles
+    int32_t pack_off[IA_MAX_LEVELS + 1];  // prefix of B*A*HW: element offset of a level in the packed targets
+};
+
+struct FocalMLArgs {
+    HLLevels lv;
+    const void *cls[IA_MAX_LEVELS];
+    const int32_t *lab_am;                // packed targets: anchor-major labels / weights,
+    const float *w_am;                    // level l at pack_off[l], then (B, A, HW)
+    float *grad[IA_MAX_LEVELS];
+    double *sums;                         // fwd: [3][L][IA_LOSS_SLOTS]
+    const float *gin, *res;               // bwd
+    float alpha_pos, alpha_neg, loss_weight;
+    int32_t big_logits;                   // evaluate the exact tail for logits > kXMax (fwd)
+};
+
+// geometry -> table (IA_E_ARG for what the kernels do not cover); headloss.hip
+int fill_levels(const ia_head_geom *g, int B, HLLevels &lv);
+// k_focal_ml<float, bwd> over fa.lv.fblk_off[L] wavefronts; headloss.hip
+int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s);
+
+}  // namespace ia

@@ -1,0 +1,504 @@
+// Training side of the FCOS heads (IoUawareFCOSHead, FCOSHead): point targets and the loss of
+// every pyramid level (reference fcos_head.py:105-191 / iou_aware_fcos_head.py:139-226 `loss`,
+// `fcos_target`, `fcos_target_single`, `centerness_target`; core/loss/losses.py:636-646 iou_loss;
+// core/bbox/geometry.py aligned bbox_overlaps; core/bbox/transforms.py distance2bbox).
+//
+//   targets : k_point_targets                                               (1 launch)
+//   forward : [k_point_pack]  k_focal_ml<fwd>  k_point_box<fwd>  k_point_finalize   (3-4 launches)
+//   backward: k_point_box<bwd>  k_focal_ml<bwd>                             (2 launches)
+//
+// * k_point_targets -- a workgroup owns 256 points of one (level, image), stages that image's gt
+//   boxes and areas in LDS once and every thread scans them.  Every quantity is one IEEE fp32
+//   operation on fp32 inputs, the area's product is not contracted (-ffp-contract=off is part of
+//   the build): labels and targets are bit-identical to the torch evaluation on the CPU.  It also
+//   writes the int32 label copy (+ weights of 1) the focal kernel reads: with A = 1 the kernel's
+//   anchor-major (B, A, HW) order IS the level-major (B, N_l) order of the targets.
+// * focal term -- k_focal_ml<float> of headloss.hip with A = 1, through launch_focal_ml_f32.  Its
+//   backward reads upstream gradient and normaliser in the (3L + 4) layout of the anchor node:
+//   k_point_finalize writes an internal vector in that layout (normaliser n + B), and
+//   k_point_box<bwd>, which runs before it, copies the upstream gradient of loss_cls into it.
+// * k_point_box -- one pass over the labels; only a positive point (< 2 % of them) reads targets,
+//   distances, centerness and IoU logits; exact-math helpers of ia_math.hpp there.  Forward: five
+//   fp64 sums into the IA_LOSS_SLOTS scheme; backward: d bbox_pred (IoU-loss part + the part
+//   through the attached IoU target in one store), d centerness, d iou for every point.
+// * k_point_finalize -- slots -> the six result floats; n = 0 decided here, on the device.
+#include <string.h>
+#include "ia_loss.hpp"
+#include "ia_headloss.hpp"
+
+namespace ia {
+
+constexpr int kPtMaxGt = 512;             // gt boxes per image held in LDS
+constexpr float kPtInf = 1e8f;            // the reference's INF sentinel (fcos_head.py:11)
+constexpr int kPtSums = 5;                // sum -log(u) c | sum c | sum BCE_ctr | sum BCE_iou | n
+constexpr int kPtSlotMask = IA_LOSS_SLOTS - 1;
+
+static int point_levels(const ia_point_head_geom *pg, int B, HLLevels &lv)
+{
+    if (!pg) return IA_E_ARG;
+    ia_head_geom g = ia_head_geom{};
+    g.num_levels = pg->num_levels;
+    g.num_anchors = 1;
+    g.num_classes = pg->num_classes;
+    if (g.num_levels < 1 || g.num_levels > IA_MAX_LEVELS) return IA_E_ARG;
+    for (int l = 0; l < g.num_levels; ++l) {
+        g.H[l] = pg->H[l]; g.W[l] = pg->W[l]; g.stride[l] = pg->stride[l];
+        if (g.stride[l] < 1) return IA_E_ARG;
+    }
+    g.layout = IA_LAYOUT_NCHW;
+    g.cls_activation = IA_CLS_SIGMOID_NOIOU;
+    int rc = fill_levels(&g, B, lv);
+    if (rc) return rc;
+    // the focal kernel reads the packed labels of a level with HW % 4 == 0 in 16-byte pieces
+    for (int l = 0; l < lv.L; ++l)
+        if (((lv.H[l] * lv.W[l]) & 3) == 0 && (lv.pack_off[l] & 3)) return IA_E_ARG;
+    return 0;
+}
+
+// packed labels: int32 labels [padded] | fp32 weights [padded]
+static size_t packed_pad(const HLLevels &lv) { return ((size_t)lv.pack_off[lv.L] + 63) / 64 * 64; }
+
+struct PtBlock { int l, b, p0; };
+__device__ __forceinline__ PtBlock locate_point_block(const HLLevels &lv, int bid)
+{
+    int o = 0;
+    while (bid >= lv.blk_off[o + 1]) ++o;                 // launch order: small levels first
+    PtBlock r;
+    r.l = lv.L - 1 - o;
+    const int q = bid - lv.blk_off[o];
+    const int tiles = (lv.H[r.l] * lv.W[r.l] + 255) / 256;
+    r.b = q / tiles;
+    r.p0 = (q - r.b * tiles) * 256;
+    return r;
+}
+
+// ------------------------------------------------------------------ targets
+struct PtTargetArgs {
+    HLLevels lv;
+    const float *gt_ptr[IA_MAX_TARGET_BATCH];
+    const int64_t *gl_ptr[IA_MAX_TARGET_BATCH];
+    int16_t num_gt[IA_MAX_TARGET_BATCH];
+    float lo[IA_MAX_LEVELS], hi[IA_MAX_LEVELS];
+    int64_t *labels;                      // level-major (B, N_l) blocks
+    float *bbox_targets;                  // level-major (B, N_l, 4) blocks
+    int32_t *lab32;                       // packed copy or NULL
+    float *w32;
+    int32_t *counts;                      // (B), zero-initialised
+};
+
+__global__ void __launch_bounds__(256) k_point_targets(PtTargetArgs a)
+{
+    __shared__ float4 s_gt[kPtMaxGt];
+    __shared__ float s_area[kPtMaxGt];
+    __shared__ uint32_t s_cnt;
+    const PtBlock r = locate_point_block(a.lv, blockIdx.x);
+    const int G = a.num_gt[r.b];
+    const float4 *gsrc = reinterpret_cast<const float4 *>(a.gt_ptr[r.b]);
+    for (int g = threadIdx.x; g < G; g += 256) {
+        const float4 q = gsrc[g];
+        s_gt[g] = q;
+        s_area[g] = ((q.z - q.x) + 1.0f) * ((q.w - q.y) + 1.0f);
+    }
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const int W = a.lv.W[r.l], HW = a.lv.H[r.l] * W, s = a.lv.stride[r.l];
+    const int p = r.p0 + threadIdx.x;
+    bool is_pos = false;
+    if (p < HW) {
+        const int y = p / W, x = p - y * W;
+        const float px = (float)(x * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+        const float lo = a.lo[r.l], hi = a.hi[r.l];
+        // areas.min(dim=1) over the row with non-candidates set to INF: the first minimum
+        float best = 0.0f;
+        int arg = 0;
+        float4 bt = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int g = 0; g < G; ++g) {
+            const float4 q = s_gt[g];
+            const float dl = px - q.x, dt = py - q.y, dr = q.z - px, db = q.w - py;
+            const float mn = __builtin_fminf(__builtin_fminf(dl, dt), __builtin_fminf(dr, db));
+            const float mx = __builtin_fmaxf(__builtin_fmaxf(dl, dt), __builtin_fmaxf(dr, db));
+            const bool cand = (mn > 0.0f) && (mx >= lo) && (mx <= hi);
+            const float ar = cand ? s_area[g] : kPtInf;
+            if (g == 0 || ar < best) { best = ar; arg = g; bt = make_float4(dl, dt, dr, db); }
+        }
+        int64_t label = 0;
+        if (best != kPtInf) { label = a.gl_ptr[r.b][arg]; is_pos = label != 0; }
+        const size_t out = (size_t)a.lv.pack_off[r.l] + (size_t)r.b * HW + p;   // A = 1: B * point_off_l + b * N_l + p
+        a.labels[out] = label;
+        reinterpret_cast<float4 *>(a.bbox_targets)[out] = bt;
+        if (a.lab32) { a.lab32[out] = (int32_t)label; a.w32[out] = 1.0f; }
+    }
+    const uint64_t mp = __ballot(is_pos);
+    if ((threadIdx.x & 63) == 0 && mp) atomicAdd(&s_cnt, (uint32_t)__builtin_popcountll(mp));
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&a.counts[r.b], (int32_t)s_cnt);
+}
+
+// ------------------------------------------------------------------ labels -> packed copy
+struct PtPackArgs {
+    HLLevels lv;
+    const int64_t *labels[IA_MAX_LEVELS];
+    int32_t *lab32;
+    float *w32;
+};
+
+__global__ void __launch_bounds__(256) k_point_pack(PtPackArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.lv.pack_off[a.lv.L]) return;
+    int l = 0;
+    while (i >= a.lv.pack_off[l + 1]) ++l;
+    a.lab32[i] = (int32_t)a.labels[l][i - a.lv.pack_off[l]];
+    a.w32[i] = 1.0f;
+}
+
+// ------------------------------------------------------------------ regression / centerness / IoU terms
+struct PtBoxArgs {
+    HLLevels lv;
+    const float *reg[IA_MAX_LEVELS], *ctr[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
+    const float *bt[IA_MAX_LEVELS];
+    const int32_t *lab32;
+    float *g_reg[IA_MAX_LEVELS], *g_ctr[IA_MAX_LEVELS], *g_iou[IA_MAX_LEVELS];
+    double *sums;                         // fwd: [kPtSums][IA_LOSS_SLOTS] behind the focal slots
+    const float *res, *gin;               // bwd: the six result floats, the four upstream gradients
+    float *fgin;                          // bwd: the focal kernel's upstream vector (entry 3L)
+    int32_t attach;
+};
+
+struct PtElem { float c, u, ov, un, w, h, pw, ph; bool x1in, y1in, x2in, y2in; };
+
+// centerness target, the two boxes and their aligned IoU (+1 widths) of one positive point
+__device__ __forceinline__ PtElem point_elem(float px, float py, const float (&d)[4], const float4 &t)
+{
+    PtElem e;
+    const float lrmin = __builtin_fminf(t.x, t.z), lrmax = __builtin_fmaxf(t.x, t.z);
+    const float tbmin = __builtin_fminf(t.y, t.w), tbmax = __builtin_fmaxf(t.y, t.w);
+    e.c = __builtin_sqrtf((lrmin / lrmax) * (tbmin / tbmax));
+    const float px1 = px - d[0], py1 = py - d[1], px2 = px + d[2], py2 = py + d[3];
+    const float tx1 = px - t.x, ty1 = py - t.y, tx2 = px + t.z, ty2 = py + t.w;
+    e.x1in = px1 > tx1; e.y1in = py1 > ty1; e.x2in = px2 < tx2; e.y2in = py2 < ty2;
+    const float ltx = e.x1in ? px1 : tx1, lty = e.y1in ? py1 : ty1;
+    const float rbx = e.x2in ? px2 : tx2, rby = e.y2in ? py2 : ty2;
+    const float w0 = (rbx - ltx) + 1.0f, h0 = (rby - lty) + 1.0f;
+    e.w = (w0 < 0.0f) ? 0.0f : w0; e.h = (h0 < 0.0f) ? 0.0f : h0;
+    e.ov = e.w * e.h;
+    e.pw = (px2 - px1) + 1.0f; e.ph = (py2 - py1) + 1.0f;
+    const float ap = e.pw * e.ph;
+    const float at = ((tx2 - tx1) + 1.0f) * ((ty2 - ty1) + 1.0f);
+    e.un = (ap + at) - e.ov;
+    e.u = e.ov / e.un;
+    return e;
+}
+
+template <bool BWD, bool IOU>
+__global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
+{
+    __shared__ double red[kPtSums][4];
+    const PtBlock r = locate_point_block(a.lv, blockIdx.x);
+    const int W = a.lv.W[r.l], HW = a.lv.H[r.l] * W;
+    const int p = r.p0 + threadIdx.x;
+    if (BWD && blockIdx.x == 0 && threadIdx.x == 0) a.fgin[3 * a.lv.L] = a.gin[0];
+    double acc[kPtSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    bool pos = false;
+    if (p < HW) {
+        const size_t e1 = (size_t)r.b * HW + p;
+        pos = a.lab32[(size_t)a.lv.pack_off[r.l] + e1] > 0;
+        float g_box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g_ctr = 0.0f, g_iou = 0.0f;
+        if (pos) {
+            const float *bp = a.reg[r.l] + (size_t)r.b * 4 * HW + p;
+            const float d[4] = {bp[0], bp[(size_t)HW], bp[(size_t)2 * HW], bp[(size_t)3 * HW]};
+            const float4 t = reinterpret_cast<const float4 *>(a.bt[r.l])[e1];
+            const int y = p / W, x = p - y * W, s = a.lv.stride[r.l];
+            const float px = (float)(x * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+            const PtElem q = point_elem(px, py, d, t);
+            const float xc = a.ctr[r.l][e1];
+            float xi = 0.0f;
+            if constexpr (IOU) xi = a.iou[r.l][e1];
+            if (!BWD) {
+                acc[0] = (double)(-logf_(q.u) * q.c);
+                acc[1] = (double)q.c;
+                acc[2] = (double)bce_logits_(xc, q.c);
+                if constexpr (IOU) acc[3] = (double)bce_logits_(xi, q.u);
+                acc[4] = 1.0;
+            } else {
+                const float n = a.res[4], sc = a.res[5];
+                const float gs_reg = a.gin[1] / sc, gs_ctr = a.gin[2] / n;
+                g_ctr = (sigmoidf_(xc) - q.c) * gs_ctr;
+                float gu = -(q.c / q.u) * gs_reg;                    // d(-log(u) c) / du
+                if constexpr (IOU) {
+                    const float gs_iou = a.gin[3] / n;
+                    g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
+                    if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
+                }
+                // u = ov / un, un = ap + at - ov
+                const float inv_un = 1.0f / q.un;
+                const float g_ov = gu * ((q.un + q.ov) * inv_un) * inv_un;
+                const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
+                const float g_w = g_ov * q.h, g_h = g_ov * q.w;      // w0, h0 > 0: both boxes hold the point
+                const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
+                // x1 = px - left, x2 = px + right: d/d left = -d/d x1
+                g_box[0] = g_pw + (q.x1in ? g_w : 0.0f);
+                g_box[1] = g_ph + (q.y1in ? g_h : 0.0f);
+                g_box[2] = g_pw + (q.x2in ? g_w : 0.0f);
+                g_box[3] = g_ph + (q.y2in ? g_h : 0.0f);
+            }
+        }
+        if (BWD) {
+            float *go = a.g_reg[r.l] + (size_t)r.b * 4 * HW + p;
+            go[0] = g_box[0];
+            go[(size_t)HW] = g_box[1];
+            go[(size_t)2 * HW] = g_box[2];
+            go[(size_t)3 * HW] = g_box[3];
+            a.g_ctr[r.l][e1] = g_ctr;
+            if constexpr (IOU) a.g_iou[r.l][e1] = g_iou;
+        }
+    }
+    if (!BWD) {
+        // positives are rare: most workgroups have nothing to add
+        if (!__syncthreads_or(pos)) return;
+        const int w = threadIdx.x >> 6;
+#pragma unroll
+        for (int k = 0; k < kPtSums; ++k) {
+            if (k == 3 && !IOU) continue;
+            const double s = wave_sum(acc[k]);
+            if ((threadIdx.x & 63) == 0) red[k][w] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < kPtSums && (IOU || threadIdx.x != 3)) {
+            const int k = threadIdx.x;
+            const double s = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+            atomicAdd(a.sums + (size_t)k * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask), s);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ slots -> losses
+struct PtFinArgs {
+    const double *sums;                   // [L + kPtSums][IA_LOSS_SLOTS]
+    const int32_t *counts;                // (B) or NULL
+    int32_t L, B, iou;
+    float *res;                           // 6
+    float *fgin, *fres;                   // (3L + 4) each: what k_focal_ml<bwd> reads
+};
+
+__global__ void __launch_bounds__(64) k_point_finalize(PtFinArgs a)
+{
+    __shared__ double s_q[IA_MAX_LEVELS + kPtSums];
+    const int i = threadIdx.x;
+    if (i < a.L + kPtSums) {
+        double s = 0.0;
+        for (int k = 0; k < IA_LOSS_SLOTS; ++k) s += a.sums[(size_t)i * IA_LOSS_SLOTS + k];
+        s_q[i] = s;
+    }
+    if (i < 3 * a.L + 4) { a.fgin[i] = 0.0f; a.fres[i] = 0.0f; }
+    __syncthreads();
+    if (i == 0) {
+        double cls = 0.0;
+        for (int l = 0; l < a.L; ++l) cls += s_q[l];
+        const double *q = s_q + a.L;
+        double n = q[4];
+        if (a.counts) {
+            int tot = 0;
+            for (int b = 0; b < a.B; ++b) tot += a.counts[b];
+            n = (double)tot;
+        }
+        const bool any = n > 0.0;                 // n = 0: the reference's empty.sum() = 0
+        a.res[0] = (float)(cls / (n + (double)a.B));
+        a.res[1] = any ? (float)(q[0] / q[1]) : 0.0f;
+        a.res[2] = any ? (float)(q[2] / n) : 0.0f;
+        a.res[3] = (any && a.iou) ? (float)(q[3] / n) : 0.0f;
+        a.res[4] = (float)n;
+        a.res[5] = (float)q[1];
+        a.fres[3 * a.L + 3] = (float)(n + (double)a.B);
+    }
+}
+
+struct PtWorkspace { double *sums; float *fgin, *fres; int32_t *lab32; float *w32; size_t bytes; };
+
+static PtWorkspace carve_point(const HLLevels &lv, void *workspace)
+{
+    const size_t slots = ((sizeof(double) * (lv.L + kPtSums) * IA_LOSS_SLOTS + 255) / 256) * 256;
+    const size_t fint = ((sizeof(float) * 2 * (3 * lv.L + 4) + 255) / 256) * 256;
+    const size_t pk = ((packed_pad(lv) * 4 + 255) / 256) * 256;
+    char *w = static_cast<char *>(workspace);
+    PtWorkspace r;
+    r.sums = reinterpret_cast<double *>(w);
+    r.fgin = reinterpret_cast<float *>(w + slots);
+    r.fres = r.fgin + (3 * lv.L + 4);
+    r.lab32 = reinterpret_cast<int32_t *>(w + slots + fint);
+    r.w32 = reinterpret_cast<float *>(w + slots + fint + pk);
+    r.bytes = slots + fint + 2 * pk;
+    return r;
+}
+
+// what forward and backward check alike; fills the focal and box arguments except the outputs
+static int point_loss_args(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
+                           const ia_point_targets *t, const ia_point_loss_cfg *cfg, void *workspace,
+                           FocalMLArgs &fa, PtBoxArgs &ba, PtWorkspace &ws, bool &with_iou)
+{
+    if (!p || !t || !cfg || !workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
+    int rc = point_levels(g, batch, fa.lv);
+    if (rc) return rc;
+    if (cfg->gamma != 2.0f) return IA_E_ARG;
+    const int L = fa.lv.L;
+    with_iou = p->iou[0] != nullptr;
+    ws = carve_point(fa.lv, workspace);
+    if (t->packed) {
+        if ((uintptr_t)t->packed & 15u) return IA_E_ARG;
+        ws.lab32 = const_cast<int32_t *>(t->packed);
+        ws.w32 = reinterpret_cast<float *>(ws.lab32 + packed_pad(fa.lv));
+    }
+    ba.lv = fa.lv;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < L;
+        if (on && (!p->cls[l] || !p->reg[l] || !p->ctr[l] || !t->labels[l] || !t->bbox_targets[l]))
+            return IA_E_ARG;
+        if (on && ((p->iou[l] != nullptr) != with_iou)) return IA_E_ARG;
+        if (on && ((uintptr_t)t->bbox_targets[l] & 15u)) return IA_E_ARG;
+        if (on && ((uintptr_t)p->cls[l] & 15u)) return IA_E_ARG;                // 16-byte class loads
+        fa.cls[l] = on ? p->cls[l] : nullptr;
+        fa.grad[l] = nullptr;
+        ba.reg[l] = on ? static_cast<const float *>(p->reg[l]) : nullptr;
+        ba.ctr[l] = on ? static_cast<const float *>(p->ctr[l]) : nullptr;
+        ba.iou[l] = on ? static_cast<const float *>(p->iou[l]) : nullptr;
+        ba.bt[l] = on ? t->bbox_targets[l] : nullptr;
+        ba.g_reg[l] = ba.g_ctr[l] = ba.g_iou[l] = nullptr;
+    }
+    fa.lab_am = ws.lab32; fa.w_am = ws.w32;
+    fa.sums = nullptr; fa.gin = fa.res = nullptr;
+    fa.big_logits = 0;
+    fa.alpha_pos = cfg->alpha;
+    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);   // python: (1 - alpha) in double, then fp32
+    fa.loss_weight = 1.0f;
+    ba.lab32 = ws.lab32;
+    ba.sums = nullptr; ba.res = ba.gin = nullptr; ba.fgin = nullptr;
+    ba.attach = cfg->attach_iou_target ? 1 : 0;
+    return 0;
+}
+
+}  // namespace ia
+
+extern "C" {
+
+size_t ia_point_packed_labels_elems(const ia_point_head_geom *g, int batch)
+{
+    ia::HLLevels lv;
+    if (ia::point_levels(g, batch, lv)) return 0;
+    return 2 * ia::packed_pad(lv);
+}
+
+int ia_point_targets_ptrs(const ia_point_head_geom *g, const float *const *gt_boxes,
+                          const int64_t *const *gt_labels, const int32_t *num_gt, int batch,
+                          const float *regress_ranges, int64_t *labels, float *bbox_targets,
+                          int32_t *packed, int32_t *counts, void *stream)
+{
+    using namespace ia;
+    if (!g || !gt_boxes || !gt_labels || !num_gt || !regress_ranges || !labels || !bbox_targets ||
+        !counts || batch < 1 || batch > IA_MAX_TARGET_BATCH)
+        return IA_E_ARG;
+    if (((uintptr_t)bbox_targets & 15u) || ((uintptr_t)packed & 15u)) return IA_E_ARG;
+    PtTargetArgs a;
+    memset(&a, 0, sizeof(a));
+    int rc = point_levels(g, batch, a.lv);
+    if (rc) return rc;
+    for (int b = 0; b < batch; ++b) {
+        if (!gt_boxes[b] || !gt_labels[b] || num_gt[b] < 1 || num_gt[b] > kPtMaxGt) return IA_E_ARG;
+        if (((uintptr_t)gt_boxes[b]) & 15u) return IA_E_ARG;          // float4 loads
+        a.gt_ptr[b] = gt_boxes[b];
+        a.gl_ptr[b] = gt_labels[b];
+        a.num_gt[b] = (int16_t)num_gt[b];
+    }
+    for (int l = 0; l < a.lv.L; ++l) {
+        a.lo[l] = regress_ranges[2 * l]; a.hi[l] = regress_ranges[2 * l + 1];
+        if (!(a.lo[l] <= a.hi[l])) return IA_E_ARG;
+    }
+    a.labels = labels; a.bbox_targets = bbox_targets; a.counts = counts;
+    a.lab32 = packed;
+    a.w32 = packed ? reinterpret_cast<float *>(packed + packed_pad(a.lv)) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)batch, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_point_targets, dim3((unsigned)a.lv.blk_off[a.lv.L]), dim3(256), 0, s, a);
+    return hip_status(hipGetLastError());
+}
+
+size_t ia_point_head_loss_workspace_bytes(const ia_point_head_geom *g, int batch)
+{
+    ia::HLLevels lv;
+    if (ia::point_levels(g, batch, lv)) return 0;
+    return ia::carve_point(lv, nullptr).bytes;
+}
+
+int ia_point_head_loss_fwd(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
+                           const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                           void *workspace, size_t workspace_bytes, float *result, void *stream)
+{
+    using namespace ia;
+    if (!result) return IA_E_ARG;
+    FocalMLArgs fa;
+    PtBoxArgs ba;
+    PtWorkspace ws;
+    bool with_iou;
+    int rc = point_loss_args(g, p, batch, t, cfg, workspace, fa, ba, ws, with_iou);
+    if (rc) return rc;
+    if (workspace_bytes < ws.bytes) return IA_E_WORKSPACE;
+    const int L = fa.lv.L;
+    fa.sums = ws.sums;
+    fa.big_logits = cfg->exact_large_logits ? 1 : 0;
+    ba.sums = ws.sums + (size_t)L * IA_LOSS_SLOTS;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s);
+    if (e != hipSuccess) return (int)e;
+    if (!t->packed) {
+        PtPackArgs pa;
+        pa.lv = fa.lv;
+        for (int l = 0; l < IA_MAX_LEVELS; ++l) pa.labels[l] = l < L ? t->labels[l] : nullptr;
+        pa.lab32 = ws.lab32; pa.w32 = ws.w32;
+        hipLaunchKernelGGL(k_point_pack, dim3((unsigned)((fa.lv.pack_off[L] + 255) / 256)), dim3(256), 0, s, pa);
+    }
+    if ((rc = launch_focal_ml_f32(fa, false, s))) return rc;
+    const unsigned grid = (unsigned)fa.lv.blk_off[L];
+    if (with_iou) hipLaunchKernelGGL((k_point_box<false, true>), dim3(grid), dim3(256), 0, s, ba);
+    else hipLaunchKernelGGL((k_point_box<false, false>), dim3(grid), dim3(256), 0, s, ba);
+    PtFinArgs f;
+    f.sums = ws.sums; f.counts = t->counts; f.L = L; f.B = batch; f.iou = with_iou ? 1 : 0;
+    f.res = result; f.fgin = ws.fgin; f.fres = ws.fres;
+    hipLaunchKernelGGL(k_point_finalize, dim3(1), dim3(64), 0, s, f);
+    return hip_status(hipGetLastError());
+}
+
+int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
+                           const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                           void *workspace, const float *result, const float *grad_result,
+                           const ia_point_level_ptrs *grads, void *stream)
+{
+    using namespace ia;
+    if (!result || !grad_result || !grads) return IA_E_ARG;
+    FocalMLArgs fa;
+    PtBoxArgs ba;
+    PtWorkspace ws;
+    bool with_iou;
+    int rc = point_loss_args(g, p, batch, t, cfg, workspace, fa, ba, ws, with_iou);
+    if (rc) return rc;
+    const int L = fa.lv.L;
+    for (int l = 0; l < L; ++l) {
+        if (!grads->cls[l] || !grads->reg[l] || !grads->ctr[l]) return IA_E_ARG;
+        if ((grads->iou[l] != nullptr) != with_iou) return IA_E_ARG;
+        if ((uintptr_t)grads->cls[l] & 15u) return IA_E_ARG;
+        fa.grad[l] = (float *)grads->cls[l];
+        ba.g_reg[l] = (float *)grads->reg[l];
+        ba.g_ctr[l] = (float *)grads->ctr[l];
+        ba.g_iou[l] = (float *)grads->iou[l];
+    }
+    fa.gin = ws.fgin; fa.res = ws.fres;
+    ba.res = result; ba.gin = grad_result; ba.fgin = ws.fgin;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned grid = (unsigned)fa.lv.blk_off[L];
+    // the box kernel first: it hands the upstream gradient of loss_cls to the focal kernel
+    if (with_iou) hipLaunchKernelGGL((k_point_box<true, true>), dim3(grid), dim3(256), 0, s, ba);
+    else hipLaunchKernelGGL((k_point_box<true, false>), dim3(grid), dim3(256), 0, s, ba);
+    if ((rc = hip_status(hipGetLastError()))) return rc;
+    return launch_focal_ml_f32(fa, true, s);
+}
+
+}  // extern "C"

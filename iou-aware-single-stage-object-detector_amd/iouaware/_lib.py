@@ -66,6 +66,24 @@ class HeadLossCfg(C.Structure):
                 ('grad_rows_start_at_reg', C.c_int32)]
 
 
+class PointLevelPtrs(C.Structure):
+    """ia_point_level_ptrs"""
+    _fields_ = [('cls', C.c_void_p * IA_MAX_LEVELS), ('reg', C.c_void_p * IA_MAX_LEVELS),
+                ('ctr', C.c_void_p * IA_MAX_LEVELS), ('iou', C.c_void_p * IA_MAX_LEVELS)]
+
+
+class PointTargets(C.Structure):
+    """ia_point_targets"""
+    _fields_ = [('labels', C.c_void_p * IA_MAX_LEVELS), ('bbox_targets', C.c_void_p * IA_MAX_LEVELS),
+                ('packed', C.c_void_p), ('counts', C.c_void_p)]
+
+
+class PointLossCfg(C.Structure):
+    """ia_point_loss_cfg"""
+    _fields_ = [('gamma', C.c_float), ('alpha', C.c_float), ('attach_iou_target', C.c_int32),
+                ('exact_large_logits', C.c_int32)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('src_h', C.c_int32), ('src_w', C.c_int32),
                 ('dst_h', C.c_int32), ('dst_w', C.c_int32), ('flip', C.c_int32)]
@@ -92,6 +110,7 @@ class WinoSeg(C.Structure):
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 _G, _P = C.POINTER(HeadGeom), C.POINTER(LevelPtrs)
 _PG, _WG = C.POINTER(PointHeadGeom), C.POINTER(WinoGeom)
+_PP, _PT, _PC = C.POINTER(PointLevelPtrs), C.POINTER(PointTargets), C.POINTER(PointLossCfg)
 
 # name -> (restype, argtypes); mirrors include/iouaware.h one to one
 SIGNATURES = {
@@ -218,6 +237,13 @@ SIGNATURES = {
     'ia_point_ctr_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _vp, _sz, _vp]),
     'ia_point_ctr_get_bboxes': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp,
                                      _vp, _vp, _vp]),
+    'ia_point_packed_labels_elems': (_sz, [_PG, _i]),
+    'ia_point_targets_ptrs': (_i, [_PG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), _vp, _vp, _vp,
+                                   _vp, _vp]),
+    'ia_point_head_loss_workspace_bytes': (_sz, [_PG, _i]),
+    'ia_point_head_loss_fwd': (_i, [_PG, _PP, _i, _PT, _PC, _vp, _sz, _vp, _vp]),
+    'ia_point_head_loss_bwd': (_i, [_PG, _PP, _i, _PT, _PC, _vp, _vp, _vp, _PP, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

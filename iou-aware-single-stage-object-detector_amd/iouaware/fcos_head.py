@@ -8,8 +8,10 @@ constructor kwargs, parameter names and method signatures.
   * get_bboxes: one call into the HIP library for the whole batch (row max, per-level top-k,
     distance2bbox, batched NMS): ia_point_get_bboxes with the fused alpha score (IoU-aware),
     ia_point_ctr_get_bboxes with the raw-threshold / centerness-product scores (plain);
-  * loss: targets and the terms in torch ops on the device, the class term through the
-    HIP sigmoid focal-loss op (integer targets, the reference CUDA op's semantics).
+  * loss: point targets and all terms of every level on HIP kernels (fcos_ops.point_targets,
+    fcos_ops.point_head_loss: csrc/pointloss.hip), no host synchronisation; `fuse_loss = False`, or
+    inputs the node does not cover (see _fused_loss_ok), take the torch transcription of the
+    reference with the class term through the HIP sigmoid focal-loss op.
 There is no CPU fallback for get_bboxes / loss: they need tensors on a gfx950 device.
 
 Both heads are `_FCOSHeadBase` with the class attribute `iou_branch` (fcos_iou present or absent):
@@ -168,6 +170,28 @@ class _FCOSHeadBase(nn.Module):
         return torch.sqrt(c)
 
     # ------------------------------------------------------------------ training
+    # targets and loss on the HIP kernels of csrc/pointloss.hip where they apply (_fused_loss_ok)
+    fuse_loss = True
+
+    def _fused_loss_ok(self, maps, gt_bboxes, gt_labels, cfg):
+        """what the HIP node covers: fp32 NCHW-contiguous device maps, gamma 2, at most 8 levels,
+        1..512 gts per image, at most 16 images"""
+        L = len(maps[0])
+        if not 1 <= L <= fcos_ops._lib.IA_MAX_LEVELS or L != len(self.strides):
+            return False
+        if float(cfg.gamma) != 2.0:
+            return False
+        B = maps[0][0].size(0)
+        if not 1 <= B <= fcos_ops._lib.IA_MAX_TARGET_BATCH or len(gt_bboxes) != B or len(gt_labels) != B:
+            return False
+        for t in [t for m in maps for t in m]:
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+                return False
+        for b, l in zip(gt_bboxes, gt_labels):
+            if not (b.is_cuda and l.is_cuda) or not 1 <= b.size(0) <= 512 or l.size(0) != b.size(0):
+                return False
+        return True
+
     def _loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, cfg):
         """focal classification over (num_pos + num_imgs), the centerness-weighted IoU loss, the
         centerness BCE and, with the IoU branch, the IoU BCE whose target is
@@ -175,6 +199,15 @@ class _FCOSHeadBase(nn.Module):
         maps = (cls_scores, bbox_preds, centernesses) + ((ious,) if self.iou_branch else ())
         if len(set(len(m) for m in maps)) != 1:
             raise AssertionError('level count mismatch')
+        geom = None
+        if self.fuse_loss and self._fused_loss_ok(maps, gt_bboxes, gt_labels, cfg):
+            geom = self.geometry([tuple(c.shape[-2:]) for c in cls_scores])
+        if geom is not None and fcos_ops.point_loss_supported(geom, cls_scores[0].size(0)):
+            labels, bbox_targets, counts = fcos_ops.point_targets(geom, gt_bboxes, gt_labels,
+                                                                  self.regress_ranges)
+            return fcos_ops.point_head_loss(geom, cls_scores, bbox_preds, centernesses,
+                                            ious if self.iou_branch else None, labels,
+                                            bbox_targets, counts, cfg.gamma, cfg.alpha)
         featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores]
         all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device)
         labels, bbox_targets = self.fcos_target(all_level_points, gt_bboxes, gt_labels)

@@ -1,16 +1,17 @@
-"""torch front-end of the FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip): the point
-heads' post-conv paths (ia_point_get_bboxes: IoU-aware; ia_point_ctr_get_bboxes: plain FCOS, the
-centerness map in the third slot) and the towers' GroupNorm + ReLU.
+"""torch front-end of the FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip,
+csrc/pointloss.hip): the point heads' post-conv paths (ia_point_get_bboxes: IoU-aware;
+ia_point_ctr_get_bboxes: plain FCOS, the centerness map in the third slot), the towers'
+GroupNorm + ReLU, and the training side: point targets and the all-levels loss node.
 Device tensors only, launched on the current torch stream, like ops.py."""
 import ctypes as C
 
 import torch
 
 from . import _lib
-from ._lib import LevelPtrs, PointHeadGeom
+from ._lib import LevelPtrs, PointHeadGeom, PointLevelPtrs
 from . import winograd
-from .ops import (_LayoutTwin, _det_outputs, _meta_tensors, _ptr, _require_gpu, _state_workspace,
-                  _stream, _ws_views, stream_id, to_nchw)
+from .ops import (_LayoutTwin, _det_outputs, _meta_tensors, _own_workspace, _ptr, _require_gpu,
+                  _state_workspace, _stream, _ws_views, _zero1, stream_id, to_nchw)
 
 
 class PointGeometry(_LayoutTwin):
@@ -183,3 +184,150 @@ def groupnorm_relu_(xs, gamma, beta, groups, eps=1e-5, relu=True):
                                     float(eps), int(bool(relu)), _ptr(ws), nbytes, _stream()),
                'ia_groupnorm_apply')
     return xs
+
+
+# ------------------------------------------------------------------ training
+class PackedLabels(list):
+    """per-level int64 label views (B, N_l) of point_targets, plus `.packed`: the int32 copy the
+    loss node's focal kernel reads, written by the same launch"""
+    packed = None
+
+
+def point_loss_supported(geom, batch):
+    """whether the training kernels cover this geometry and batch (level sizes whose packed labels
+    the focal kernel can read in 16-byte pieces)"""
+    g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
+    return _lib.lib().ia_point_head_loss_workspace_bytes(g.ref(), int(batch)) != 0
+
+
+def point_targets(geom, gt_bboxes, gt_labels, regress_ranges):
+    """fcos_target for a batch in one launch (ia_point_targets_ptrs).  gt_bboxes: list of (G_i, 4)
+    device tensors, gt_labels: list of (G_i,) int64 tensors, 1 <= G_i <= 512, at most
+    IA_MAX_TARGET_BATCH images; regress_ranges: L pairs (lo, hi).  -> (labels[L] (B, N_l) int64,
+    bbox_targets[L] (B, N_l, 4) fp32, counts (B,) int32 positives per image): views of one
+    allocation each, on the device, no host sync."""
+    B = len(gt_bboxes)
+    if B < 1 or len(gt_labels) != B:
+        raise ValueError('one gt_labels tensor per image')
+    for t in list(gt_bboxes) + list(gt_labels):
+        _require_gpu(t, 'gt_bboxes / gt_labels')
+    if len(regress_ranges) != geom.L:
+        raise ValueError('one regress range per level')
+    dev = gt_bboxes[0].device
+    sizes = [int(g_.shape[0]) for g_ in gt_bboxes]
+    L_ = _lib.lib()
+    g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
+    n_packed = L_.ia_point_packed_labels_elems(g.ref(), B)
+    if n_packed == 0 or B > _lib.IA_MAX_TARGET_BATCH or min(sizes) < 1 or max(sizes) > 512:
+        raise _lib.IouAwareLibraryError(
+            'ia_point_targets_ptrs: unsupported geometry, batch %d (1..%d) or gts per image %d..%d '
+            '(1..512)' % (B, _lib.IA_MAX_TARGET_BATCH, min(sizes), max(sizes)))
+    keep = [g_.to(dev, torch.float32).contiguous() for g_ in gt_bboxes]
+    keep_l = [l_.to(dev, torch.int64).contiguous() for l_ in gt_labels]
+    gp = (C.c_void_p * B)(*[g_.data_ptr() for g_ in keep])
+    lp = (C.c_void_p * B)(*[l_.data_ptr() for l_ in keep_l])
+    ng = (C.c_int32 * B)(*sizes)
+    rr = (C.c_float * (2 * geom.L))(*[float(v) for r in regress_ranges for v in r])
+    N = geom.N
+    labels = torch.empty(B * N, dtype=torch.int64, device=dev)
+    bt = torch.empty(B * N * 4, dtype=torch.float32, device=dev)
+    packed = torch.empty(int(n_packed), dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(L_.ia_point_targets_ptrs(g.ref(), gp, lp, ng, B, rr, _ptr(labels), _ptr(bt),
+                                        _ptr(packed), _ptr(counts), _stream()),
+               'ia_point_targets_ptrs')
+    out_l, out_t = PackedLabels(), []
+    off = 0
+    for n_l in geom.level_points:
+        out_l.append(labels[B * off:B * (off + n_l)].view(B, n_l))
+        out_t.append(bt[4 * B * off:4 * B * (off + n_l)].view(B, n_l, 4))
+        off += n_l
+    out_l.packed = packed
+    return out_l, out_t, counts
+
+
+class _PointHeadLossFn(torch.autograd.Function):
+    """the three / four FCOS losses of every level (csrc/pointloss.hip): 3 launches forward (4
+    without packed labels), 2 backward.  Outputs: four (1,) views of one result vector
+    (loss_cls, loss_reg, loss_centerness, loss_iou)."""
+
+    @staticmethod
+    def forward(ctx, geom, targets, cfg, with_iou, *outs):
+        L = geom.L
+        if len(outs) != (4 if with_iou else 3) * L:
+            raise AssertionError('expected %d head outputs' % ((4 if with_iou else 3) * L))
+        for t in outs:
+            _require_gpu(t, 'head output')
+            if t.dtype != torch.float32:
+                raise TypeError('the point-head loss takes fp32 head outputs')
+        maps = [[t.contiguous() for t in outs[k * L:(k + 1) * L]] for k in range(len(outs) // L)]
+        B, dev = maps[0][0].shape[0], maps[0][0].device
+        for l in range(L):
+            h, w = geom.featmap_sizes[l]
+            for m, ch in zip(maps, (geom.C, 4, 1, 1)):
+                if tuple(m[l].shape) != (B, ch, h, w):
+                    raise AssertionError('level %d: head output of shape %s, expected %s'
+                                         % (l, tuple(m[l].shape), (B, ch, h, w)))
+        labels, bbox_targets, counts = targets
+        packed = getattr(labels, 'packed', None)
+        labels = [t.contiguous().to(torch.int64) for t in labels]
+        bbox_targets = [t.contiguous().to(torch.float32) for t in bbox_targets]
+        for t in labels + bbox_targets:
+            _require_gpu(t, 'targets')
+        p, pt = PointLevelPtrs(), _lib.PointTargets()
+        for l in range(L):
+            p.cls[l], p.reg[l], p.ctr[l] = (m[l].data_ptr() for m in maps[:3])
+            p.iou[l] = maps[3][l].data_ptr() if with_iou else None
+            pt.labels[l], pt.bbox_targets[l] = labels[l].data_ptr(), bbox_targets[l].data_ptr()
+        pt.packed = packed.data_ptr() if packed is not None else None
+        pt.counts = counts.data_ptr() if counts is not None else None
+        pc = _lib.PointLossCfg(*cfg)
+        g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
+        nbytes = _lib.lib().ia_point_head_loss_workspace_bytes(g.ref(), B)
+        if nbytes == 0:
+            raise _lib.IouAwareLibraryError('unsupported geometry / batch for ia_point_head_loss')
+        # own buffer: it carries the normalisers (and packed labels) from forward to backward
+        ws = _own_workspace(dev, nbytes)
+        res = torch.empty(6, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().ia_point_head_loss_fwd(g.ref(), C.byref(p), B, C.byref(pt),
+                                                     C.byref(pc), _ptr(ws), nbytes, _ptr(res),
+                                                     _stream()), 'ia_point_head_loss_fwd')
+        ctx.ws, ctx.res, ctx.geom, ctx.cfg, ctx.B = ws, res, g, pc, B
+        ctx.keep = (maps, p, pt, (labels, bbox_targets, counts, packed))
+        ctx.set_materialize_grads(False)
+        return tuple(res[:4].view(4, 1).unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        maps, p, pt, _ = ctx.keep
+        L, dev = ctx.geom.L, maps[0][0].device
+        z = _zero1(dev)
+        gin = torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
+        grads = [[torch.empty(t.shape, dtype=torch.float32, device=dev) for t in m] for m in maps]
+        gp = PointLevelPtrs()
+        for l in range(L):
+            gp.cls[l], gp.reg[l], gp.ctr[l] = (m[l].data_ptr() for m in grads[:3])
+            gp.iou[l] = grads[3][l].data_ptr() if len(grads) == 4 else None
+        _lib.check(_lib.lib().ia_point_head_loss_bwd(ctx.geom.ref(), C.byref(p), ctx.B,
+                                                     C.byref(pt), C.byref(ctx.cfg), _ptr(ctx.ws),
+                                                     _ptr(ctx.res), _ptr(gin), C.byref(gp),
+                                                     _stream()), 'ia_point_head_loss_bwd')
+        return (None, None, None, None) + tuple(g for m in grads for g in m)
+
+
+def point_head_loss(geom, cls, reg, ctr, iou, labels, bbox_targets, counts, gamma=2.0, alpha=0.25,
+                    attach_iou_target=True, exact_large_logits=False):
+    """Loss of the FCOS heads for all levels (ia_point_head_loss_*).  cls / reg / ctr / iou: per-level
+    fp32 NCHW device tensors (reg = the exponentiated distances; iou = None: plain FCOS); labels /
+    bbox_targets / counts as point_targets returns them (counts may be None).  -> dict of (1,)
+    tensors with the reference's keys loss_cls, loss_reg, loss_centerness [, loss_iou]."""
+    with_iou = iou is not None
+    outs = list(cls) + list(reg) + list(ctr) + (list(iou) if with_iou else [])
+    for t in outs:
+        _require_gpu(t, 'head output')
+    cfg = (float(gamma), float(alpha), int(bool(attach_iou_target)), int(bool(exact_large_logits)))
+    res = _PointHeadLossFn.apply(geom, (labels, bbox_targets, counts), cfg, with_iou, *outs)
+    losses = dict(loss_cls=res[0], loss_reg=res[1], loss_centerness=res[2])
+    if with_iou:
+        losses['loss_iou'] = res[3]
+    return losses
