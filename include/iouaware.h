@@ -316,6 +316,15 @@ int ia_wino_input_transform(const ia_wino_geom *g, const float *const *x, int ch
 int ia_wino_output_transform(const ia_wino_geom *g, const float *M, int channels, int groups,
                              const float *bias, int relu, int nseg, const ia_wino_seg *segs,
                              void *stream);
+/* Output transform of a layer and input transform of the next 3x3 convolution of the SAME
+ * geometry in one launch: V = B^T relu?(A^T M A + bias) B per tile, the activation in between
+ * (zero outside the feature maps) stays on chip.  M (groups_m*36, T, C/groups_m) -> V
+ * (groups_v*36, T, C/groups_v): the bits that ia_wino_output_transform(groups_m) into a
+ * (B, H_l, W_l, channels) tensor per level followed by ia_wino_input_transform(groups_v) of those
+ * tensors gives.  C/groups_m % 32 == 0, C/groups_v % 32 == 0; M, V, bias 16-byte aligned; V must
+ * not overlap M.                                                                              */
+int ia_wino_mid_transform(const ia_wino_geom *g, const float *M, int channels, int groups_m,
+                          const float *bias, int relu, float *V, int groups_v, void *stream);
 
 /* Training: gradient of the output transform, dM = A dY A^T per tile (dY (B,H,W,channels)
  * channels-last per level, zero outside the map), written as 36 matrices (36, tiles, channels)

@@ -14,7 +14,10 @@
 //   batched GEMM              M[k] = V[k] (tiles x Cin) . U[k] (Cin x Cout), 36 (x groups) plain
 //                             fp32 GEMMs -> rocBLAS / hipBLASLt through torch.bmm (library GEMM);
 //   k_wino_out  (this file)   Y = A^T M A (4x4 outputs per tile) + bias (+ ReLU), written straight
-//                             into the channels-last activation / head-output tensors.
+//                             into the channels-last activation / head-output tensors;
+//   k_wino_mid  (this file)   k_wino_out of a layer and k_wino_in of the next layer of the same
+//                             geometry in one launch (the head's tower transitions): the
+//                             activation in between stays in LDS.
 // Activations are channels-last fp32: a wavefront handles one tile x 256 channels, 16 bytes per
 // lane, so every load / store instruction moves one contiguous 1 KiB pixel row.  Both kernels
 // are HBM-bound streams (36 x 16 B in, 36 x 16 B out per lane; 36 in, 16 out).
@@ -338,6 +341,148 @@ __global__ void __launch_bounds__(64) k_wino_out(WinoOutArgs a)
     }
 }
 
+// ---- Output transform of one tower layer and input transform of the next in ONE launch: the
+// bias + ReLU activation between two 3x3 convolutions of the same geometry never goes to HBM.
+// k_wino_out writes 16 pixels per tile and channel and k_wino_in reads them back as overlapping
+// 6x6 patches (36 issued loads per tile): 36 + 36 load and 16 + 36 store units per tile for the
+// pair.  Here a workgroup owns a block of 8 x 8 tiles of one (level, image) and a slice of 32
+// channels (128-byte pieces of M and V):
+//   phase 1  M of the block and of a one-tile ring around it (clipped to the tile grid) ->
+//            Y = A^T M A + bias, ReLU -> the 34 x 34 pixel window of the activation in LDS; pixels
+//            outside the feature map are the ZERO PADDING of the input transform, not what
+//            A^T M A gives there (partial tiles);
+//   phase 2  every tile of the block takes its 6x6 patch from LDS -> V = B^T d B.
+// 36 * (10/8)^2 = 56 load and 36 store units per tile.  The arithmetic is that of k_wino_out
+// followed by k_wino_in, expression by expression: V has the same bits.
+constexpr int kMidB = 8;                              // tiles per side of a block
+constexpr int kMidR = kMidB + 2;                      // ... with the ring
+constexpr int kMidP = 4 * kMidB + 2;                  // pixels per side of the activation window
+constexpr int kMidCh = 32;                            // channels per workgroup
+constexpr int kMidQ = kMidCh / 4;                     // lanes (channel quads) per tile
+constexpr int kMidThreads = kMidB * kMidB * kMidQ;    // 512: one lane per (tile, quad) of phase 2
+constexpr int kMidPasses = (kMidR * kMidR * kMidQ + kMidThreads - 1) / kMidThreads;
+
+struct WinoMidArgs {
+    WinoLevels lv;
+    const float *M;                       // (groups_m * 36, T, Cm)
+    const float *bias;                    // (Ctot) or NULL
+    float *V;                             // (groups_v * 36, T, Cv)
+    int32_t bx[IA_MAX_LEVELS], bpi[IA_MAX_LEVELS];        // blocks per row of blocks / per image
+    int32_t blk_off[IA_MAX_LEVELS + 1];                   // prefix of B * blocks_per_image
+    int32_t nblk, Ctot, Cm, Cv, T, relu;
+};
+
+__global__ void __launch_bounds__(kMidThreads) k_wino_mid(WinoMidArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float s_y[kMidP * kMidP * kMidCh];     // 144.5 KiB
+    const int tid = threadIdx.x;
+    const int blk = __builtin_amdgcn_readfirstlane(xcd_tile(blockIdx.x, a.nblk));
+    if (blk >= a.nblk) return;                            // the whole workgroup
+    // block -> level, image, block row / column (workgroup-uniform: scalar compares and selects)
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) l += (i < a.lv.L && blk >= a.blk_off[i]) ? 1 : 0;
+    int off = a.blk_off[0], bpi = a.bpi[0], bx = a.bx[0], tx = a.lv.tx[0], tpi = a.lv.tpi[0],
+        toff = a.lv.tile_off[0], H = a.lv.H[0], W = a.lv.W[0];
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) {
+        const bool m = l == i;
+        off = m ? a.blk_off[i] : off; bpi = m ? a.bpi[i] : bpi; bx = m ? a.bx[i] : bx;
+        tx = m ? a.lv.tx[i] : tx; tpi = m ? a.lv.tpi[i] : tpi; toff = m ? a.lv.tile_off[i] : toff;
+        H = m ? a.lv.H[i] : H; W = m ? a.lv.W[i] : W;
+    }
+    const int qb = blk - off;
+    const int b = qb / bpi, rb = qb - b * bpi;
+    const int byi = rb / bx, bxi = rb - byi * bx;
+    const int ty_n = tpi / tx;
+    const int tbase = toff + b * tpi;                     // first tile of this image
+    const int cq = (tid & (kMidQ - 1)) * 4;
+    const int c = blockIdx.y * kMidCh + cq;
+    // the channel -> group mapping of M (the layer behind) and of V (the layer in front) may differ:
+    // the first tower layer is one GEMM with 2F columns, the second 2 x 36 GEMMs of F
+    const int gm = c / a.Cm, gv = c / a.Cv;
+    const size_t mstride = (size_t)a.T * a.Cm, vstride = (size_t)a.T * a.Cv;
+    float4 bz = f4(0.0f);
+    if (a.bias) bz = *reinterpret_cast<const float4 *>(a.bias + c);
+
+    // ---- phase 1: lane = (tile of the ringed block, channel quad)
+#pragma unroll 1
+    for (int p = 0; p < kMidPasses; ++p) {
+        const int ti = tid / kMidQ + p * (kMidThreads / kMidQ);
+        if (ti >= kMidR * kMidR) break;
+        const int ry = ti / kMidR, rx = ti - ry * kMidR;
+        const int tyi = kMidB * byi - 1 + ry, txi = kMidB * bxi - 1 + rx;
+        const int ly0 = 4 * ry - 3, lx0 = 4 * rx - 3;     // window coordinates of the tile's first pixel
+        float *sy = s_y + cq;
+        if (tyi >= 0 && tyi < ty_n && txi >= 0 && txi < tx) {
+            const float *m = a.M + (size_t)gm * 36 * mstride + (size_t)(tbase + tyi * tx + txi) * a.Cm + (c - gm * a.Cm);
+            float4 s[4][6];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {                 // columns: s = A^T m
+                float4 col[6], o[4];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) col[i] = *reinterpret_cast<const float4 *>(m + (size_t)(i * 6 + j) * mstride);
+                at6(col, o);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[i][j] = o[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                 // rows: Y = s A
+                float4 o[4];
+                at6(s[i], o);
+                const int y = 4 * tyi + i, ly = ly0 + i;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int xx = 4 * txi + j, lx = lx0 + j;
+                    float4 v = o[j] + bz;
+                    if (a.relu) v = make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f,
+                                                v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
+                    v = (y < H && xx < W) ? v : f4(0.0f); // a partial tile: padding of the next layer
+                    if (ly >= 0 && ly < kMidP && lx >= 0 && lx < kMidP)
+                        *reinterpret_cast<float4 *>(sy + (ly * kMidP + lx) * kMidCh) = v;
+                }
+            }
+        } else {                                          // no such tile: padding
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ly = ly0 + i, lx = lx0 + j;
+                    if (ly >= 0 && ly < kMidP && lx >= 0 && lx < kMidP)
+                        *reinterpret_cast<float4 *>(sy + (ly * kMidP + lx) * kMidCh) = f4(0.0f);
+                }
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: lane = (tile of the block, channel quad)
+    const int tl = tid / kMidQ, tyl = tl / kMidB, txl = tl - tyl * kMidB;
+    const int tyi = kMidB * byi + tyl, txi = kMidB * bxi + txl;
+    if (tyi >= ty_n || txi >= tx) return;                 // a partial block: no tile here
+    const float *sp = s_y + ((4 * tyl) * kMidP + 4 * txl) * kMidCh + cq;
+    float4 tmp[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {                         // columns: tmp = B^T d
+        float4 col[6], o[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) col[i] = *reinterpret_cast<const float4 *>(sp + (i * kMidP + j) * kMidCh);
+        bt6(col, o);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) tmp[i][j] = o[i];
+        // (left alone the scheduler hoists all 36 LDS reads next to tmp: 288 registers)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    float *v = a.V + (size_t)gv * 36 * vstride + (size_t)(tbase + tyi * tx + txi) * a.Cv + (c - gv * a.Cv);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {                         // rows: V = tmp B
+        float4 o[6];
+        bt6(tmp[i], o);
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            *reinterpret_cast<float4 *>(v + (size_t)(i * 6 + j) * vstride) = o[j];
+    }
+}
+
 }  // namespace ia
 
 extern "C" {
@@ -429,6 +574,38 @@ int ia_wino_output_transform(const ia_wino_geom *g, const float *M, int channels
     dim3 grid((unsigned)((waves + 7) / 8 * 8), (unsigned)((channels / 4 + 63) / 64));
     if (a.tpw > 1) hipLaunchKernelGGL(ia::k_wino_out<true>, grid, dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ia::k_wino_out<false>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+int ia_wino_mid_transform(const ia_wino_geom *g, const float *M, int channels, int groups_m,
+                          const float *bias, int relu, float *V, int groups_v, void *stream)
+{
+    ia::WinoMidArgs a;
+    int rc = ia::make_wino_levels(g, a.lv);
+    if (rc) return rc;
+    if (!M || !V || channels < ia::kMidCh || groups_m < 1 || channels % groups_m || groups_v < 1 ||
+        channels % groups_v)
+        return IA_E_ARG;
+    a.M = M; a.bias = bias; a.V = V; a.Ctot = channels;
+    a.Cm = channels / groups_m; a.Cv = channels / groups_v;
+    // a workgroup's 32 channels lie inside one group on both sides; 128-byte pieces of M and V
+    if (a.Cm % ia::kMidCh || a.Cv % ia::kMidCh || ((uintptr_t)M & 15u) || ((uintptr_t)V & 15u) ||
+        ((uintptr_t)bias & 15u))
+        return IA_E_ARG;
+    a.T = a.lv.tile_off[a.lv.L]; a.relu = relu ? 1 : 0;
+    int64_t n = 0;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < a.lv.L;
+        const int ty = on ? a.lv.tpi[l] / a.lv.tx[l] : 0;
+        a.bx[l] = on ? (a.lv.tx[l] + ia::kMidB - 1) / ia::kMidB : 0;
+        a.bpi[l] = on ? ((ty + ia::kMidB - 1) / ia::kMidB) * a.bx[l] : 0;
+        a.blk_off[l] = (int32_t)n;
+        n += (int64_t)a.lv.B * a.bpi[l];
+    }
+    a.blk_off[IA_MAX_LEVELS] = (int32_t)n;
+    a.nblk = (int32_t)n;
+    dim3 grid((unsigned)((n + 7) / 8 * 8), (unsigned)(channels / ia::kMidCh));
+    hipLaunchKernelGGL(ia::k_wino_mid, grid, dim3(ia::kMidThreads), 0, (hipStream_t)stream, a);
     return ia::hip_status(hipGetLastError());
 }
 

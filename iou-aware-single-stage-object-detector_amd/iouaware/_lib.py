@@ -162,6 +162,7 @@ SIGNATURES = {
     'ia_relu_bwd_bias_grad': (_i, [_vp, _vp, C.c_int64, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     'ia_wino_output_transform': (_i, [C.POINTER(WinoGeom), _vp, _i, _i, _vp, _i, _i,
                                       C.POINTER(WinoSeg), _vp]),
+    'ia_wino_mid_transform': (_i, [C.POINTER(WinoGeom), _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     'ia_linear_bias_act': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_linear_bias_act_bf16': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_batched_gemm': (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _sz, _vp]),

@@ -5,6 +5,7 @@ retina_reg, retina_iou) and of the FPN output convolutions (fpn.py:124-127).
     activations (channels-last, all five levels)  --k_wino_in-->   V  (36 matrices tiles x Cin)
     V . U   (36 [x2 towers] plain fp32 GEMMs: hipBLASLt, strided batched, csrc/gemm.hip)    -->  M
     M  --k_wino_out (+bias, +ReLU)-->  next activations / the head outputs, channels-last
+    M  --k_wino_mid (+bias, +ReLU)-->  V of the next tower layer (bias + ReLU towers: no activation tensor)
 
 The head's weights are shared by the pyramid levels, so every layer is ONE batched GEMM over the
 tiles of all levels; the two towers run side by side (first layer: one GEMM with 512 output
@@ -167,6 +168,21 @@ def output_transform(plan, m, channels, groups, bias, relu, segments):
                                             _stream()), 'ia_wino_output_transform'))
 
 
+MID_CHANNELS = 32     # ia_wino_mid_transform: channels per group in multiples of this
+
+
+def mid_transform(plan, m, channels, groups_m, bias, relu, out, groups_v):
+    """V (groups_v * 36, T, C / groups_v) of the next 3x3 convolution of the same geometry straight
+    from this layer's M (groups_m * 36, T, C / groups_m): the bits of output_transform (+bias,
+    +ReLU) into activation tensors followed by input_transform of them, without the activation's
+    trip through HBM.  Bytes: M read + V written (36 + 36 per tile)."""
+    _timed('mid', plan.T * int(channels) * 4 * (36 + 36), lambda: _lib.check(
+        _lib.lib().ia_wino_mid_transform(C.byref(plan.geom), _ptr(m), int(channels), int(groups_m),
+                                         _ptr(bias), int(bool(relu)), _ptr(out), int(groups_v),
+                                         _stream()), 'ia_wino_mid_transform'))
+    return out
+
+
 _LT_WS_BYTES = 128 << 20
 
 
@@ -260,7 +276,12 @@ class _WinogradTowers(object):
     """the two conv towers of a head, all levels at once: layer 0 one GEMM with 2F output columns
     on the shared input, layers 1..n-1 72 matrices (cls tower = channels [0,F), reg tower =
     [F,2F)), activations ping-pong between the plan's 'a' / 'b' sets.  A subclass supplies the
-    layer epilogue (`_layer_out`) and the output convolutions behind `_towers`."""
+    layer epilogue (`_layer_out`) and the output convolutions behind `_towers`.  Where that epilogue
+    is plain bias + ReLU the subclass sets `mid_bias` (per layer (2F,)) and the activations between
+    the layers stay on chip: `mid_transform` instead of `_layer_out` + `input_transform`."""
+
+    FUSE_MID = True       # False: the two-launch route (tests compare the two bit for bit)
+    mid_bias = None
 
     def __init__(self, head):
         convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
@@ -291,6 +312,20 @@ class _WinogradTowers(object):
         # layer 0
         v = input_transform(plan, feats, 1, plan.buf('v', (36, T, self.cin)))
         m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)))
+        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=dev,  # noqa: E731
+                                     memory_format=torch.channels_last) for (h, w) in sizes]
+        if self.FUSE_MID and self.mid_bias is not None and F % MID_CHANNELS == 0:
+            # plain bias + ReLU layers: M of a layer -> V of the next in one launch; the ping-pong
+            # activation tensors are not touched (layer 0's M is ONE group of 2F columns)
+            groups = 1
+            for i, u in enumerate(self.u):
+                v = mid_transform(plan, m, 2 * F, groups, self.mid_bias[i], True,
+                                  plan.buf('v', (72, T, F)), 2)
+                m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
+                groups = 2
+            v = mid_transform(plan, m, 2 * F, groups, self.mid_bias[self.n_layers - 1], True,
+                              plan.buf('v', (72, T, F)), 2)
+            return plan, v, new
         acts = plan.acts('a', 2 * F)
         self._layer_out(plan, m, 1, 0, acts)
         # layers 1..n-1: groups = 2
@@ -301,8 +336,6 @@ class _WinogradTowers(object):
             self._layer_out(plan, m, 2, i + 1, nxt)
             acts = nxt
         v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
-        new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=dev,  # noqa: E731
-                                     memory_format=torch.channels_last) for (h, w) in sizes]
         return plan, v, new
 
     @staticmethod
@@ -331,6 +364,7 @@ class WinogradHead(_WinogradTowers):
 
         # per layer: the two towers' biases side by side (2F,)
         self.b = [torch.cat([bias(mc), bias(mr)]).contiguous() for mc, mr in zip(convs_c, convs_r)]
+        self.mid_bias = self.b
         if head.retina_cls.out_channels % 4:
             raise ValueError('A*C must be a multiple of 4')
         # retina_cls goes in unpadded, reg | iou padded to 16 columns
