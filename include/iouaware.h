@@ -785,6 +785,43 @@ int ia_groupnorm_stats(const ia_wino_geom *g, const float *const *x, int channel
 int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int groups,
                        const float *gamma, const float *beta, float eps, int relu,
                        const void *workspace, size_t workspace_bytes, void *stream);
+/* The same GroupNorm + ReLU as a training node, out of place (csrc/groupnorm.hip).  Forward:
+ * ia_groupnorm_stats on x, then
+ *   ia_groupnorm_apply_to: y[l] = relu?(x[l] * s + t), the bits ia_groupnorm_apply leaves in x;
+ *     x is only read, y[l] != x[l].  saved (ia_groupnorm_saved_bytes, caller-owned) receives
+ *     (mean, rstd) in fp64 per (level, image, group): with x, all the backward needs.
+ * Backward, with xh = (x - mean) * rstd, g = dy * [x * s + t > 0] (the forward's fp32 expression,
+ * so the forward's mask bit for bit; g = dy with relu == 0), n = channels / groups * H_l * W_l:
+ *     dbeta_c = sum g,  dgamma_c = sum g * xh   over all pixels, images and levels
+ *     dx = rstd * (gamma * g - mean_grp(gamma * g) - xh * mean_grp(gamma * g * xh))
+ *   ia_groupnorm_bwd_reduce: per workgroup (level, image, chunk) fp64 partials of the two sums per
+ *     channel and, weighted by gamma, per group, to workspace (ia_groupnorm_bwd_workspace_bytes).
+ *   ia_groupnorm_bwd_apply: adds the group partials of a (level, image) in chunk order and writes
+ *     dx[l] (dx == NULL: skipped; dx[l] != dy[l], x[l]); then adds the per-channel partials in a
+ *     fixed order (16 contiguous runs of the level-major / image / chunk rows, each in index order,
+ *     then the runs in index order) into dgamma / dbeta (channels) fp32, either may be NULL.
+ * dy and x are only read.  No atomics: same bits from run to run, and an image's y and dx do not
+ * depend on the other images / levels of the launch.  relu, gamma and beta as in the forward call.
+ * All five entries: channels a power of two, 4 <= channels <= 1024; 1 <= groups <= 256, groups
+ * divides channels and channels / groups % 4 == 0; x[l], y[l], dy[l], dx[l], saved and workspace
+ * 16-byte aligned; the calls of a forward, and those of a backward, on one stream with the
+ * workspace untouched in between.  The size queries return 0 for what the kernels do
+ * not cover.                                                                                  */
+size_t ia_groupnorm_saved_bytes(const ia_wino_geom *g, int channels, int groups);
+int ia_groupnorm_apply_to(const ia_wino_geom *g, const float *const *x, float *const *y,
+                          int channels, int groups, const float *gamma, const float *beta,
+                          float eps, int relu, const void *workspace, size_t workspace_bytes,
+                          void *saved, size_t saved_bytes, void *stream);
+size_t ia_groupnorm_bwd_workspace_bytes(const ia_wino_geom *g, int channels, int groups);
+int ia_groupnorm_bwd_reduce(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                            int channels, int groups, const float *gamma, const float *beta,
+                            int relu, const void *saved, size_t saved_bytes, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                           float *const *dx, int channels, int groups, const float *gamma,
+                           const float *beta, int relu, const void *saved, size_t saved_bytes,
+                           const void *workspace, size_t workspace_bytes, float *dgamma,
+                           float *dbeta, void *stream);
 /* The FCOS regression epilogue bbox_pred = exp(scale_l * x) (iou_aware_fcos_head.py:105) in place
  * on per-level (batch, H_l, W_l, channels) fp32 tensors (channels % 4 == 0, 16-byte aligned);
  * scales: (num_levels) fp32 device array (the head's Scale parameters).                      */

@@ -1,6 +1,7 @@
-// GroupNorm + ReLU of the IoU-aware FCOS head towers at inference (reference
+// GroupNorm + ReLU of the IoU-aware FCOS head towers (reference
 // mmdet/models/anchor_heads/iou_aware_fcos_head.py:41-62, ConvModule(3x3, GN(32), ReLU); torch
-// nn.GroupNorm semantics: biased variance, eps inside the square root).
+// nn.GroupNorm semantics: biased variance, eps inside the square root): the in-place inference pair,
+// and further down the out-of-place forward and the backward of the training node.
 //
 // Input: the activations the Winograd output transform writes, per level (B, H_l, W_l, channels)
 // fp32 channels-last; all levels and images of a tower layer in one pair of launches.
@@ -184,6 +185,337 @@ static int gn_args(const ia_wino_geom *g, int channels, int groups, GnArgs &a)
     return 0;
 }
 
+// ------------------------------------------------------------------ training node
+// Out-of-place forward and the backward of y = relu?(GroupNorm(x)) over the same level lists and the
+// same (level, image, chunk) workgroups.  With xh = (x - mean) * rstd, g = dy * [x * s + t > 0]
+// (the forward's fp32 expression: the same mask bit for bit) and n = channels / groups * H_l * W_l:
+//     dbeta_c = sum g,  dgamma_c = sum g * xh  (all pixels, images, levels)
+//     dx = rstd * (gamma * g - mean_grp(gamma * g) - xh * mean_grp(gamma * g * xh))
+//   k_gn_apply_to     k_gn_apply writing y to a second tensor; chunk 0 of every (level, image) also
+//                     leaves (mean, rstd) per group in fp64 for the backward.
+//   k_gn_bwd_reduce   every thread owns a 16-byte column and a strided subset of the chunk's pixels
+//                     and accumulates sum g and sum g * x per channel in fp64 (the product of two
+//                     floats is exact there); the threads of a column are added in a fixed order
+//                     through LDS, sum g * xh = rstd * (sum g * x - mean * sum g), and the workgroup
+//                     writes (sum g, sum g * xh) per channel and, weighted by gamma and added over a
+//                     group's channels in index order, per group to its own workspace rows.
+//   k_gn_bwd_apply    the first `groups` threads add the group partials of the (level, image) over
+//                     its chunks in index order; dx = s * g + (c1 + xc * c2) per element with
+//                     s = gamma * rstd as in the forward, c1 = -rstd * m1, c2 = -rstd^2 * m2 and
+//                     xc = (x - mean_hi) - mean_lo: the mean as two floats, so that |mean| >> std
+//                     costs nothing (x - mean_hi is exact there).
+//   k_gn_bwd_params   per channel the (sum g, sum g * xh) rows in a fixed order: kGnSeg contiguous
+//                     runs of rows (level-major / image / chunk), each in index order by one thread,
+//                     then the runs in index order.
+// No atomics; dy is only read; an image's dx depends on its own pixels only.
+struct GnTrainArgs {
+    int32_t num_levels, batch, channels, groups;
+    int32_t HW[IA_MAX_LEVELS];
+    int32_t nch[IA_MAX_LEVELS];
+    int32_t blk_off[IA_MAX_LEVELS + 1];
+    const float *x[IA_MAX_LEVELS];
+    const float *dy[IA_MAX_LEVELS];             // backward only
+    float *out[IA_MAX_LEVELS];                  // y (forward) / dx (backward apply)
+    const float *gamma, *beta;
+    float eps;
+    int32_t relu;
+    const double2 *part;                        // forward: the (sum, sumsq) rows of k_gn_stats
+    double2 *saved;                             // (num_levels * batch, groups) (mean, rstd)
+    double2 *gpart;                             // (slab rows, groups)   (sum gamma g, sum gamma g xh)
+    double2 *cpart;                             // (slab rows, channels) (sum g, sum g xh)
+};
+
+struct GnTrainBlock { int l, b, chunk, HW, nch, row0; const float *x, *dy; float *out; };
+
+template <bool kBwd>
+__device__ __forceinline__ GnTrainBlock gn_train_block(const GnTrainArgs &a, int blk)
+{
+    GnTrainBlock k;
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) l += (i < a.num_levels && blk >= a.blk_off[i]) ? 1 : 0;
+    k.l = l;
+    k.HW = a.HW[0]; k.nch = a.nch[0];
+    int off = a.blk_off[0];
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) {
+        const bool m = l == i;
+        k.HW = m ? a.HW[i] : k.HW; k.nch = m ? a.nch[i] : k.nch;
+        off = m ? a.blk_off[i] : off;
+    }
+    k.x = a.x[0];
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) k.x = (l == i) ? a.x[i] : k.x;
+    k.dy = nullptr;
+    if (kBwd) {
+        k.dy = a.dy[0];
+#pragma unroll
+        for (int i = 1; i < IA_MAX_LEVELS; ++i) k.dy = (l == i) ? a.dy[i] : k.dy;
+    }
+    k.out = a.out[0];
+#pragma unroll
+    for (int i = 1; i < IA_MAX_LEVELS; ++i) k.out = (l == i) ? a.out[i] : k.out;
+    const int rem = blk - off;
+    k.b = rem / k.nch;
+    k.chunk = rem - k.b * k.nch;
+    k.row0 = off + k.b * k.nch;
+    return k;
+}
+
+// per channel s = gamma * rstd, t = beta - mean * s: fp64, rounded once (k_gn_apply's expression)
+__device__ __forceinline__ void gn_scale_shift(const float *gamma, const float *beta, int v,
+                                               double mean, double rstd, float4 &sc, float4 &sh)
+{
+    float s[4], t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = 4 * v + j;
+        s[j] = (float)((double)gamma[c] * rstd);
+        t[j] = (float)((double)beta[c] - mean * (double)s[j]);
+    }
+    sc = make_float4(s[0], s[1], s[2], s[3]);
+    sh = make_float4(t[0], t[1], t[2], t[3]);
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_apply_to(GnTrainArgs a)
+{
+    __shared__ double s_mean[256], s_rstd[256];
+    __shared__ float4 s_scale[256], s_shift[256];
+    const GnTrainBlock k = gn_train_block<false>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double ts = 0.0, tss = 0.0;
+        const double2 *pp = a.part + (size_t)k.row0 * a.groups + g;
+        for (int c = 0; c < k.nch; ++c) {
+            const double2 q = pp[(size_t)c * a.groups];
+            ts += q.x;
+            tss += q.y;
+        }
+        const double n = (double)k.HW * cpg;
+        const double mean = ts / n;
+        double var = tss / n - mean * mean;
+        var = var > 0.0 ? var : 0.0;
+        const double rstd = 1.0 / sqrt(var + (double)a.eps);
+        s_mean[g] = mean;
+        s_rstd[g] = rstd;
+        if (k.chunk == 0)
+            a.saved[(size_t)(k.l * a.batch + k.b) * a.groups + g] = make_double2(mean, rstd);
+    }
+    __syncthreads();
+    const int vc = a.channels >> 2;
+    for (int v = tid; v < vc; v += kGnThreads) {
+        const int g = (4 * v) / cpg;
+        float4 sc, sh;
+        gn_scale_shift(a.gamma, a.beta, v, s_mean[g], s_rstd[g], sc, sh);
+        s_scale[v] = sc;
+        s_shift[v] = sh;
+    }
+    __syncthreads();
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const float4 sc = s_scale[v], sh = s_shift[v];
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const size_t img = (size_t)k.b * k.HW * a.channels;
+    const float4 *x = reinterpret_cast<const float4 *>(k.x + img) + v;
+    float4 *y = reinterpret_cast<float4 *>(k.out + img) + v;
+    for (int p = p0 + r; p < p1; p += rows) {
+        float4 q = x[(size_t)p * vc];
+        q.x = q.x * sc.x + sh.x;
+        q.y = q.y * sc.y + sh.y;
+        q.z = q.z * sc.z + sh.z;
+        q.w = q.w * sc.w + sh.w;
+        if (a.relu) {
+            q.x = q.x > 0.0f ? q.x : 0.0f;
+            q.y = q.y > 0.0f ? q.y : 0.0f;
+            q.z = q.z > 0.0f ? q.z : 0.0f;
+            q.w = q.w > 0.0f ? q.w : 0.0f;
+        }
+        y[(size_t)p * vc] = q;
+    }
+}
+
+// g = dy where the forward's pre-activation is positive (all of dy without the ReLU)
+__device__ __forceinline__ float4 gn_masked(const float4 q, const float4 d, const float4 sc,
+                                            const float4 sh, int relu)
+{
+    float4 g = d;
+    if (relu) {
+        g.x = (q.x * sc.x + sh.x) > 0.0f ? d.x : 0.0f;
+        g.y = (q.y * sc.y + sh.y) > 0.0f ? d.y : 0.0f;
+        g.z = (q.z * sc.z + sh.z) > 0.0f ? d.z : 0.0f;
+        g.w = (q.w * sc.w + sh.w) > 0.0f ? d.w : 0.0f;
+    }
+    return g;
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_bwd_reduce(GnTrainArgs a)
+{
+    __shared__ double s_acc[8][kGnThreads];     // [2 * j + (0: g, 1: g x)][thread]
+    __shared__ double2 s_ch[1024];              // per channel gamma * (sum g, sum g xh)
+    const GnTrainBlock k = gn_train_block<true>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    const int vc = a.channels >> 2;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const double2 *saved = a.saved + (size_t)(k.l * a.batch + k.b) * a.groups;
+    float4 sc, sh;
+    {
+        const double2 mr = saved[(4 * v) / cpg];
+        gn_scale_shift(a.gamma, a.beta, v, mr.x, mr.y, sc, sh);
+    }
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const size_t img = (size_t)k.b * k.HW * a.channels;
+    const float4 *x = reinterpret_cast<const float4 *>(k.x + img) + v;
+    const float4 *dy = reinterpret_cast<const float4 *>(k.dy + img) + v;
+    double sg[4] = {0.0, 0.0, 0.0, 0.0}, sx[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = p0 + r; p < p1; p += rows) {
+        const float4 q = x[(size_t)p * vc];
+        const float4 g = gn_masked(q, dy[(size_t)p * vc], sc, sh, a.relu);
+        const double g0 = g.x, g1 = g.y, g2 = g.z, g3 = g.w;
+        sg[0] += g0; sg[1] += g1; sg[2] += g2; sg[3] += g3;
+        sx[0] += g0 * (double)q.x; sx[1] += g1 * (double)q.y;
+        sx[2] += g2 * (double)q.z; sx[3] += g3 * (double)q.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s_acc[2 * j][tid] = sg[j];
+        s_acc[2 * j + 1][tid] = sx[j];
+    }
+    __syncthreads();
+    const size_t row = (size_t)(k.row0 + k.chunk);
+    for (int c = tid; c < a.channels; c += kGnThreads) {
+        const int cv = c >> 2, j = c & 3;
+        double tg = 0.0, tx = 0.0;
+        for (int rr = 0; rr < rows; ++rr) {
+            tg += s_acc[2 * j][rr * vc + cv];
+            tx += s_acc[2 * j + 1][rr * vc + cv];
+        }
+        const double2 mr = saved[c / cpg];
+        const double th = mr.y * (tx - mr.x * tg);          // sum g * xh
+        a.cpart[row * a.channels + c] = make_double2(tg, th);
+        const double gm = (double)a.gamma[c];
+        s_ch[c] = make_double2(gm * tg, gm * th);
+    }
+    __syncthreads();
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int j = 0; j < cpg; ++j) {
+            const double2 q = s_ch[g * cpg + j];
+            t1 += q.x;
+            t2 += q.y;
+        }
+        a.gpart[row * a.groups + g] = make_double2(t1, t2);
+    }
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_bwd_apply(GnTrainArgs a)
+{
+    __shared__ double2 s_mr[256];
+    __shared__ float4 s_k[256];                 // per group (mean_hi, mean_lo, c1, c2)
+    const GnTrainBlock k = gn_train_block<true>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    const double2 *saved = a.saved + (size_t)(k.l * a.batch + k.b) * a.groups;
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double t1 = 0.0, t2 = 0.0;
+        const double2 *pp = a.gpart + (size_t)k.row0 * a.groups + g;
+        for (int c = 0; c < k.nch; ++c) {
+            const double2 q = pp[(size_t)c * a.groups];
+            t1 += q.x;
+            t2 += q.y;
+        }
+        const double n = (double)k.HW * cpg;
+        const double2 mr = saved[g];
+        const float mh = (float)mr.x;
+        s_mr[g] = mr;
+        s_k[g] = make_float4(mh, (float)(mr.x - (double)mh), (float)(-mr.y * (t1 / n)),
+                             (float)(-mr.y * mr.y * (t2 / n)));
+    }
+    __syncthreads();
+    const int vc = a.channels >> 2;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const int grp = (4 * v) / cpg;
+    float4 sc, sh;
+    gn_scale_shift(a.gamma, a.beta, v, s_mr[grp].x, s_mr[grp].y, sc, sh);
+    const float4 kk = s_k[grp];
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const size_t img = (size_t)k.b * k.HW * a.channels;
+    const float4 *x = reinterpret_cast<const float4 *>(k.x + img) + v;
+    const float4 *dy = reinterpret_cast<const float4 *>(k.dy + img) + v;
+    float4 *dx = reinterpret_cast<float4 *>(k.out + img) + v;
+    for (int p = p0 + r; p < p1; p += rows) {
+        const float4 q = x[(size_t)p * vc];
+        const float4 g = gn_masked(q, dy[(size_t)p * vc], sc, sh, a.relu);
+        float4 o;
+        o.x = sc.x * g.x + (kk.z + ((q.x - kk.x) - kk.y) * kk.w);
+        o.y = sc.y * g.y + (kk.z + ((q.y - kk.x) - kk.y) * kk.w);
+        o.z = sc.z * g.z + (kk.z + ((q.z - kk.x) - kk.y) * kk.w);
+        o.w = sc.w * g.w + (kk.z + ((q.w - kk.x) - kk.y) * kk.w);
+        dx[(size_t)p * vc] = o;
+    }
+}
+
+constexpr int kGnSeg = 16;                      // runs of rows per channel in k_gn_bwd_params
+
+// one workgroup per 16 channels: thread (seg, c) adds its run of rows in index order
+__global__ void __launch_bounds__(kGnThreads) k_gn_bwd_params(const double2 *cpart, int rows,
+                                                              int channels, float *dgamma,
+                                                              float *dbeta)
+{
+    __shared__ double2 s_p[kGnSeg][16];
+    const int tid = threadIdx.x;
+    const int cl = tid & 15, seg = tid >> 4;
+    const int c = blockIdx.x * 16 + cl;
+    const int per = (rows + kGnSeg - 1) / kGnSeg;
+    const int r0 = seg * per, r1 = min(r0 + per, rows);
+    double tg = 0.0, th = 0.0;
+    if (c < channels)
+        for (int r = r0; r < r1; ++r) {
+            const double2 q = cpart[(size_t)r * channels + c];
+            tg += q.x;
+            th += q.y;
+        }
+    s_p[seg][cl] = make_double2(tg, th);
+    __syncthreads();
+    if (seg == 0 && c < channels) {
+        double ug = 0.0, uh = 0.0;
+        for (int s = 0; s < kGnSeg; ++s) {
+            ug += s_p[s][cl].x;
+            uh += s_p[s][cl].y;
+        }
+        if (dbeta) dbeta[c] = (float)ug;
+        if (dgamma) dgamma[c] = (float)uh;
+    }
+}
+
+static void gn_train_args(const GnArgs &s, GnTrainArgs &a)
+{
+    a.num_levels = s.num_levels; a.batch = s.batch; a.channels = s.channels; a.groups = s.groups;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        a.HW[l] = s.HW[l]; a.nch[l] = s.nch[l]; a.blk_off[l] = s.blk_off[l];
+        a.x[l] = nullptr; a.dy[l] = nullptr; a.out[l] = nullptr;
+    }
+    a.blk_off[IA_MAX_LEVELS] = s.blk_off[IA_MAX_LEVELS];
+    a.gamma = a.beta = nullptr; a.eps = 0.0f; a.relu = 0;
+    a.part = nullptr; a.saved = nullptr; a.gpart = nullptr; a.cpart = nullptr;
+}
+
+static bool gn_level_ptrs(int n, const float *const *p, const float **out)
+{
+    if (!p) return false;
+    for (int l = 0; l < n; ++l) {
+        if (!p[l] || ((uintptr_t)p[l] & 15u)) return false;
+        out[l] = p[l];
+    }
+    return true;
+}
+
 // the FCOS regression epilogue bbox_pred = exp(scale_l * x) (iou_aware_fcos_head.py:105), in place
 // on per-level channels-last tensors; the scales stay on the device (no host read of a parameter)
 struct ScaleExpArgs {
@@ -288,6 +620,116 @@ int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int
     hipLaunchKernelGGL(ia::k_gn_apply, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]), dim3(ia::kGnThreads),
                        0, (hipStream_t)stream, a);
     return ia::hip_status(hipGetLastError());
+}
+
+
+size_t ia_groupnorm_saved_bytes(const ia_wino_geom *g, int channels, int groups)
+{
+    ia::GnArgs a;
+    if (ia::gn_args(g, channels, groups, a)) return 0;
+    return ((size_t)a.num_levels * a.batch * groups * sizeof(double2) + 255) / 256 * 256;
+}
+
+int ia_groupnorm_apply_to(const ia_wino_geom *g, const float *const *x, float *const *y,
+                          int channels, int groups, const float *gamma, const float *beta,
+                          float eps, int relu, const void *workspace, size_t workspace_bytes,
+                          void *saved, size_t saved_bytes, void *stream)
+{
+    ia::GnArgs s;
+    int rc = ia::gn_args(g, channels, groups, s);
+    if (rc) return rc;
+    if (!workspace || !saved || !gamma || !beta || !(eps >= 0.0f)) return IA_E_ARG;
+    if (((uintptr_t)workspace & 15u) || ((uintptr_t)saved & 15u)) return IA_E_ARG;
+    ia::GnTrainArgs a;
+    ia::gn_train_args(s, a);
+    if (!ia::gn_level_ptrs(a.num_levels, x, a.x) ||
+        !ia::gn_level_ptrs(a.num_levels, y, const_cast<const float **>(a.out)))
+        return IA_E_ARG;
+    for (int l = 0; l < a.num_levels; ++l)
+        if (x[l] == y[l]) return IA_E_ARG;             // out of place: ia_groupnorm_apply otherwise
+    if (workspace_bytes < ia_groupnorm_workspace_bytes(g, channels, groups) ||
+        saved_bytes < ia_groupnorm_saved_bytes(g, channels, groups))
+        return IA_E_WORKSPACE;
+    a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu ? 1 : 0;
+    a.part = static_cast<const double2 *>(workspace);
+    a.saved = static_cast<double2 *>(saved);
+    hipLaunchKernelGGL(ia::k_gn_apply_to, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
+                       dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+size_t ia_groupnorm_bwd_workspace_bytes(const ia_wino_geom *g, int channels, int groups)
+{
+    ia::GnArgs a;
+    if (ia::gn_args(g, channels, groups, a)) return 0;
+    const size_t rows = (size_t)a.blk_off[IA_MAX_LEVELS];
+    return (rows * ((size_t)groups + channels) * sizeof(double2) + 255) / 256 * 256;
+}
+
+static int gn_bwd_args(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                       int channels, int groups, const float *gamma, const float *beta,
+                       const void *saved, size_t saved_bytes, int relu, void *workspace,
+                       size_t workspace_bytes, ia::GnTrainArgs &a)
+{
+    ia::GnArgs s;
+    int rc = ia::gn_args(g, channels, groups, s);
+    if (rc) return rc;
+    if (!workspace || !saved || !gamma || !beta) return IA_E_ARG;
+    if (((uintptr_t)workspace & 15u) || ((uintptr_t)saved & 15u)) return IA_E_ARG;
+    ia::gn_train_args(s, a);
+    if (!ia::gn_level_ptrs(a.num_levels, x, a.x) || !ia::gn_level_ptrs(a.num_levels, dy, a.dy))
+        return IA_E_ARG;
+    if (workspace_bytes < ia_groupnorm_bwd_workspace_bytes(g, channels, groups) ||
+        saved_bytes < ia_groupnorm_saved_bytes(g, channels, groups))
+        return IA_E_WORKSPACE;
+    a.gamma = gamma; a.beta = beta; a.relu = relu ? 1 : 0;
+    a.saved = const_cast<double2 *>(static_cast<const double2 *>(saved));
+    a.gpart = static_cast<double2 *>(workspace);
+    a.cpart = a.gpart + (size_t)a.blk_off[IA_MAX_LEVELS] * groups;
+    return 0;
+}
+
+int ia_groupnorm_bwd_reduce(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                            int channels, int groups, const float *gamma, const float *beta,
+                            int relu, const void *saved, size_t saved_bytes, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    ia::GnTrainArgs a;
+    int rc = gn_bwd_args(g, x, dy, channels, groups, gamma, beta, saved, saved_bytes, relu,
+                         workspace, workspace_bytes, a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ia::k_gn_bwd_reduce, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
+                       dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                           float *const *dx, int channels, int groups, const float *gamma,
+                           const float *beta, int relu, const void *saved, size_t saved_bytes,
+                           const void *workspace, size_t workspace_bytes, float *dgamma,
+                           float *dbeta, void *stream)
+{
+    ia::GnTrainArgs a;
+    int rc = gn_bwd_args(g, x, dy, channels, groups, gamma, beta, saved, saved_bytes, relu,
+                         const_cast<void *>(workspace), workspace_bytes, a);
+    if (rc) return rc;
+    if (dx) {                                           // NULL: parameter gradients only
+        if (!ia::gn_level_ptrs(a.num_levels, dx, const_cast<const float **>(a.out)))
+            return IA_E_ARG;
+        for (int l = 0; l < a.num_levels; ++l)
+            if (dx[l] == dy[l] || dx[l] == x[l]) return IA_E_ARG;
+        hipLaunchKernelGGL(ia::k_gn_bwd_apply, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
+                           dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
+        rc = ia::hip_status(hipGetLastError());
+        if (rc) return rc;
+    }
+    if (dgamma || dbeta) {
+        hipLaunchKernelGGL(ia::k_gn_bwd_params, dim3((unsigned)((channels + 15) / 16)),
+                           dim3(ia::kGnThreads), 0, (hipStream_t)stream, a.cpart,
+                           a.blk_off[IA_MAX_LEVELS], channels, dgamma, dbeta);
+        rc = ia::hip_status(hipGetLastError());
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -3,8 +3,11 @@
 constructor kwargs, parameter names and method signatures.
 
   * forward / forward_single: the 4 + 4 GN towers and the output convolutions as PyTorch
-    modules (the training route; at inference `fuse.fuse_inference(winograd=True)` swaps in the
-    Winograd runner with the HIP GroupNorm + ReLU, winograd.WinogradFCOSHead);
+    modules.  In training with `train_winograd = True` (opt-in; where
+    winograd_train.fcos_usable holds) forward instead runs every tower convolution as one
+    Winograd autograd node over all levels and every GroupNorm + ReLU as one HIP node with a HIP
+    backward (fcos_ops.groupnorm_relu); at inference `fuse.fuse_inference(winograd=True)` swaps
+    in the Winograd runner with the in-place HIP GroupNorm + ReLU (winograd.WinogradFCOSHead);
   * get_bboxes: one call into the HIP library for the whole batch (row max, per-level top-k,
     distance2bbox, batched NMS): ia_point_get_bboxes with the fused alpha score (IoU-aware),
     ia_point_ctr_get_bboxes with the raw-threshold / centerness-product scores (plain);
@@ -85,8 +88,19 @@ class _FCOSHeadBase(nn.Module):
         if self.iou_branch:
             normal_init(self.fcos_iou, std=0.01)
 
+    # training: all-levels Winograd towers + HIP GroupNorm when set and usable.  Off by default: the
+    # whole-iteration comparison against the module route is not measured yet
+    train_winograd = False
+
     def forward(self, feats):
-        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L][, ious[L]])"""
+        """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L][, ious[L]]).
+        With `train_winograd = True`, in training on a ROCm device every tower convolution runs once for all levels on the
+        Winograd path and every GroupNorm + ReLU as one HIP node, each with its own backward
+        (winograd_train.fcos_head_forward) -- same parameters, same outputs to fp32 rounding."""
+        if self.training and self.train_winograd:
+            from . import winograd_train
+            if winograd_train.fcos_usable(feats, self):
+                return winograd_train.fcos_head_forward(self, feats)
         return multi_apply(self.forward_single, feats, self.scales)
 
     def forward_single(self, x, scale):

@@ -1,7 +1,8 @@
 """torch front-end of the FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip,
 csrc/pointloss.hip): the point heads' post-conv paths (ia_point_get_bboxes: IoU-aware;
 ia_point_ctr_get_bboxes: plain FCOS, the centerness map in the third slot), the towers'
-GroupNorm + ReLU, and the training side: point targets and the all-levels loss node.
+GroupNorm + ReLU (in place for inference, groupnorm_relu: the autograd node), and the training
+side: point targets and the all-levels loss node.
 Device tensors only, launched on the current torch stream, like ops.py."""
 import ctypes as C
 
@@ -153,30 +154,28 @@ def _wino_geom(xs):
 _gn_ws = {}
 
 
+def _gn_workspace(dev, nbytes):
+    """the partials' buffer of (device, stream): written and read by consecutive launches only"""
+    key = (dev.index, stream_id())
+    ws = _gn_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _gn_ws[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    return ws
+
+
 def groupnorm_relu_(xs, gamma, beta, groups, eps=1e-5, relu=True):
     """In place over the levels xs[l] (B, ch, H_l, W_l) fp32 channels-last: GroupNorm (statistics
     per level and image) + ReLU, two launches for all of them.  gamma / beta (ch,) fp32."""
-    if not xs or len(xs) > _lib.IA_MAX_LEVELS:
-        raise ValueError('1..%d levels' % _lib.IA_MAX_LEVELS)
-    ch = int(xs[0].shape[1])
     for x in xs:
         _require_gpu(x, 'x')
-        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != ch or x.shape[0] != xs[0].shape[0] \
-                or not x.is_contiguous(memory_format=torch.channels_last):
-            raise ValueError('groupnorm_relu_ takes fp32 channels-last (B, %d, H, W) levels' % ch)
-    for t in (gamma, beta):
-        if t.dtype != torch.float32 or t.numel() != ch or not t.is_contiguous() or t.device != xs[0].device:
-            raise ValueError('gamma / beta: (%d,) fp32 on the device' % ch)
+    ch = _gn_check('groupnorm_relu_', xs, gamma, beta)
     g = _wino_geom(xs)
     L = _lib.lib()
     nbytes = L.ia_groupnorm_workspace_bytes(C.byref(g), ch, int(groups))
     if nbytes == 0:
         raise _lib.IouAwareLibraryError('unsupported GroupNorm geometry (channels %d, groups %d)'
                                         % (ch, groups))
-    key = (xs[0].device.index, stream_id())
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _gn_ws[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=xs[0].device)
+    ws = _gn_workspace(xs[0].device, nbytes)
     ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
     _lib.check(L.ia_groupnorm_stats(C.byref(g), ptrs, ch, int(groups), _ptr(ws), nbytes, _stream()),
                'ia_groupnorm_stats')
@@ -184,6 +183,107 @@ def groupnorm_relu_(xs, gamma, beta, groups, eps=1e-5, relu=True):
                                     float(eps), int(bool(relu)), _ptr(ws), nbytes, _stream()),
                'ia_groupnorm_apply')
     return xs
+
+
+def _gn_check(name, xs, gamma, beta):
+    """the argument contract of groupnorm_relu_ / groupnorm_relu: ValueError before the device is
+    touched -> channels"""
+    if not xs or len(xs) > _lib.IA_MAX_LEVELS:
+        raise ValueError('1..%d levels' % _lib.IA_MAX_LEVELS)
+    ch = int(xs[0].shape[1]) if xs[0].dim() == 4 else -1
+    for x in xs:
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != ch \
+                or x.shape[0] != xs[0].shape[0] or x.device != xs[0].device \
+                or not x.is_contiguous(memory_format=torch.channels_last):
+            raise ValueError('%s takes fp32 channels-last (B, %d, H, W) levels on one device' % (name, ch))
+    for t in (gamma, beta):
+        if t.dtype != torch.float32 or t.numel() != ch or not t.is_contiguous() or t.device != xs[0].device:
+            raise ValueError('gamma / beta: (%d,) fp32 on the device' % ch)
+    return ch
+
+
+def _gn_upstream(d):
+    """an upstream gradient as the kernels read it: fp32, channels-last, 16-byte aligned (a copy
+    where autograd hands over anything else, e.g. a slice with a storage offset)"""
+    d = d.to(torch.float32).contiguous(memory_format=torch.channels_last)
+    return d.clone(memory_format=torch.channels_last) if d.data_ptr() % 16 else d
+
+
+def _level_ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+class _GroupNormReluFn(torch.autograd.Function):
+    """y_l = relu?(GroupNorm(x_l)) over a level list, out of place (csrc/groupnorm.hip): 2 launches
+    forward, 2 (+ 1 for the parameter gradients) backward.  Keeps x and (mean, rstd) in fp64 per
+    (level, image, group); y is not kept."""
+
+    @staticmethod
+    def forward(ctx, gamma, beta, groups, eps, relu, *xs):
+        ch = int(xs[0].shape[1])
+        g = _wino_geom(xs)
+        L = _lib.lib()
+        nbytes = L.ia_groupnorm_workspace_bytes(C.byref(g), ch, groups)
+        nsaved = L.ia_groupnorm_saved_bytes(C.byref(g), ch, groups)
+        nbwd = L.ia_groupnorm_bwd_workspace_bytes(C.byref(g), ch, groups)
+        if nbytes == 0 or nsaved == 0 or nbwd == 0:
+            raise _lib.IouAwareLibraryError('unsupported GroupNorm geometry (channels %d, groups %d)'
+                                            % (ch, groups))
+        dev = xs[0].device
+        gamma_, beta_ = gamma.detach(), beta.detach()
+        ws = _gn_workspace(dev, max(nbytes, nbwd))
+        saved = torch.empty(int(nsaved), dtype=torch.uint8, device=dev)
+        ys = [torch.empty_like(x) for x in xs]
+        px = _level_ptrs(xs)
+        _lib.check(L.ia_groupnorm_stats(C.byref(g), px, ch, groups, _ptr(ws), nbytes, _stream()),
+                   'ia_groupnorm_stats')
+        _lib.check(L.ia_groupnorm_apply_to(C.byref(g), px, _level_ptrs(ys), ch, groups, _ptr(gamma_),
+                                           _ptr(beta_), eps, int(relu), _ptr(ws), nbytes, _ptr(saved),
+                                           nsaved, _stream()), 'ia_groupnorm_apply_to')
+        ctx.geom, ctx.cfg, ctx.sizes = g, (ch, groups, int(relu)), (nsaved, nbwd)
+        ctx.save_for_backward(gamma, beta, saved, *xs)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        gamma, beta, saved = ctx.saved_tensors[:3]
+        xs = ctx.saved_tensors[3:]
+        ch, groups, relu = ctx.cfg
+        nsaved, nbwd = ctx.sizes
+        g, L, dev = ctx.geom, _lib.lib(), xs[0].device
+        gamma_, beta_ = gamma.detach(), beta.detach()
+        dys = [_gn_upstream(d) for d in dys]
+        ws = _gn_workspace(dev, nbwd)
+        px, pdy = _level_ptrs(xs), _level_ptrs(dys)
+        _lib.check(L.ia_groupnorm_bwd_reduce(C.byref(g), px, pdy, ch, groups, _ptr(gamma_), _ptr(beta_),
+                                             relu, _ptr(saved), nsaved, _ptr(ws), nbwd, _stream()),
+                   'ia_groupnorm_bwd_reduce')
+        need_x = any(ctx.needs_input_grad[5:])
+        dxs = [torch.empty_like(x) for x in xs] if need_x else None
+        dgamma = torch.empty(ch, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dbeta = torch.empty(ch, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        if need_x or dgamma is not None or dbeta is not None:
+            _lib.check(L.ia_groupnorm_bwd_apply(C.byref(g), px, pdy, _level_ptrs(dxs) if need_x else None,
+                                                ch, groups, _ptr(gamma_), _ptr(beta_), relu, _ptr(saved),
+                                                nsaved, _ptr(ws), nbwd, _ptr(dgamma), _ptr(dbeta),
+                                                _stream()), 'ia_groupnorm_bwd_apply')
+        return (dgamma, dbeta, None, None, None) + (tuple(dxs) if need_x else (None,) * len(xs))
+
+
+def groupnorm_supported(sizes, batch, channels, groups):
+    """whether the GroupNorm training kernels cover per-level (H, W) sizes at this batch, channel
+    and group count (the library's own answer: its workspace query)"""
+    g = winograd._wino_geom([tuple(int(v) for v in s) for s in sizes], int(batch))
+    return _lib.lib().ia_groupnorm_bwd_workspace_bytes(C.byref(g), int(channels), int(groups)) != 0
+
+
+def groupnorm_relu(xs, gamma, beta, groups, eps=1e-5, relu=True):
+    """Out of place over the levels xs[l] (B, ch, H_l, W_l) fp32 channels-last: GroupNorm (statistics
+    per level and image) + ReLU as one autograd node with gradients for every x_l, gamma and beta
+    (those that require them).  -> list of new channels-last tensors."""
+    xs = list(xs)
+    _gn_check('groupnorm_relu', xs, gamma, beta)
+    return list(_GroupNormReluFn.apply(gamma, beta, int(groups), float(eps), bool(relu), *xs))
 
 
 # ------------------------------------------------------------------ training

@@ -287,3 +287,92 @@ def head_forward(head, feats):
         return cls, reg
     iou = [t[:, n_reg:n_reg + n_iou] for t in ri]
     return cls, reg, iou
+
+
+# ------------------------------------------------------------------ FCOS heads
+def _fcos_tower_layer(m, channels):
+    """ConvModule(3x3 / stride 1 / pad 1 without bias, GroupNorm with affine parameters, ReLU): a
+    tower layer of the FCOS heads (fcos_head.py: norm_cfg = GN).  Whether the kernels take the
+    GroupNorm's channel / group counts is the library's answer (fcos_head_supported)."""
+    conv = m.conv
+    if not (type(conv) is torch.nn.Conv2d and W.plain_3x3(conv) and conv.bias is None
+            and conv.padding_mode == 'zeros' and conv.out_channels == channels):
+        return False
+    if not (m.with_norm and m.with_activatation and m.activate_last):
+        return False
+    gn = m.norm
+    return (type(gn) is torch.nn.GroupNorm and gn.affine and gn.num_channels == channels
+            and gn.weight.dtype == torch.float32)
+
+
+def fcos_head_supported(head, sizes, batch):
+    """the module side of fcos_usable: what fcos_head_forward computes for this head on per-level
+    (H, W) feature sizes.  No device needed (the library's size query runs on the host)."""
+    from . import fcos_ops
+    towers = list(head.cls_convs) + list(head.reg_convs)
+    outs = [head.fcos_cls, head.fcos_centerness, head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else [])
+    if not towers or head.in_channels % 4 or head.feat_channels % 4:
+        return False
+    if not (1 <= len(sizes) <= len(head.scales)):
+        return False
+    if not all(_fcos_tower_layer(m, head.feat_channels) for m in towers):
+        return False
+    if not all(_plain_3x3(c) and c.in_channels == head.feat_channels for c in outs):
+        return False
+    if not _library_loads():
+        return False
+    return all(fcos_ops.groupnorm_supported(sizes, batch, head.feat_channels, g)
+               for g in set(m.norm.num_groups for m in towers))
+
+
+def fcos_usable(feats, head):
+    return (torch.is_grad_enabled() and len(feats) > 0
+            and all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                    and x.shape[1] == head.in_channels for x in feats)
+            and fcos_head_supported(head, [tuple(x.shape[-2:]) for x in feats], feats[0].shape[0]))
+
+
+def _packed_outputs(convs, feat):
+    """several output convolutions of one tower as one (columns padded with zero weights and bias
+    to a multiple of 4) -> per convolution the list of per-level channel slices"""
+    n = [c.out_channels for c in convs]
+    pad = (-sum(n)) % 4
+    if len(convs) == 1 and not pad:
+        return [wino_conv_levels(feat, convs[0].weight, convs[0].bias)]
+    w0, b0 = convs[0].weight, convs[0].bias
+    w = torch.cat([c.weight for c in convs] + ([w0.new_zeros((pad,) + tuple(w0.shape[1:]))] if pad else []))
+    b = torch.cat([c.bias for c in convs] + ([b0.new_zeros(pad)] if pad else []))
+    ys = wino_conv_levels(feat, w, b)
+    res, off = [], 0
+    for k in n:
+        res.append([t[:, off:off + k] for t in ys])
+        off += k
+    return res
+
+
+def fcos_head_forward(head, feats):
+    """_FCOSHeadBase.forward (multi_apply(forward_single), reference fcos_head.py /
+    iou_aware_fcos_head.py) with every tower convolution one Winograd node over all levels, followed
+    by the HIP GroupNorm + ReLU node (fcos_ops.groupnorm_relu); fcos_cls | fcos_centerness are one
+    output convolution on the cls tower (81 -> 84 columns), fcos_reg | fcos_iou one on the reg tower
+    (5 -> 8; fcos_reg alone in the plain head).  bbox_pred = exp(scale_l * reg) in torch on the
+    4-channel slice.  Returns the reference's tuple (cls[L], bbox[L], centerness[L][, iou[L]]) of
+    NCHW-contiguous maps, which the fused loss node takes."""
+    from .fcos_ops import groupnorm_relu
+    cls_feat = reg_feat = [_cl(x) for x in feats]
+    for m in head.cls_convs:
+        gn = m.norm
+        cls_feat = groupnorm_relu(wino_conv_levels(cls_feat, m.conv.weight, None, relu=False),
+                                  gn.weight, gn.bias, gn.num_groups, gn.eps)
+    for m in head.reg_convs:
+        gn = m.norm
+        reg_feat = groupnorm_relu(wino_conv_levels(reg_feat, m.conv.weight, None, relu=False),
+                                  gn.weight, gn.bias, gn.num_groups, gn.eps)
+    cls, ctr = _packed_outputs([head.fcos_cls, head.fcos_centerness], cls_feat)
+    ri = _packed_outputs([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []), reg_feat)
+    cls = [t.contiguous() for t in cls]
+    ctr = [t.contiguous() for t in ctr]
+    bbox = [scale(t.contiguous()).exp() for t, scale in zip(ri[0], head.scales)]
+    if not head.iou_branch:
+        return cls, bbox, ctr
+    return cls, bbox, ctr, [t.contiguous() for t in ri[1]]

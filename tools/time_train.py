@@ -1,9 +1,17 @@
 """Scratch: BASELINE config 5 on one GPU -- training iterations of R-50 IoU-aware RetinaNet at
-800x1344, B images, HIP target assignment + loss kernels (no data-parallel all-reduce here)."""
+800x1344, B images, HIP target assignment + loss kernels (no data-parallel all-reduce here).
+
+    python tools/time_train.py [B]
+    MODEL=fcos|fcos_plain python tools/time_train.py [B]     the two FCOS detectors (R-50 caffe, GN
+                                                             towers): tools/time_fcos.py's own
+                                                             config, or CONFIG=<an mmdet config file
+                                                             with model / train_cfg / test_cfg>
+    TRAIN_WINOGRAD=0    the head's module route (bbox_head.train_winograd = False)
+    ITERS=n             timed iterations (default 5)"""
 import sys, os, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, os.path.join(ROOT, 'iou-aware-single-stage-object-detector_amd'))
-sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import torch, bench, synth, iouaware
 from iouaware.config import ConfigDict
 from iouaware.train import build_optimizer, train_step
@@ -12,7 +20,24 @@ torch.backends.cudnn.benchmark = not os.environ.get('NOFIND')
 TRAIN_CFG = ConfigDict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0,
                                      ignore_iof_thr=-1), allowed_border=-1, pos_weight=-1, debug=False)
 torch.manual_seed(0)
-model = iouaware.build_detector(ConfigDict(bench.MODEL), train_cfg=TRAIN_CFG, test_cfg=ConfigDict(bench.TEST_CFG)).cuda().train()
+MODEL = os.environ.get('MODEL', 'retina')
+if MODEL == 'retina':
+    model = iouaware.build_detector(ConfigDict(bench.MODEL), train_cfg=TRAIN_CFG, test_cfg=ConfigDict(bench.TEST_CFG)).cuda().train()
+else:
+    TRAIN_CFG = ConfigDict(gamma=2.0, alpha=0.25)
+    if os.environ.get('CONFIG'):
+        from iouaware.config import Config
+        cfg = Config.fromfile(os.environ['CONFIG'])
+        cfg.model['pretrained'] = None
+        TRAIN_CFG = cfg.train_cfg
+        model = iouaware.build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).cuda().train()
+    else:
+        import time_fcos
+        model = time_fcos.build(head=dict(fcos='iou_aware', fcos_plain='plain')[MODEL]).train()
+        model.train_cfg = TRAIN_CFG
+if os.environ.get('TRAIN_WINOGRAD') is not None:
+    model.bbox_head.train_winograd = bool(int(os.environ['TRAIN_WINOGRAD']))
+print('model %s  head %s  train_winograd %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd))
 opt = build_optimizer(model, dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001))
 img = torch.randn(B, 3, 800, 1344, device='cuda')
 if os.environ.get('FUSE'):
@@ -25,7 +50,7 @@ gts, gls = synth.train_targets(5, B, 800, 1333, max_gt=20)
 gtb = [torch.from_numpy(x).cuda() for x in gts]; gtl = [torch.from_numpy(x).cuda() for x in gls]
 metas = [synth.img_meta(800, 1333, 800, 1344) for _ in range(B)]
 for _ in range(3): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
-torch.cuda.synchronize(); t = time.time(); n = 5
+torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats(); t = time.time(); n = int(os.environ.get('ITERS', 5))
 for _ in range(n): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); dt = (time.time() - t) / n
 print('B=%d  %.1f ms/iter  %.1f img/s  loss %s  mem %.1f GB' % (B, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
