@@ -785,6 +785,22 @@ int ia_groupnorm_stats(const ia_wino_geom *g, const float *const *x, int channel
 int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int groups,
                        const float *gamma, const float *beta, float eps, int relu,
                        const void *workspace, size_t workspace_bytes, void *stream);
+/* The inference triple for dtype IA_F32 / IA_BF16 activations (gamma, beta, eps, the workspace and
+ * its contract as above).  IA_F32: the entries above, same bits.  IA_BF16: x[l] (batch, H_l, W_l,
+ * channels) bf16 channels-last, normalised in place -- fp64 sums of the exactly converted values,
+ * added in a fixed order (a thread's 16-byte column is 8 channels of one group); s = gamma * rstd
+ * and t = beta - mean * s formed in fp64 and rounded once to fp32; y = relu?(x * s + t) in fp32 and
+ * ONE round-to-nearest-even to bf16; 16-byte loads and stores.  Same bits from run to run; an
+ * image's result does not depend on the other images / levels of the launch.
+ * What IA_BF16 covers: channels a power of two, 8 <= channels <= 1024; 1 <= groups <= 256, groups
+ * divides channels and channels / groups % 8 == 0; x[l] 16-byte aligned.  The size query returns 0
+ * for anything else (and for any other dtype); the two launches then return IA_E_ARG.          */
+size_t ia_groupnorm_workspace_bytes_dt(const ia_wino_geom *g, int channels, int groups, int dtype);
+int ia_groupnorm_stats_dt(const ia_wino_geom *g, const void *const *x, int dtype, int channels,
+                          int groups, void *workspace, size_t workspace_bytes, void *stream);
+int ia_groupnorm_apply_dt(const ia_wino_geom *g, void *const *x, int dtype, int channels, int groups,
+                          const float *gamma, const float *beta, float eps, int relu,
+                          const void *workspace, size_t workspace_bytes, void *stream);
 /* The same GroupNorm + ReLU as a training node, out of place (csrc/groupnorm.hip).  Forward:
  * ia_groupnorm_stats on x, then
  *   ia_groupnorm_apply_to: y[l] = relu?(x[l] * s + t), the bits ia_groupnorm_apply leaves in x;
@@ -827,6 +843,11 @@ int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const f
  * scales: (num_levels) fp32 device array (the head's Scale parameters).                      */
 int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, const float *scales,
                         void *stream);
+/* dtype IA_F32: the entry above.  IA_BF16: x[l] bf16 (channels % 4 == 0, 8-byte aligned), in place
+ * bf16(exp(scale_l * float(x))): the fp32 entry's evaluation, rounded once (nearest even) -- the
+ * bits of the fp32 entry on the widened tensor, converted to bf16.                             */
+int ia_scale_exp_levels_dt(const ia_wino_geom *g, void *const *x, int dtype, int channels,
+                           const float *scales, void *stream);
 
 /* Point head (IoU-aware FCOS) post-processing: get_bboxes / get_bboxes_single of
  * iou_aware_fcos_head.py:248-370.  One point per position (no anchors), stored like the anchor
@@ -881,6 +902,28 @@ int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p,
                             float score_thr, float iou_thr, int max_per_img, int candidates,
                             void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                             int32_t *rows, int32_t *num, void *stream);
+/* The four point entries for dtype IA_F32 / IA_BF16 maps (one dtype for cls, reg and iou /
+ * centerness; dtype after batch, as ia_get_bboxes has it).  A bf16 value converts exactly to fp32
+ * when it is loaded and everything behind the load is the fp32 arithmetic: bf16 maps give the bits
+ * the fp32 entries give on their widened copies.  Workspace, outputs and tie rule unchanged (scores
+ * and boxes are fp32).  Channels-last bf16: C % 8 == 0 and 16-byte aligned cls pointers.        */
+int ia_point_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                             int dtype, const float *img_hw, const float *scale_factor, int rescale,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int ia_point_get_bboxes_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                           int dtype, const float *img_hw, const float *scale_factor, int rescale,
+                           float score_thr, float iou_thr, int max_per_img, int candidates,
+                           void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                           int32_t *rows, int32_t *num, void *stream);
+int ia_point_ctr_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                                 int dtype, const float *img_hw, const float *scale_factor,
+                                 int rescale, float score_thr, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int ia_point_ctr_get_bboxes_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                               int dtype, const float *img_hw, const float *scale_factor,
+                               int rescale, float score_thr, float iou_thr, int max_per_img,
+                               int candidates, void *workspace, size_t workspace_bytes, float *dets,
+                               int32_t *labels, int32_t *rows, int32_t *num, void *stream);
 
 /* ------------------------------------------------------------------ FCOS training: point targets
  * fcos_target / fcos_target_single of fcos_head.py and iou_aware_fcos_head.py for a whole batch in

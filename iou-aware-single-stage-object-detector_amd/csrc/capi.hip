@@ -459,7 +459,8 @@ int ia_point_workspace_layout(const ia_point_head_geom *g, int batch, size_t off
 static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                              const float *img_hw, const float *scale_factor, int rescale,
                              void *workspace, size_t workspace_bytes, hipStream_t s,
-                             ia::WsLayout &w, ia::LevelTable &t, int kind, float score_thr)
+                             ia::WsLayout &w, ia::LevelTable &t, int kind, float score_thr,
+                             int dtype)
 {
     ia_head_geom hg;
     int rc = ia::point_head_geom(g, hg);
@@ -475,33 +476,51 @@ static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p
                                    reinterpret_cast<int32_t *>(ws + w.off[1]), ws + w.off[8],
                                    reinterpret_cast<float *>(ws + w.off[2]),
                                    reinterpret_cast<float *>(ws + w.off[3]),
-                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, kind, score_thr, s);
+                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, kind, score_thr,
+                                   dtype, s);
+}
+
+int ia_point_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                             int dtype, const float *img_hw, const float *scale_factor, int rescale,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    ia::WsLayout w;
+    ia::LevelTable t;
+    return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
+                             (hipStream_t)stream, w, t, 0, 0.0f, dtype);
 }
 
 int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                           const float *img_hw, const float *scale_factor, int rescale,
                           void *workspace, size_t workspace_bytes, void *stream)
 {
+    return ia_point_decode_stage_dt(g, p, batch, IA_F32, img_hw, scale_factor, rescale, workspace,
+                                    workspace_bytes, stream);
+}
+
+int ia_point_ctr_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                                 int dtype, const float *img_hw, const float *scale_factor,
+                                 int rescale, float score_thr, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
     ia::WsLayout w;
     ia::LevelTable t;
     return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
-                             (hipStream_t)stream, w, t, 0, 0.0f);
+                             (hipStream_t)stream, w, t, 1, score_thr, dtype);
 }
 
 int ia_point_ctr_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                               const float *img_hw, const float *scale_factor, int rescale,
                               float score_thr, void *workspace, size_t workspace_bytes, void *stream)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
-    return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
-                             (hipStream_t)stream, w, t, 1, score_thr);
+    return ia_point_ctr_decode_stage_dt(g, p, batch, IA_F32, img_hw, scale_factor, rescale,
+                                        score_thr, workspace, workspace_bytes, stream);
 }
 
 // decode stage of `kind`, then the shared NMS stages at `stage_thr` (the IoU-aware head: its
 // score_thr; plain FCOS: kPointCtrStageThr, the raw threshold having been applied by the gather)
 static int point_get_bboxes_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
-                                 const float *img_hw, const float *scale_factor, int rescale,
+                                 int dtype, const float *img_hw, const float *scale_factor, int rescale,
                                  int kind, float score_thr, float stage_thr, float iou_thr,
                                  int max_per_img, int candidates, void *workspace,
                                  size_t workspace_bytes, float *dets, int32_t *labels,
@@ -511,7 +530,7 @@ static int point_get_bboxes_impl(const ia_point_head_geom *g, const ia_level_ptr
     ia::LevelTable t;
     if (!dets || !labels || !rows || !num) return IA_E_ARG;
     int rc = point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace,
-                               workspace_bytes, s, w, t, kind, score_thr);
+                               workspace_bytes, s, w, t, kind, score_thr, dtype);
     if (rc) return rc;
     char *ws = static_cast<char *>(workspace);
     float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
@@ -539,15 +558,37 @@ static int point_get_bboxes_impl(const ia_point_head_geom *g, const ia_level_ptr
                                dets, labels, rows, num, s, gate);
 }
 
+int ia_point_get_bboxes_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                           int dtype, const float *img_hw, const float *scale_factor, int rescale,
+                           float score_thr, float iou_thr, int max_per_img, int candidates,
+                           void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
+                           int32_t *rows, int32_t *num, void *stream)
+{
+    return point_get_bboxes_impl(g, p, batch, dtype, img_hw, scale_factor, rescale, 0, 0.0f,
+                                 score_thr, iou_thr, max_per_img, candidates, workspace,
+                                 workspace_bytes, dets, labels, rows, num, (hipStream_t)stream);
+}
+
 int ia_point_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                         const float *img_hw, const float *scale_factor, int rescale,
                         float score_thr, float iou_thr, int max_per_img, int candidates,
                         void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                         int32_t *rows, int32_t *num, void *stream)
 {
-    return point_get_bboxes_impl(g, p, batch, img_hw, scale_factor, rescale, 0, 0.0f, score_thr,
-                                 iou_thr, max_per_img, candidates, workspace, workspace_bytes, dets,
-                                 labels, rows, num, (hipStream_t)stream);
+    return ia_point_get_bboxes_dt(g, p, batch, IA_F32, img_hw, scale_factor, rescale, score_thr,
+                                  iou_thr, max_per_img, candidates, workspace, workspace_bytes,
+                                  dets, labels, rows, num, stream);
+}
+
+int ia_point_ctr_get_bboxes_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
+                               int dtype, const float *img_hw, const float *scale_factor,
+                               int rescale, float score_thr, float iou_thr, int max_per_img,
+                               int candidates, void *workspace, size_t workspace_bytes, float *dets,
+                               int32_t *labels, int32_t *rows, int32_t *num, void *stream)
+{
+    return point_get_bboxes_impl(g, p, batch, dtype, img_hw, scale_factor, rescale, 1, score_thr,
+                                 ia::kPointCtrStageThr, iou_thr, max_per_img, candidates, workspace,
+                                 workspace_bytes, dets, labels, rows, num, (hipStream_t)stream);
 }
 
 int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
@@ -556,9 +597,9 @@ int ia_point_ctr_get_bboxes(const ia_point_head_geom *g, const ia_level_ptrs *p,
                             void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                             int32_t *rows, int32_t *num, void *stream)
 {
-    return point_get_bboxes_impl(g, p, batch, img_hw, scale_factor, rescale, 1, score_thr,
-                                 ia::kPointCtrStageThr, iou_thr, max_per_img, candidates, workspace,
-                                 workspace_bytes, dets, labels, rows, num, (hipStream_t)stream);
+    return ia_point_ctr_get_bboxes_dt(g, p, batch, IA_F32, img_hw, scale_factor, rescale,
+                                      score_thr, iou_thr, max_per_img, candidates, workspace,
+                                      workspace_bytes, dets, labels, rows, num, stream);
 }
 
 size_t ia_nms_workspace_bytes(int n)

@@ -159,6 +159,114 @@ __global__ void __launch_bounds__(kGnThreads) k_gn_apply(GnArgs a)
     }
 }
 
+// ------------------------------------------------------------------ bf16 (in place, inference)
+// The same pair on (B, H_l, W_l, channels) bf16 channels-last activations (the towers of the bf16
+// head route, conv3x3_bf16.hip in front): GnArgs::x[l] then carries the bf16 base pointers.  A
+// thread's 16-byte column is 8 channels (inside one group: channels / groups % 8 == 0); the values
+// convert exactly to fp32 / fp64, so the statistics are those of the stored numbers, accumulated
+// and combined exactly as above.  The apply forms s and t as above, evaluates x * s + t (and the
+// ReLU) in fp32 and rounds ONCE to bf16 (nearest even).
+__device__ __forceinline__ const uint16_t *gn_image_bf16(const GnBlock &k, int channels)
+{
+    return reinterpret_cast<const uint16_t *>(k.x) + (size_t)k.b * k.HW * channels;
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_stats_bf16(GnArgs a)
+{
+    __shared__ double s_sum[kGnThreads], s_sq[kGnThreads];
+    const GnBlock k = gn_block(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int vc = a.channels >> 3;             // 16-byte columns per pixel (divides kGnThreads)
+    const int rows = kGnThreads / vc;           // pixels per pass
+    const int v = tid % vc, r = tid / vc;
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const uint4 *x = reinterpret_cast<const uint4 *>(gn_image_bf16(k, a.channels)) + v;
+    double s = 0.0, ss = 0.0;
+    for (int p = p0 + r; p < p1; p += rows) {
+        float f[8];
+        bf16x8_to_f32(x[(size_t)p * vc], f);
+        const double d0 = f[0], d1 = f[1], d2 = f[2], d3 = f[3], d4 = f[4], d5 = f[5], d6 = f[6],
+                     d7 = f[7];
+        s += (((d0 + d1) + (d2 + d3)) + ((d4 + d5) + (d6 + d7)));
+        ss += (((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) +
+               ((d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7)));
+    }
+    s_sum[tid] = s;
+    s_sq[tid] = ss;
+    __syncthreads();
+    const int vpg = (a.channels / a.groups) >> 3;    // columns per group
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double ts = 0.0, tss = 0.0;
+        for (int rr = 0; rr < rows; ++rr)
+            for (int j = 0; j < vpg; ++j) {
+                const int t = rr * vc + g * vpg + j;
+                ts += s_sum[t];
+                tss += s_sq[t];
+            }
+        a.part[(size_t)(k.row0 + k.chunk) * a.groups + g] = make_double2(ts, tss);
+    }
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_apply_bf16(GnArgs a)
+{
+    __shared__ double s_mean[256], s_rstd[256];
+    __shared__ float4 s_scale[256], s_shift[256];      // per 4 channels
+    const GnBlock k = gn_block(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double ts = 0.0, tss = 0.0;
+        const double2 *pp = a.part + (size_t)k.row0 * a.groups + g;
+        for (int c = 0; c < k.nch; ++c) {
+            const double2 q = pp[(size_t)c * a.groups];
+            ts += q.x;
+            tss += q.y;
+        }
+        const double n = (double)k.HW * cpg;
+        const double mean = ts / n;
+        double var = tss / n - mean * mean;
+        var = var > 0.0 ? var : 0.0;
+        s_mean[g] = mean;
+        s_rstd[g] = 1.0 / sqrt(var + (double)a.eps);
+    }
+    __syncthreads();
+    for (int q = tid; q < (a.channels >> 2); q += kGnThreads) {
+        const int g = (4 * q) / cpg;
+        const double mean = s_mean[g], rstd = s_rstd[g];
+        float sc[4], sh[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = 4 * q + j;
+            sc[j] = (float)((double)a.gamma[c] * rstd);
+            sh[j] = (float)((double)a.beta[c] - mean * (double)sc[j]);
+        }
+        s_scale[q] = make_float4(sc[0], sc[1], sc[2], sc[3]);
+        s_shift[q] = make_float4(sh[0], sh[1], sh[2], sh[3]);
+    }
+    __syncthreads();
+    const int vc = a.channels >> 3;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const float4 sa = s_scale[2 * v], sb = s_scale[2 * v + 1];
+    const float4 ta = s_shift[2 * v], tb = s_shift[2 * v + 1];
+    const float sc[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+    const float sh[8] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w};
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    uint4 *x = reinterpret_cast<uint4 *>(const_cast<uint16_t *>(gn_image_bf16(k, a.channels))) + v;
+    for (int p = p0 + r; p < p1; p += rows) {
+        float f[8];
+        bf16x8_to_f32(x[(size_t)p * vc], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            f[j] = f[j] * sc[j] + sh[j];
+            if (a.relu) f[j] = f[j] > 0.0f ? f[j] : 0.0f;
+        }
+        x[(size_t)p * vc] = f32_to_bf16x8(f);
+    }
+}
+
 static int gn_args(const ia_wino_geom *g, int channels, int groups, GnArgs &a)
 {
     if (!g || g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS || g->batch < 1) return IA_E_ARG;
@@ -182,6 +290,16 @@ static int gn_args(const ia_wino_geom *g, int channels, int groups, GnArgs &a)
         a.x[l] = nullptr;
     }
     a.gamma = a.beta = nullptr; a.eps = 0.0f; a.relu = 0; a.part = nullptr;
+    return 0;
+}
+
+// what the bf16 pair takes on top of gn_args: whole 16-byte columns inside a group
+static int gn_args_dt(const ia_wino_geom *g, int channels, int groups, int dtype, GnArgs &a)
+{
+    if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
+    int rc = gn_args(g, channels, groups, a);
+    if (rc) return rc;
+    if (dtype == IA_BF16 && (channels < 8 || (channels / groups) % 8 != 0)) return IA_E_ARG;
     return 0;
 }
 
@@ -545,16 +663,45 @@ __global__ void __launch_bounds__(256) k_scale_exp(ScaleExpArgs a)
     x[i - base] = q;
 }
 
+// the same on bf16 tensors: a thread's four values are 8 bytes; bf16(expf_(scale_l * float(x))),
+// the fp32 kernel's evaluation and one rounding (ScaleExpArgs::x[l] carries the bf16 pointers,
+// vec_off counts groups of four values as above)
+__global__ void __launch_bounds__(256) k_scale_exp_bf16(ScaleExpArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.vec_off[a.num_levels]) return;
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < IA_MAX_LEVELS; ++k) l += (k < a.num_levels && i >= a.vec_off[k]) ? 1 : 0;
+    uint2 *x = reinterpret_cast<uint2 *>(a.x[0]);
+    int64_t base = a.vec_off[0];
+#pragma unroll
+    for (int k = 1; k < IA_MAX_LEVELS; ++k) {
+        x = (l == k) ? reinterpret_cast<uint2 *>(a.x[k]) : x;
+        base = (l == k) ? a.vec_off[k] : base;
+    }
+    const float s = a.scales[l];
+    uint2 q = x[i - base];
+    const float e0 = expf_(from_bits(q.x << 16) * s), e1 = expf_(from_bits(q.x & 0xffff0000u) * s);
+    const float e2 = expf_(from_bits(q.y << 16) * s), e3 = expf_(from_bits(q.y & 0xffff0000u) * s);
+    q.x = f32_to_bf16(e0) | (f32_to_bf16(e1) << 16);
+    q.y = f32_to_bf16(e2) | (f32_to_bf16(e3) << 16);
+    x[i - base] = q;
+}
+
 }  // namespace ia
 
 extern "C" {
 
-int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, const float *scales,
-                        void *stream)
+// dtype IA_F32: 16-byte groups of four floats; IA_BF16: 8-byte groups of four bf16
+static int scale_exp_impl(const ia_wino_geom *g, void *const *x, int channels, int dtype,
+                          const float *scales, void *stream)
 {
     if (!g || g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS || g->batch < 1 || !x || !scales)
         return IA_E_ARG;
     if (channels < 4 || (channels & 3)) return IA_E_ARG;
+    if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
+    const uintptr_t align = dtype == IA_BF16 ? 7u : 15u;
     ia::ScaleExpArgs a;
     a.num_levels = g->num_levels;
     a.scales = scales;
@@ -563,7 +710,7 @@ int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, co
         int64_t n = 0;
         a.x[l] = nullptr;
         if (l < g->num_levels) {
-            if (g->H[l] < 1 || g->W[l] < 1 || !x[l] || ((uintptr_t)x[l] & 15u)) return IA_E_ARG;
+            if (g->H[l] < 1 || g->W[l] < 1 || !x[l] || ((uintptr_t)x[l] & align)) return IA_E_ARG;
             n = (int64_t)g->batch * g->H[l] * g->W[l] * (channels / 4);
             a.x[l] = reinterpret_cast<float4 *>(x[l]);
         }
@@ -571,55 +718,99 @@ int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, co
     }
     const int64_t n = a.vec_off[IA_MAX_LEVELS];
     if (n > (1LL << 40)) return IA_E_ARG;
-    hipLaunchKernelGGL(ia::k_scale_exp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, a);
+    if (dtype == IA_BF16)
+        hipLaunchKernelGGL(ia::k_scale_exp_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(ia::k_scale_exp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, a);
     return ia::hip_status(hipGetLastError());
 }
 
+int ia_scale_exp_levels(const ia_wino_geom *g, float *const *x, int channels, const float *scales,
+                        void *stream)
+{
+    return scale_exp_impl(g, reinterpret_cast<void *const *>(x), channels, IA_F32, scales, stream);
+}
+
+int ia_scale_exp_levels_dt(const ia_wino_geom *g, void *const *x, int dtype, int channels,
+                           const float *scales, void *stream)
+{
+    return scale_exp_impl(g, x, channels, dtype, scales, stream);
+}
+
+
+size_t ia_groupnorm_workspace_bytes_dt(const ia_wino_geom *g, int channels, int groups, int dtype)
+{
+    ia::GnArgs a;
+    if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
+    return ((size_t)a.blk_off[IA_MAX_LEVELS] * groups * sizeof(double2) + 255) / 256 * 256;
+}
+
+int ia_groupnorm_stats_dt(const ia_wino_geom *g, const void *const *x, int dtype, int channels,
+                          int groups, void *workspace, size_t workspace_bytes, void *stream)
+{
+    ia::GnArgs a;
+    int rc = ia::gn_args_dt(g, channels, groups, dtype, a);
+    if (rc) return rc;
+    if (!x || !workspace) return IA_E_ARG;
+    if (workspace_bytes < ia_groupnorm_workspace_bytes_dt(g, channels, groups, dtype))
+        return IA_E_WORKSPACE;
+    for (int l = 0; l < g->num_levels; ++l) {
+        if (!x[l] || ((uintptr_t)x[l] & 15u)) return IA_E_ARG;
+        a.x[l] = static_cast<float *>(const_cast<void *>(x[l]));
+    }
+    a.part = static_cast<double2 *>(workspace);
+    const dim3 grid((unsigned)a.blk_off[IA_MAX_LEVELS]), block(ia::kGnThreads);
+    if (dtype == IA_BF16)
+        hipLaunchKernelGGL(ia::k_gn_stats_bf16, grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(ia::k_gn_stats, grid, block, 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+int ia_groupnorm_apply_dt(const ia_wino_geom *g, void *const *x, int dtype, int channels, int groups,
+                          const float *gamma, const float *beta, float eps, int relu,
+                          const void *workspace, size_t workspace_bytes, void *stream)
+{
+    ia::GnArgs a;
+    int rc = ia::gn_args_dt(g, channels, groups, dtype, a);
+    if (rc) return rc;
+    if (!x || !workspace || !gamma || !beta || !(eps >= 0.0f)) return IA_E_ARG;
+    if (workspace_bytes < ia_groupnorm_workspace_bytes_dt(g, channels, groups, dtype))
+        return IA_E_WORKSPACE;
+    for (int l = 0; l < g->num_levels; ++l) {
+        if (!x[l] || ((uintptr_t)x[l] & 15u)) return IA_E_ARG;
+        a.x[l] = static_cast<float *>(x[l]);
+    }
+    a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu ? 1 : 0;
+    a.part = const_cast<double2 *>(static_cast<const double2 *>(workspace));
+    const dim3 grid((unsigned)a.blk_off[IA_MAX_LEVELS]), block(ia::kGnThreads);
+    if (dtype == IA_BF16)
+        hipLaunchKernelGGL(ia::k_gn_apply_bf16, grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(ia::k_gn_apply, grid, block, 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
 
 size_t ia_groupnorm_workspace_bytes(const ia_wino_geom *g, int channels, int groups)
 {
-    ia::GnArgs a;
-    if (ia::gn_args(g, channels, groups, a)) return 0;
-    return ((size_t)a.blk_off[IA_MAX_LEVELS] * groups * sizeof(double2) + 255) / 256 * 256;
+    return ia_groupnorm_workspace_bytes_dt(g, channels, groups, IA_F32);
 }
 
 int ia_groupnorm_stats(const ia_wino_geom *g, const float *const *x, int channels, int groups,
                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    ia::GnArgs a;
-    int rc = ia::gn_args(g, channels, groups, a);
-    if (rc) return rc;
-    if (!x || !workspace) return IA_E_ARG;
-    if (workspace_bytes < ia_groupnorm_workspace_bytes(g, channels, groups)) return IA_E_WORKSPACE;
-    for (int l = 0; l < g->num_levels; ++l) {
-        if (!x[l] || ((uintptr_t)x[l] & 15u)) return IA_E_ARG;
-        a.x[l] = const_cast<float *>(x[l]);
-    }
-    a.part = static_cast<double2 *>(workspace);
-    hipLaunchKernelGGL(ia::k_gn_stats, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]), dim3(ia::kGnThreads),
-                       0, (hipStream_t)stream, a);
-    return ia::hip_status(hipGetLastError());
+    return ia_groupnorm_stats_dt(g, reinterpret_cast<const void *const *>(x), IA_F32, channels,
+                                 groups, workspace, workspace_bytes, stream);
 }
 
 int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int groups,
                        const float *gamma, const float *beta, float eps, int relu,
                        const void *workspace, size_t workspace_bytes, void *stream)
 {
-    ia::GnArgs a;
-    int rc = ia::gn_args(g, channels, groups, a);
-    if (rc) return rc;
-    if (!x || !workspace || !gamma || !beta || !(eps >= 0.0f)) return IA_E_ARG;
-    if (workspace_bytes < ia_groupnorm_workspace_bytes(g, channels, groups)) return IA_E_WORKSPACE;
-    for (int l = 0; l < g->num_levels; ++l) {
-        if (!x[l] || ((uintptr_t)x[l] & 15u)) return IA_E_ARG;
-        a.x[l] = x[l];
-    }
-    a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu ? 1 : 0;
-    a.part = const_cast<double2 *>(static_cast<const double2 *>(workspace));
-    hipLaunchKernelGGL(ia::k_gn_apply, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]), dim3(ia::kGnThreads),
-                       0, (hipStream_t)stream, a);
-    return ia::hip_status(hipGetLastError());
+    return ia_groupnorm_apply_dt(g, reinterpret_cast<void *const *>(x), IA_F32, channels, groups,
+                                 gamma, beta, eps, relu, workspace, workspace_bytes, stream);
 }
 
 

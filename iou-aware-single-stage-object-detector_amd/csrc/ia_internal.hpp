@@ -171,6 +171,7 @@ int launch_nms_single(const float *dets, int n, float iou_thr, int32_t *keep, in
 // kind 0: IoU-aware fused score; kind 1: plain FCOS, sigmoid(cls) * sigmoid(centerness) where
 // sigmoid(cls) > score_thr, else kPointCtrSentinel -- the NMS stages behind it then run with
 // score threshold kPointCtrStageThr, which every product (>= 0) passes and no sentinel does.
+// dtype: IA_F32 / IA_BF16 storage of the three maps.
 constexpr float kPointCtrSentinel = -1.0f;
 constexpr float kPointCtrStageThr = -0.5f;
 int point_head_geom(const ia_point_head_geom *pg, ia_head_geom &g);
@@ -178,7 +179,7 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
                         int batch, const float *img_hw, const float *scale_factor, int rescale,
                         float *rowmax, int32_t *cand_idx, void *select_ws, float *boxes,
                         float *scores_t, float *best_score, int Rs, int kind, float score_thr,
-                        hipStream_t s);
+                        int dtype, hipStream_t s);
 
 // the IoU maps the score kind needs: every level's iou pointer set (IoU-aware kinds) or every one
 // NULL (IA_CLS_*_NOIOU)

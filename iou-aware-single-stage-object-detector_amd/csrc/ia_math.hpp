@@ -151,6 +151,31 @@ __device__ __forceinline__ float ordered_key_inv(uint32_t k)
 // bf16 (raw bits) -> fp32
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return from_bits((uint32_t)h << 16); }
 
+// fp32 -> bf16 (raw bits), round to nearest even; a NaN stays a (quiet) NaN
+__device__ __forceinline__ uint32_t f32_to_bf16(float f)
+{
+    const uint32_t u = to_bits(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// 16 bytes of bf16 <-> eight floats (element j of the vector = channel j)
+__device__ __forceinline__ void bf16x8_to_f32(const uint4 &q, float (&v)[8])
+{
+    v[0] = from_bits(q.x << 16); v[1] = from_bits(q.x & 0xffff0000u);
+    v[2] = from_bits(q.y << 16); v[3] = from_bits(q.y & 0xffff0000u);
+    v[4] = from_bits(q.z << 16); v[5] = from_bits(q.z & 0xffff0000u);
+    v[6] = from_bits(q.w << 16); v[7] = from_bits(q.w & 0xffff0000u);
+}
+__device__ __forceinline__ uint4 f32_to_bf16x8(const float (&v)[8])
+{
+    uint4 q;
+    q.x = f32_to_bf16(v[0]) | (f32_to_bf16(v[1]) << 16);
+    q.y = f32_to_bf16(v[2]) | (f32_to_bf16(v[3]) << 16);
+    q.z = f32_to_bf16(v[4]) | (f32_to_bf16(v[5]) << 16);
+    q.w = f32_to_bf16(v[6]) | (f32_to_bf16(v[7]) << 16);
+    return q;
+}
+
 template <typename T> __device__ __forceinline__ float load_f32(const T *p);
 template <> __device__ __forceinline__ float load_f32<float>(const float *p) { return *p; }
 template <> __device__ __forceinline__ float load_f32<uint16_t>(const uint16_t *p) { return bf16_to_f32(*p); }

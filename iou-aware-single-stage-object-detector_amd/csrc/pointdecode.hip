@@ -15,7 +15,10 @@
 //                    (px - l, py - t, px + r, py + b) with px = x * stride + stride / 2, clamped to
 //                    [0, w-1] x [0, h-1], divided by scale_factor when rescaling.
 //
-// Both kernels are templates on the score kind (launch-uniform):
+// Both kernels are templates on the storage type of the three maps (float, or uint16_t = bf16 raw
+// bits: a load converts exactly to fp32 and everything behind it is the fp32 arithmetic, so bf16
+// maps give the bits of their fp32 copies; the channels-last class row is then 8 values per
+// 16-byte vector) and on the score kind (launch-uniform):
 //   kPointIouAware   the fused score above (the third map is the IoU logit);
 //   kPointCtr        plain FCOS: the third map is the centerness logit.  Row max
 //                    max_c(sigmoid(x_c) * sigmoid(ctr)) (fp32 product, the reference's max_scores);
@@ -45,31 +48,37 @@ struct PointArgs {
 // score kinds (template parameter of the two kernels)
 constexpr int kPointIouAware = 0, kPointCtr = 1;
 
-struct PointLevel { int l, base, H, W, stride; const float *cls, *reg, *iou; };   // iou: or centerness
+template <typename T>
+struct PointLevel { int l, base, H, W, stride; const T *cls, *reg, *iou; };   // iou: or centerness
 
 // level of an index into a prefix table (the per-level scalars through selects: scalar kernarg
 // loads, no per-lane indexing of the argument block)
-__device__ __forceinline__ PointLevel point_level(const PointArgs &a, const int32_t *off, int i)
+template <typename T>
+__device__ __forceinline__ PointLevel<T> point_level(const PointArgs &a, const int32_t *off, int i)
 {
-    PointLevel s;
+    PointLevel<T> s;
     s.l = 0;
 #pragma unroll
     for (int k = 1; k < IA_MAX_LEVELS; ++k) s.l += (k < a.t.num_levels && i >= off[k]) ? 1 : 0;
     s.base = off[0]; s.H = a.t.H[0]; s.W = a.t.W[0]; s.stride = a.t.stride[0];
-    s.cls = static_cast<const float *>(a.p.cls[0]);
-    s.reg = static_cast<const float *>(a.p.reg[0]);
-    s.iou = static_cast<const float *>(a.p.iou[0]);
+    s.cls = static_cast<const T *>(a.p.cls[0]);
+    s.reg = static_cast<const T *>(a.p.reg[0]);
+    s.iou = static_cast<const T *>(a.p.iou[0]);
 #pragma unroll
     for (int k = 1; k < IA_MAX_LEVELS; ++k) {
         const bool m = s.l == k;
         s.base = m ? off[k] : s.base;
         s.H = m ? a.t.H[k] : s.H; s.W = m ? a.t.W[k] : s.W; s.stride = m ? a.t.stride[k] : s.stride;
-        s.cls = m ? static_cast<const float *>(a.p.cls[k]) : s.cls;
-        s.reg = m ? static_cast<const float *>(a.p.reg[k]) : s.reg;
-        s.iou = m ? static_cast<const float *>(a.p.iou[k]) : s.iou;
+        s.cls = m ? static_cast<const T *>(a.p.cls[k]) : s.cls;
+        s.reg = m ? static_cast<const T *>(a.p.reg[k]) : s.reg;
+        s.iou = m ? static_cast<const T *>(a.p.iou[k]) : s.iou;
     }
     return s;
 }
+
+// a stored value as fp32 (bf16: exact)
+__device__ __forceinline__ float point_f32(float v) { return v; }
+__device__ __forceinline__ float point_f32(uint16_t v) { return bf16_to_f32(v); }
 
 // the per-point factor of the score: powf(sigmoid(iou), 1 - alpha), or sigmoid(centerness)
 template <int KIND>
@@ -84,56 +93,97 @@ __device__ __forceinline__ float point_score(float x, float fi, float alpha)
     return KIND == kPointCtr ? sigmoidf_(x) * fi : powf_pos_(sigmoidf_(x), alpha) * fi;
 }
 
-template <int KIND>
+template <int KIND, typename T>
 __global__ void __launch_bounds__(256) k_point_rowmax(PointArgs a)
 {
     const int N = a.t.anchor_off[a.t.num_levels];
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (int64_t)a.batch * N) return;
     const int b = (int)(gid / N), i = (int)(gid - (int64_t)b * N);
-    const PointLevel lv = point_level(a, a.t.anchor_off, i);
+    const PointLevel<T> lv = point_level<T>(a, a.t.anchor_off, i);
     const int pos = i - lv.base, HW = lv.H * lv.W, C = a.t.C;
-    const float fi = point_factor<KIND>(lv.iou[(size_t)b * HW + pos], a.beta);
+    const float fi = point_factor<KIND>(point_f32(lv.iou[(size_t)b * HW + pos]), a.beta);
     float best = 0.0f;                       // scores are >= 0
     if (a.t.layout == IA_LAYOUT_NHWC) {
-        const float4 *row = reinterpret_cast<const float4 *>(lv.cls + ((size_t)b * HW + pos) * C);
-        for (int v = 0; v < C / 4; ++v) {
-            const float4 q = row[v];
-            float sc = point_score<KIND>(q.x, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score<KIND>(q.y, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score<KIND>(q.z, fi, a.alpha); best = (best < sc) ? sc : best;
-            sc = point_score<KIND>(q.w, fi, a.alpha); best = (best < sc) ? sc : best;
+        if constexpr (sizeof(T) == 2) {
+            const uint4 *row = reinterpret_cast<const uint4 *>(lv.cls + ((size_t)b * HW + pos) * C);
+            for (int v = 0; v < C / 8; ++v) {
+                float f[8];
+                bf16x8_to_f32(row[v], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float sc = point_score<KIND>(f[j], fi, a.alpha);
+                    best = (best < sc) ? sc : best;
+                }
+            }
+        } else {
+            const float4 *row = reinterpret_cast<const float4 *>(lv.cls + ((size_t)b * HW + pos) * C);
+            for (int v = 0; v < C / 4; ++v) {
+                const float4 q = row[v];
+                float sc = point_score<KIND>(q.x, fi, a.alpha); best = (best < sc) ? sc : best;
+                sc = point_score<KIND>(q.y, fi, a.alpha); best = (best < sc) ? sc : best;
+                sc = point_score<KIND>(q.z, fi, a.alpha); best = (best < sc) ? sc : best;
+                sc = point_score<KIND>(q.w, fi, a.alpha); best = (best < sc) ? sc : best;
+            }
         }
     } else {
-        const float *cls = lv.cls + (size_t)b * C * HW + pos;
+        const T *cls = lv.cls + (size_t)b * C * HW + pos;
         for (int c = 0; c < C; ++c) {
-            const float sc = point_score<KIND>(cls[(size_t)c * HW], fi, a.alpha);
+            const float sc = point_score<KIND>(point_f32(cls[(size_t)c * HW]), fi, a.alpha);
             best = (best < sc) ? sc : best;
         }
     }
     a.rowmax[(size_t)b * N + i] = best;
 }
 
-template <int KIND>
+template <int KIND, typename T>
 __global__ void __launch_bounds__(256) k_point_gather(PointArgs a)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (r >= a.R) return;
-    const PointLevel lv = point_level(a, a.t.cand_off, r);
+    const PointLevel<T> lv = point_level<T>(a, a.t.cand_off, r);
     const int HW = lv.H * lv.W, C = a.t.C;
     const int pos = a.cand_idx[(size_t)b * a.R + r];
     const bool nhwc = a.t.layout == IA_LAYOUT_NHWC;
     const size_t cs = nhwc ? (size_t)1 : (size_t)HW;
-    const float fi = point_factor<KIND>(lv.iou[(size_t)b * HW + pos], a.beta);
-    const float *cls = lv.cls + (nhwc ? ((size_t)b * HW + pos) * C : (size_t)b * C * HW + pos);
+    const float fi = point_factor<KIND>(point_f32(lv.iou[(size_t)b * HW + pos]), a.beta);
+    const T *cls = lv.cls + (nhwc ? ((size_t)b * HW + pos) * C : (size_t)b * C * HW + pos);
     float *so = a.scores_t + (size_t)b * C * a.Rs + r;
-    if (KIND == kPointCtr) {
+    bool done = false;                       // fp32: constant, the loops below are all there is
+    if constexpr (sizeof(T) == 2) {
+        if (nhwc) {
+            // bf16 channels-last: the candidate's class row in 16-byte vectors of 8, the classes
+            // in index order through the expressions of the loops below
+            float best = KIND == kPointCtr ? kPointCtrSentinel : 0.0f;
+            const uint4 *row = reinterpret_cast<const uint4 *>(cls);
+            for (int v = 0; v < C / 8; ++v) {
+                float f[8];
+                bf16x8_to_f32(row[v], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float sc;
+                    if (KIND == kPointCtr) {
+                        const float s = sigmoidf_(f[j]);
+                        sc = (s > a.score_thr) ? s * fi : kPointCtrSentinel;
+                    } else {
+                        sc = point_score<KIND>(f[j], fi, a.alpha);
+                    }
+                    so[(size_t)(8 * v + j) * a.Rs] = sc;
+                    best = (best < sc) ? sc : best;
+                }
+            }
+            if (a.best_score) a.best_score[(size_t)b * a.R + r] = best;
+            done = true;
+        }
+    }
+    if (done) {
+    } else if (KIND == kPointCtr) {
         // raw-score threshold, then the product; best = max of what was written (the sentinel
         // when no class passes: the row then stays out of k_adj's relation)
         float best = kPointCtrSentinel;
         for (int c = 0; c < C; ++c) {
-            const float s = sigmoidf_(cls[(size_t)c * cs]);
+            const float s = sigmoidf_(point_f32(cls[(size_t)c * cs]));
             const float sc = (s > a.score_thr) ? s * fi : kPointCtrSentinel;
             so[(size_t)c * a.Rs] = sc;
             best = (best < sc) ? sc : best;
@@ -142,16 +192,17 @@ __global__ void __launch_bounds__(256) k_point_gather(PointArgs a)
     } else {
         float best = 0.0f;
         for (int c = 0; c < C; ++c) {
-            const float sc = point_score<KIND>(cls[(size_t)c * cs], fi, a.alpha);
+            const float sc = point_score<KIND>(point_f32(cls[(size_t)c * cs]), fi, a.alpha);
             so[(size_t)c * a.Rs] = sc;
             best = (best < sc) ? sc : best;
         }
         if (a.best_score) a.best_score[(size_t)b * a.R + r] = best;
     }
-    const float *reg = lv.reg + (nhwc ? ((size_t)b * HW + pos) * 4 : (size_t)b * 4 * HW + pos);
+    const T *reg = lv.reg + (nhwc ? ((size_t)b * HW + pos) * 4 : (size_t)b * 4 * HW + pos);
     const int y = pos / lv.W, x = pos - y * lv.W;
     const float px = (float)(x * lv.stride + lv.stride / 2), py = (float)(y * lv.stride + lv.stride / 2);
-    float x1 = px - reg[0], y1 = py - reg[cs], x2 = px + reg[2 * cs], y2 = py + reg[3 * cs];
+    float x1 = px - point_f32(reg[0]), y1 = py - point_f32(reg[cs]);
+    float x2 = px + point_f32(reg[2 * cs]), y2 = py + point_f32(reg[3 * cs]);
     // clamp(min=0, max=w-1): comparisons, so a NaN stays NaN like torch.clamp
     const float mx = a.img_hw[2 * b + 1] - 1.0f, my = a.img_hw[2 * b] - 1.0f;
     x1 = (x1 < 0.0f) ? 0.0f : x1;  x1 = (x1 > mx) ? mx : x1;
@@ -193,10 +244,14 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
                         int batch, const float *img_hw, const float *scale_factor, int rescale,
                         float *rowmax, int32_t *cand_idx, void *select_ws, float *boxes,
                         float *scores_t, float *best_score, int Rs, int kind, float score_thr,
-                        hipStream_t s)
+                        int dtype, hipStream_t s)
 {
     if (batch < 1 || !img_hw || (rescale && !scale_factor)) return IA_E_ARG;
     if (kind != kPointIouAware && kind != kPointCtr) return IA_E_ARG;
+    if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
+    const bool bf = dtype == IA_BF16;
+    // channels-last bf16: the class row in whole 16-byte vectors
+    if (bf && t.layout == IA_LAYOUT_NHWC && t.C % 8 != 0) return IA_E_ARG;
     PointArgs a;
     a.t = t; a.p = p;
     a.alpha = pg->score_alpha; a.beta = 1.0f - pg->score_alpha;
@@ -209,19 +264,25 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
         if (t.layout == IA_LAYOUT_NHWC && ((uintptr_t)p.cls[l] & 15u)) return IA_E_ARG;
     }
     const int64_t n = (int64_t)batch * t.anchor_off[t.num_levels];
-    if (kind == kPointCtr)
-        hipLaunchKernelGGL(k_point_rowmax<kPointCtr>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(k_point_rowmax<kPointIouAware>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           s, a);
+    const dim3 rgrid((unsigned)((n + 255) / 256));
+    if (kind == kPointCtr) {
+        if (bf) hipLaunchKernelGGL((k_point_rowmax<kPointCtr, uint16_t>), rgrid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_point_rowmax<kPointCtr, float>), rgrid, dim3(256), 0, s, a);
+    } else {
+        if (bf) hipLaunchKernelGGL((k_point_rowmax<kPointIouAware, uint16_t>), rgrid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_point_rowmax<kPointIouAware, float>), rgrid, dim3(256), 0, s, a);
+    }
     int rc = hip_status(hipGetLastError());
     if (rc) return rc;
     if ((rc = launch_select(t, rowmax, batch, cand_idx, select_ws, s, false))) return rc;
     const dim3 grid((unsigned)((a.R + 255) / 256), (unsigned)batch);
-    if (kind == kPointCtr)
-        hipLaunchKernelGGL(k_point_gather<kPointCtr>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(k_point_gather<kPointIouAware>, grid, dim3(256), 0, s, a);
+    if (kind == kPointCtr) {
+        if (bf) hipLaunchKernelGGL((k_point_gather<kPointCtr, uint16_t>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_point_gather<kPointCtr, float>), grid, dim3(256), 0, s, a);
+    } else {
+        if (bf) hipLaunchKernelGGL((k_point_gather<kPointIouAware, uint16_t>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_point_gather<kPointIouAware, float>), grid, dim3(256), 0, s, a);
+    }
     return hip_status(hipGetLastError());
 }
 

@@ -229,6 +229,10 @@ SIGNATURES = {
     'ia_groupnorm_workspace_bytes': (_sz, [_WG, _i, _i]),
     'ia_groupnorm_stats': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _sz, _vp]),
     'ia_groupnorm_apply': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),
+    'ia_groupnorm_workspace_bytes_dt': (_sz, [_WG, _i, _i, _i]),
+    'ia_groupnorm_stats_dt': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _i, _vp, _sz, _vp]),
+    'ia_groupnorm_apply_dt': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz,
+                                   _vp]),
     'ia_groupnorm_saved_bytes': (_sz, [_WG, _i, _i]),
     'ia_groupnorm_apply_to': (_i, [_WG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _vp, _vp, _f,
                                    _i, _vp, _sz, _vp, _sz, _vp]),
@@ -239,6 +243,7 @@ SIGNATURES = {
                                     C.POINTER(C.c_void_p), _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp,
                                     _vp, _vp]),
     'ia_scale_exp_levels': (_i, [_WG, C.POINTER(C.c_void_p), _i, _vp, _vp]),
+    'ia_scale_exp_levels_dt': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _vp]),
     'ia_point_workspace_bytes': (_sz, [_PG, _i]),
     'ia_point_workspace_layout': (_i, [_PG, _i, C.POINTER(_sz * 8)]),
     'ia_point_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _vp, _sz, _vp]),
@@ -247,6 +252,12 @@ SIGNATURES = {
     'ia_point_ctr_decode_stage': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _vp, _sz, _vp]),
     'ia_point_ctr_get_bboxes': (_i, [_PG, _P, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp,
                                      _vp, _vp, _vp]),
+    'ia_point_decode_stage_dt': (_i, [_PG, _P, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    'ia_point_get_bboxes_dt': (_i, [_PG, _P, _i, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp, _vp,
+                                    _vp, _vp, _vp]),
+    'ia_point_ctr_decode_stage_dt': (_i, [_PG, _P, _i, _i, _vp, _vp, _i, _f, _vp, _sz, _vp]),
+    'ia_point_ctr_get_bboxes_dt': (_i, [_PG, _P, _i, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _sz, _vp,
+                                        _vp, _vp, _vp, _vp]),
     'ia_point_packed_labels_elems': (_sz, [_PG, _i]),
     'ia_point_targets_ptrs': (_i, [_PG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_int32), _i, C.POINTER(C.c_float), _vp, _vp, _vp,

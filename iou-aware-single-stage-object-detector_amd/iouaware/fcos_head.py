@@ -7,10 +7,13 @@ constructor kwargs, parameter names and method signatures.
     winograd_train.fcos_usable holds) forward instead runs every tower convolution as one
     Winograd autograd node over all levels and every GroupNorm + ReLU as one HIP node with a HIP
     backward (fcos_ops.groupnorm_relu); at inference `fuse.fuse_inference(winograd=True)` swaps
-    in the Winograd runner with the in-place HIP GroupNorm + ReLU (winograd.WinogradFCOSHead);
+    in the Winograd runner with the in-place HIP GroupNorm + ReLU (winograd.WinogradFCOSHead)
+    and, for bf16 channels-last features, the MFMA convolution towers with the bf16 GroupNorm +
+    ReLU (conv3x3_bf16.Bf16ConvFCOSHead);
   * get_bboxes: one call into the HIP library for the whole batch (row max, per-level top-k,
     distance2bbox, batched NMS): ia_point_get_bboxes with the fused alpha score (IoU-aware),
-    ia_point_ctr_get_bboxes with the raw-threshold / centerness-product scores (plain);
+    ia_point_ctr_get_bboxes with the raw-threshold / centerness-product scores (plain); fp32 or
+    bf16 maps (the _dt entries);
   * loss: point targets and all terms of every level on HIP kernels (fcos_ops.point_targets,
     fcos_ops.point_head_loss: csrc/pointloss.hip), no host synchronisation; `fuse_loss = False`, or
     inputs the node does not cover (see _fused_loss_ok), take the torch transcription of the

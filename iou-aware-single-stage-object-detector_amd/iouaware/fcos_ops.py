@@ -43,7 +43,12 @@ class PointGeometry(_LayoutTwin):
         return C.byref(self.struct)
 
 
+_DTYPES = {torch.float32: _lib.IA_F32, torch.bfloat16: _lib.IA_BF16}
+
+
 def _point_ptrs(geom, cls, reg, iou, third='iou_pred'):
+    """-> (level pointers, batch, geometry in the maps' layout, dtype code); the maps are fp32 or
+    bf16, all of one dtype"""
     if not (len(cls) == len(reg) == len(iou) == geom.L):
         raise AssertionError('expected %d levels' % geom.L)
     B = cls[0].shape[0]
@@ -56,9 +61,10 @@ def _point_ptrs(geom, cls, reg, iou, third='iou_pred'):
             if tuple(t.shape) != (B, ch, h, w):
                 raise AssertionError('%s level %d has shape %s, expected %s'
                                      % (name, l, tuple(t.shape), (B, ch, h, w)))
-            if t.dtype != torch.float32:
-                raise TypeError('the point-head decode takes fp32 head outputs')
-    nhwc = (geom.C * 4) % 16 == 0 and not all(t.is_contiguous() for t in tensors) and all(
+            if t.dtype not in _DTYPES or t.dtype != cls[0].dtype:
+                raise TypeError('the point-head decode takes fp32 or bf16 head outputs, all of '
+                                'one dtype')
+    nhwc = (geom.C * cls[0].element_size()) % 16 == 0 and not all(t.is_contiguous() for t in tensors) and all(
         t.is_contiguous(memory_format=torch.channels_last) for t in tensors)
     geom = geom.with_layout(_lib.IA_LAYOUT_NHWC if nhwc else _lib.IA_LAYOUT_NCHW)
     p = LevelPtrs()
@@ -66,7 +72,7 @@ def _point_ptrs(geom, cls, reg, iou, third='iou_pred'):
         if not nhwc:
             cls[l], reg[l], iou[l] = to_nchw(cls[l]), to_nchw(reg[l]), to_nchw(iou[l])
         p.cls[l], p.reg[l], p.iou[l] = cls[l].data_ptr(), reg[l].data_ptr(), iou[l].data_ptr()
-    return p, B, geom
+    return p, B, geom, _DTYPES[cls[0].dtype]
 
 
 def _workspace(geom, B, dev):
@@ -85,13 +91,13 @@ def point_decode_stage(geom, cls, reg, iou, img_shapes, scale_factors, rescale):
     """decode stage only (row max, top-k, gather / distance2bbox) -> dict of workspace views
     rowmax (B,N), cand_idx (B,R), boxes (B,R,4), scores_t (B,C,Rs), best_score (B,R)"""
     cls, reg, iou = list(cls), list(reg), list(iou)
-    p, B, geom = _point_ptrs(geom, cls, reg, iou)
+    p, B, geom, dt = _point_ptrs(geom, cls, reg, iou)
     dev = cls[0].device
     nbytes, ws = _workspace(geom, B, dev)
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
-    _lib.check(_lib.lib().ia_point_decode_stage(geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf),
-                                                int(bool(rescale)), _ptr(ws), nbytes, _stream()),
-               'ia_point_decode_stage')
+    _lib.check(_lib.lib().ia_point_decode_stage_dt(geom.ref(), C.byref(p), B, dt, _ptr(hw), _ptr(sf),
+                                                   int(bool(rescale)), _ptr(ws), nbytes, _stream()),
+               'ia_point_decode_stage_dt')
     return _views(geom, B, ws)
 
 
@@ -99,14 +105,14 @@ def point_ctr_decode_stage(geom, cls, reg, ctr, img_shapes, scale_factors, resca
     """plain FCOS decode stage -> the views of point_decode_stage; scores_t holds
     sigmoid(cls) * sigmoid(ctr) where sigmoid(cls) > score_thr and a negative sentinel elsewhere"""
     cls, reg, ctr = list(cls), list(reg), list(ctr)
-    p, B, geom = _point_ptrs(geom, cls, reg, ctr, 'centerness')
+    p, B, geom, dt = _point_ptrs(geom, cls, reg, ctr, 'centerness')
     dev = cls[0].device
     nbytes, ws = _workspace(geom, B, dev)
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
-    _lib.check(_lib.lib().ia_point_ctr_decode_stage(geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf),
-                                                    int(bool(rescale)), float(score_thr), _ptr(ws),
-                                                    nbytes, _stream()),
-               'ia_point_ctr_decode_stage')
+    _lib.check(_lib.lib().ia_point_ctr_decode_stage_dt(geom.ref(), C.byref(p), B, dt, _ptr(hw),
+                                                       _ptr(sf), int(bool(rescale)),
+                                                       float(score_thr), _ptr(ws), nbytes, _stream()),
+               'ia_point_ctr_decode_stage_dt')
     return _views(geom, B, ws)
 
 
@@ -115,13 +121,13 @@ def _get_bboxes(entry, third, geom, cls, reg, iou, img_shapes, scale_factors, re
     if max_per_img > _lib.IA_MAX_PER_IMG:
         raise _lib.IouAwareLibraryError('max_per_img above %d' % _lib.IA_MAX_PER_IMG)
     cls, reg, iou = list(cls), list(reg), list(iou)
-    p, B, geom = _point_ptrs(geom, cls, reg, iou, third)
+    p, B, geom, dt = _point_ptrs(geom, cls, reg, iou, third)
     dev = cls[0].device
     nbytes, ws = _workspace(geom, B, dev)
     hw, sf = _meta_tensors(img_shapes, scale_factors, dev)
     dets, labels, rows, num = _det_outputs(B, max_per_img, dev)
     _lib.check(getattr(_lib.lib(), entry)(
-        geom.ref(), C.byref(p), B, _ptr(hw), _ptr(sf), int(bool(rescale)), float(score_thr),
+        geom.ref(), C.byref(p), B, dt, _ptr(hw), _ptr(sf), int(bool(rescale)), float(score_thr),
         float(iou_thr), int(max_per_img), 0 if lazy else -1, _ptr(ws), nbytes, _ptr(dets),
         _ptr(labels), _ptr(rows), _ptr(num), _stream()), entry)
     if not debug:
@@ -131,10 +137,10 @@ def _get_bboxes(entry, third, geom, cls, reg, iou, img_shapes, scale_factors, re
 
 def point_get_bboxes(geom, cls, reg, iou, img_shapes, scale_factors, rescale, score_thr, iou_thr,
                      max_per_img, lazy=True, debug=False):
-    """Whole post-conv path of the point head for a batch -> device tensors dets (B,max,5),
+    """Whole post-conv path of the point head for a batch (fp32 or bf16 maps) -> device tensors dets (B,max,5),
     labels (B,max) int32, rows (B,max) int32 (candidate rows), num (B) int32 (+ the decode-stage
     views with debug=True)."""
-    return _get_bboxes('ia_point_get_bboxes', 'iou_pred', geom, cls, reg, iou, img_shapes,
+    return _get_bboxes('ia_point_get_bboxes_dt', 'iou_pred', geom, cls, reg, iou, img_shapes,
                        scale_factors, rescale, score_thr, iou_thr, max_per_img, lazy, debug)
 
 
@@ -143,7 +149,7 @@ def point_ctr_get_bboxes(geom, cls, reg, ctr, img_shapes, scale_factors, rescale
     """point_get_bboxes for plain FCOS (ia_point_ctr_get_bboxes): the raw score sigmoid(cls) is
     thresholded, NMS and the final sort run on sigmoid(cls) * sigmoid(ctr); geom.score_alpha is
     not used."""
-    return _get_bboxes('ia_point_ctr_get_bboxes', 'centerness', geom, cls, reg, ctr, img_shapes,
+    return _get_bboxes('ia_point_ctr_get_bboxes_dt', 'centerness', geom, cls, reg, ctr, img_shapes,
                        scale_factors, rescale, score_thr, iou_thr, max_per_img, lazy, debug)
 
 
@@ -164,38 +170,61 @@ def _gn_workspace(dev, nbytes):
 
 
 def groupnorm_relu_(xs, gamma, beta, groups, eps=1e-5, relu=True):
-    """In place over the levels xs[l] (B, ch, H_l, W_l) fp32 channels-last: GroupNorm (statistics
-    per level and image) + ReLU, two launches for all of them.  gamma / beta (ch,) fp32."""
+    """In place over the levels xs[l] (B, ch, H_l, W_l) channels-last, all fp32 or all bf16:
+    GroupNorm (statistics per level and image) + ReLU, two launches for all of them.  gamma / beta
+    (ch,) fp32.  bf16: fp64 statistics of the stored values, fp32 x * s + t, one rounding."""
     for x in xs:
         _require_gpu(x, 'x')
-    ch = _gn_check('groupnorm_relu_', xs, gamma, beta)
+    dtype = xs[0].dtype if xs and xs[0].dtype in _DTYPES else torch.float32
+    ch = _gn_check('groupnorm_relu_', xs, gamma, beta, dtype)
+    dt = _DTYPES[dtype]
     g = _wino_geom(xs)
     L = _lib.lib()
-    nbytes = L.ia_groupnorm_workspace_bytes(C.byref(g), ch, int(groups))
+    nbytes = L.ia_groupnorm_workspace_bytes_dt(C.byref(g), ch, int(groups), dt)
     if nbytes == 0:
-        raise _lib.IouAwareLibraryError('unsupported GroupNorm geometry (channels %d, groups %d)'
-                                        % (ch, groups))
+        raise _lib.IouAwareLibraryError('unsupported GroupNorm geometry (channels %d, groups %d, %s)'
+                                        % (ch, groups, dtype))
     ws = _gn_workspace(xs[0].device, nbytes)
     ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-    _lib.check(L.ia_groupnorm_stats(C.byref(g), ptrs, ch, int(groups), _ptr(ws), nbytes, _stream()),
-               'ia_groupnorm_stats')
-    _lib.check(L.ia_groupnorm_apply(C.byref(g), ptrs, ch, int(groups), _ptr(gamma), _ptr(beta),
-                                    float(eps), int(bool(relu)), _ptr(ws), nbytes, _stream()),
-               'ia_groupnorm_apply')
+    _lib.check(L.ia_groupnorm_stats_dt(C.byref(g), ptrs, dt, ch, int(groups), _ptr(ws), nbytes,
+                                       _stream()), 'ia_groupnorm_stats_dt')
+    _lib.check(L.ia_groupnorm_apply_dt(C.byref(g), ptrs, dt, ch, int(groups), _ptr(gamma), _ptr(beta),
+                                       float(eps), int(bool(relu)), _ptr(ws), nbytes, _stream()),
+               'ia_groupnorm_apply_dt')
     return xs
 
 
-def _gn_check(name, xs, gamma, beta):
+def scale_exp_(xs, scales):
+    """In place over the levels xs[l] (B, ch, H_l, W_l) channels-last, all fp32 or all bf16 (ch % 4
+    == 0): exp(scales[l] * x), the FCOS regression epilogue; scales (L,) fp32 on the device.  bf16:
+    the fp32 evaluation, rounded once."""
+    for x in xs:
+        _require_gpu(x, 'x')
+        if x.dtype not in _DTYPES or x.dtype != xs[0].dtype or x.dim() != 4 \
+                or not x.is_contiguous(memory_format=torch.channels_last):
+            raise ValueError('scale_exp_ takes fp32 or bf16 channels-last levels of one dtype')
+    if scales.dtype != torch.float32 or scales.numel() < len(xs) or not scales.is_contiguous():
+        raise ValueError('scales: one fp32 value per level')
+    g = _wino_geom(xs)
+    ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+    _lib.check(_lib.lib().ia_scale_exp_levels_dt(C.byref(g), ptrs, _DTYPES[xs[0].dtype],
+                                                 int(xs[0].shape[1]), _ptr(scales), _stream()),
+               'ia_scale_exp_levels_dt')
+    return xs
+
+
+def _gn_check(name, xs, gamma, beta, dtype=torch.float32):
     """the argument contract of groupnorm_relu_ / groupnorm_relu: ValueError before the device is
-    touched -> channels"""
+    touched -> channels.  dtype: what the levels hold (the training node: fp32 only)"""
     if not xs or len(xs) > _lib.IA_MAX_LEVELS:
         raise ValueError('1..%d levels' % _lib.IA_MAX_LEVELS)
     ch = int(xs[0].shape[1]) if xs[0].dim() == 4 else -1
     for x in xs:
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != ch \
+        if not x.is_cuda or x.dtype != dtype or x.dim() != 4 or x.shape[1] != ch \
                 or x.shape[0] != xs[0].shape[0] or x.device != xs[0].device \
                 or not x.is_contiguous(memory_format=torch.channels_last):
-            raise ValueError('%s takes fp32 channels-last (B, %d, H, W) levels on one device' % (name, ch))
+            raise ValueError('%s takes %s channels-last (B, %d, H, W) levels on one device'
+                             % (name, 'fp32' if dtype == torch.float32 else 'fp32 or bf16', ch))
     for t in (gamma, beta):
         if t.dtype != torch.float32 or t.numel() != ch or not t.is_contiguous() or t.device != xs[0].device:
             raise ValueError('gamma / beta: (%d,) fp32 on the device' % ch)

@@ -435,15 +435,30 @@ def _head_forward(self, feats):
 
 
 def _fcos_head_forward(self, feats):
-    """IoUawareFCOSHead / FCOSHead at inference (eval, no grad, fp32 channels-last): the Winograd
-    towers with the HIP GroupNorm + ReLU (winograd.WinogradFCOSHead); anything else: the module's
-    forward"""
+    """IoUawareFCOSHead / FCOSHead at inference (eval, no grad, channels-last).  fp32: the Winograd
+    towers with the HIP GroupNorm + ReLU (winograd.WinogradFCOSHead); bf16: the MFMA convolution
+    towers with the HIP bf16 GroupNorm + ReLU (conv3x3_bf16.Bf16ConvFCOSHead); anything else: the
+    module's forward"""
     w = self._ia_wino
     if (not self.training) and w.usable(feats):
         if getattr(self, '_ia_dirty', False) or self._ia_stamp != _stamp(self):
             _fold(self)
             w = self._ia_wino
         return w(list(feats))
+    if (not self.training) and _bf16_head_ok(feats):
+        # bf16: tower convolutions on the MFMA implicit-GEMM kernel, HIP bf16 GroupNorm + ReLU
+        if getattr(self, '_ia_dirty', False) or self._ia_stamp != _stamp(self):
+            _fold(self)
+        c3 = getattr(self, '_ia_c3', None)
+        if c3 is None:
+            from .conv3x3_bf16 import Bf16ConvFCOSHead
+            try:
+                c3 = Bf16ConvFCOSHead(self)
+            except (NotImplementedError, ValueError):
+                c3 = False
+            self._ia_c3 = c3
+        if c3 and c3.usable(feats):
+            return c3(feats)
     if self.training or torch.is_grad_enabled():
         _mark_dirty(self)
     return type(self).forward(self, feats)
@@ -489,6 +504,7 @@ def _fold(m):
     elif type(m).__name__ in ('IoUawareFCOSHead', 'FCOSHead'):
         from .winograd import WinogradFCOSHead
         m._ia_wino = WinogradFCOSHead(m)
+        m._ia_c3 = None                           # bf16 weights are packed on the first bf16 call
     elif isinstance(m, Bottleneck):
         f = {}
         f['s1'], f['b1'] = _fold_bn(m.norm1)

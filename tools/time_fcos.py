@@ -6,7 +6,13 @@ towers + the HIP GroupNorm + ReLU), and the GroupNorm kernels alone on one tower
 activations (both towers, 512 channels, all five levels) with their share of the HBM bound.
 
     python tools/time_fcos.py [--head {iou_aware,plain}] [--batch 8] [--iters 20] [--warmup 5]
-                              [--out results.json]
+                              [--dtype {fp32,bf16}] [--out results.json]
+
+--dtype bf16 times three variants in alternation, three runs each (medians and their range): the
+fused fp32 route; the bf16 network (fuse_inference(winograd=True), channels-last, .to(bfloat16))
+with the head on the module forward (eager bf16 convolutions, torch GroupNorm / ReLU); and the same
+network with the bf16 head route (conv3x3_bf16.Bf16ConvFCOSHead).  Both bf16 variants decode their
+bf16 maps with the bf16 point entries.  Then the bf16 GroupNorm pair alone.
 
 Device events around the timed window, after warm-up of every shape; the detections of the two
 routes are compared on the same input (name-seeded weights, tests/synth_fcos.py)."""
@@ -65,16 +71,80 @@ def time_fn(fn, iters, warmup):
     return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
 
 
+def main_bf16(a):
+    """the three variants of --dtype bf16, alternating"""
+    import synth_fcos
+    from iouaware import fcos_ops
+    from iouaware.fuse import fuse_inference
+    B, pad_h, pad_w = a.batch, 800, 1344
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.standard_normal((B, 3, pad_h, pad_w)).astype(np.float32)).cuda()
+    x = x.contiguous(memory_format=torch.channels_last)
+    xb = x.to(torch.bfloat16)
+    meta = [dict(ori_shape=(800, 1333, 3), img_shape=(800, 1333, 3), pad_shape=(pad_h, pad_w, 3),
+                 scale_factor=1.0, flip=False)] * B
+    res = dict(batch=B, pad=[pad_h, pad_w], dtype='bf16', head=a.head)
+    m32, mb = build(head=a.head), build(head=a.head)
+    with torch.no_grad():
+        fuse_inference(m32, winograd=True)
+        fuse_inference(mb, winograd=True)
+        mb = mb.to(memory_format=torch.channels_last).to(torch.bfloat16)
+        head = mb.bbox_head
+        mb.simple_test_device(xb, meta, rescale=True)            # folds and packs the bf16 runner
+        runner = head._ia_c3
+        assert runner and runner.calls == 1, 'the bf16 head route was not taken'
+
+        def bf16_run(route):
+            head._ia_c3 = runner if route else False             # False: the module forward
+            return mb.simple_test_device(xb, meta, rescale=True)
+        variants = [('fused_fp32_ms', lambda: m32.simple_test_device(x, meta, rescale=True)),
+                    ('bf16_module_head_ms', lambda: bf16_run(False)),
+                    ('bf16_head_route_ms', lambda: bf16_run(True))]
+        for name, _ in variants:
+            res[name] = []
+        for _ in range(3):
+            for name, fn in variants:
+                res[name].append(time_fn(fn, a.iters, a.warmup)[0])
+        calls = runner.calls
+        _, _, _, n_mod = bf16_run(False)
+        assert runner.calls == calls
+        _, _, _, n_new = bf16_run(True)
+        assert runner.calls == calls + 1
+        _, _, _, n32 = m32.simple_test_device(x, meta, rescale=True)
+        res['num_dets'] = dict(fp32=n32.tolist(), bf16_module_head=n_mod.tolist(),
+                               bf16_head_route=n_new.tolist())
+        sizes = synth_fcos.level_shapes(pad_h, pad_w)
+        acts = [torch.randn((B, 512, h, w), device='cuda').to(torch.bfloat16).contiguous(
+            memory_format=torch.channels_last) for (h, w) in sizes]
+        gamma, beta = torch.ones(512, device='cuda'), torch.zeros(512, device='cuda')
+        act_bytes = sum(t.numel() for t in acts) * 2
+        med, lo, hi = time_fn(lambda: fcos_ops.groupnorm_relu_(acts, gamma, beta, 64), a.iters * 5,
+                              a.warmup)
+        res['gn_layer_us'] = [med * 1e3, lo * 1e3, hi * 1e3]
+        res['gn_activation_mb'] = act_bytes / 1e6
+        res['gn_hbm_fraction'] = 3 * act_bytes / HBM_PEAK / (med * 1e-3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--head', choices=sorted(HEADS), default='iou_aware')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--dtype', choices=('fp32', 'bf16'), default='fp32')
     ap.add_argument('--out', default=None, help='also write the JSON result to this file')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('time_fcos.py needs the MI355X')
+    if a.dtype == 'bf16':
+        res = main_bf16(a)
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as fh:
+                json.dump(res, fh, indent=1)
+        return
     import synth_fcos
     from iouaware import fcos_ops
     from iouaware.fuse import fuse_inference
