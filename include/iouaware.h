@@ -762,6 +762,47 @@ size_t ia_conv3x3_bf16_packed_bytes(int cin, int cout, int groups);
 int ia_conv3x3_bf16_pack(const void *w, int cin, int cout, int groups, void *wp, void *stream);
 int ia_conv3x3_bf16_levels(const ia_conv3x3_desc *d, const void *wp, const float *bias, int relu, void *stream);
 
+/* ------------------------------------------------------------------ bf16 training of the convolution above
+ * (csrc/conv3x3_bf16_bwd.hip): bf16 activations and gradients, fp32 master weights.
+ *   ia_conv3x3_bf16_wgrad_levels: the weight gradient of one weight shared by d->num_levels levels and
+ *     d->groups groups.  The descriptor is the forward one with y = dy (the gradient w.r.t. the
+ *     convolution's output, pixel stride y_stride >= cout):
+ *       dw[g][co][ci][ky][kx] = sum_l sum_b sum_{y,x} dy_l[b,y,x,co] * x_l[b,y+ky-1,x+kx-1,ci]
+ *     (zero outside the map), bf16 products accumulated in fp32 on v_mfma_f32_32x32x16_bf16; dw is fp32
+ *     in the layout of an nn.Conv2d weight (groups * cout, cin, 3, 3).  cin % 32 == 0, any cout >= 1,
+ *     maps down to 1 x 1; x as in the forward call (16-byte aligned, x_stride % 8 == 0); dy any 2-byte
+ *     aligned pointer and any stride (16-byte loads when every dy pointer is 16-byte aligned and
+ *     y_stride % 8 == 0, element loads otherwise).  IA_E_ARG outside that.
+ *     The pixels of all levels and images are cut into 128-pixel tiles and the tile list into `slices`
+ *     runs of `slice_tiles` tiles (ia_conv3x3_bf16_wgrad_plan reports both and the tile count; the
+ *     last slice may be shorter); each slice's fp32 partial result goes to the caller's workspace
+ *     (ia_conv3x3_bf16_wgrad_workspace_bytes, 16-byte aligned; 0 for a descriptor that is not covered --
+ *     the query does not look at the pointers) and a second kernel adds the partials in slice order:
+ *     no atomics, the same bits on every run, the workspace need not be initialised and nothing of it is
+ *     read that this call did not write.
+ *   ia_conv3x3_bf16_pack_f32: w fp32 (groups * cout, cin, 3, 3), dense -> rounded to bf16 (nearest even)
+ *     in the packed layout of ia_conv3x3_bf16_pack, one launch.  adjoint = 0: the forward weight,
+ *     ia_conv3x3_bf16_packed_bytes(cin, cout, groups) bytes.  adjoint = 1: the weight of the
+ *     input-gradient convolution, w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx], a convolution with
+ *     cout' = cin outputs and cin' = cout rounded up to a multiple of 32 inputs, the padded input
+ *     channels being ZERO weight rows: ia_conv3x3_bf16_packed_bytes(cin', cin, groups) bytes, and
+ *     dx = ia_conv3x3_bf16_levels on dy tensors of (at least) cin' channels per pixel whose padding is
+ *     finite.  cin % 32 == 0, cout >= 1.
+ *   ia_relu_bwd_bias_grad_bf16: the bf16 instance of ia_relu_bwd_bias_grad with row strides (elements;
+ *     each >= n): g = dy where y > 0, else a zero with dy's sign (= dy * (y > 0) for finite dy);
+ *     y == NULL: no mask, g = dy (g == NULL: nothing written); db[n] fp32 = column sums of g through
+ *     per-strip partial rows added in a fixed order (db == NULL: not computed; then no workspace).  Any
+ *     n >= 1; 16-byte accesses when n % 8 == 0 and every pointer and stride allows them.            */
+size_t ia_conv3x3_bf16_wgrad_workspace_bytes(const ia_conv3x3_desc *d);
+int ia_conv3x3_bf16_wgrad_plan(const ia_conv3x3_desc *d, int32_t *tiles, int32_t *slice_tiles, int32_t *slices);
+int ia_conv3x3_bf16_wgrad_levels(const ia_conv3x3_desc *d, float *dw, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int ia_conv3x3_bf16_pack_f32(const float *w, int cin, int cout, int groups, int adjoint, void *wp, void *stream);
+size_t ia_relu_bwd_bias_grad_bf16_workspace_bytes(int64_t rows, int n);
+int ia_relu_bwd_bias_grad_bf16(const void *dy, int64_t dy_stride, const void *y, int64_t y_stride, int64_t rows,
+                               int n, void *g, int64_t g_stride, float *db, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ IoU-aware FCOS
  * GroupNorm + ReLU of the FCOS head towers (reference mmdet/models/anchor_heads/
  * iou_aware_fcos_head.py:41-62: ConvModule(3x3, no bias, GN(32), ReLU); torch nn.GroupNorm:

@@ -223,6 +223,13 @@ SIGNATURES = {
     'ia_conv3x3_bf16_packed_bytes': (C.c_size_t, [_i, _i, _i]),
     'ia_conv3x3_bf16_pack': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'ia_conv3x3_bf16_levels': (_i, [_vp, _vp, _vp, _i, _vp]),
+    'ia_conv3x3_bf16_wgrad_workspace_bytes': (C.c_size_t, [_vp]),
+    'ia_conv3x3_bf16_wgrad_plan': (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'ia_conv3x3_bf16_wgrad_levels': (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
+    'ia_conv3x3_bf16_pack_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'ia_relu_bwd_bias_grad_bf16_workspace_bytes': (C.c_size_t, [C.c_int64, _i]),
+    'ia_relu_bwd_bias_grad_bf16': (_i, [_vp, C.c_int64, _vp, C.c_int64, C.c_int64, _i, _vp, C.c_int64, _vp,
+                                        _vp, C.c_size_t, _vp]),
     'ia_upsample2x_add_nhwc_dt': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_affine_relu_maxpool_nhwc_dt': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'ia_affine_relu_maxpool_nhwc': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -162,11 +162,19 @@ class _RetinaHeadBase(AnchorHead):
         return cls_feat, reg_feat
 
     train_winograd = True                 # training: all-levels Winograd convolutions when usable
+    train_bf16 = False                    # training, opt-in: bf16 activations on the MFMA convolutions
 
     def forward(self, feats):
         """multi_apply(forward_single) of the reference (anchor_head.py:102-103); in training on a
         ROCm device every convolution runs once for all levels on the Winograd path with its own
-        backward (iouaware/winograd_train.py) -- same parameters, same outputs to fp32 rounding."""
+        backward (iouaware/winograd_train.py) -- same parameters, same outputs to fp32 rounding.
+        With `train_bf16` set the convolutions run in bf16 instead (iouaware/conv3x3_bf16_train.py:
+        bf16 activations and gradients, fp32 parameters and parameter gradients; the outputs are
+        bf16 and go into the same loss path)."""
+        if self.training and self.train_bf16:
+            from . import conv3x3_bf16_train
+            if conv3x3_bf16_train.usable(feats, self):
+                return conv3x3_bf16_train.head_forward(self, feats)
         if self.training and self.train_winograd:
             from . import winograd_train
             if winograd_train.usable(feats, self):

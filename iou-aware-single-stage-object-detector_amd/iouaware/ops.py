@@ -701,11 +701,29 @@ def affine_relu_maxpool(x, scale, shift):
     return out
 
 
-def conv3x3_bf16_pack(weight, groups=1):
+def conv3x3_bf16_pack(weight, groups=1, adjoint=False):
     """(groups * Cout, Cin, 3, 3) weight -> the packed bf16 layout of `conv3x3_bf16_levels`
-    (once per model); Cin % 32 == 0, Cout even"""
+    (once per model); Cin % 32 == 0, Cout even.
+    An fp32 weight (the master weight of bf16 training) is rounded and packed in ONE launch
+    (ia_conv3x3_bf16_pack_f32; any Cout >= 1, channels beyond it are zero in the packed tile);
+    adjoint=True (fp32 only) packs the weight of the input-gradient convolution instead,
+    w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx], whose input channels (Cout) are padded with zero
+    rows to the next multiple of 32."""
     _require_gpu(weight, 'weight')
     co, ci, kh, kw = weight.shape
+    if weight.dtype == torch.float32:
+        if (kh, kw) != (3, 3) or ci % 32 or co % groups or not 1 <= groups <= 2:
+            raise ValueError('conv3x3_bf16 needs a 3x3 kernel, Cin % 32 == 0, groups <= 2')
+        w = weight.detach().contiguous()
+        cg = co // groups
+        nbytes = _lib.lib().ia_conv3x3_bf16_packed_bytes((cg + 31) // 32 * 32, ci, groups) if adjoint \
+            else _lib.lib().ia_conv3x3_bf16_packed_bytes(ci, cg, groups)
+        wp = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+        _lib.check(_lib.lib().ia_conv3x3_bf16_pack_f32(_ptr(w), ci, cg, groups, int(bool(adjoint)), _ptr(wp),
+                                                       _stream()), 'ia_conv3x3_bf16_pack_f32')
+        return wp
+    if adjoint:
+        raise TypeError('conv3x3_bf16_pack(adjoint=True) takes the fp32 master weight')
     if (kh, kw) != (3, 3) or ci % 32 or co % groups or (co // groups) % 2 or not 1 <= groups <= 2:
         raise ValueError('conv3x3_bf16 needs a 3x3 kernel, Cin % 32 == 0, an even Cout per group, groups <= 2')
     w = weight.detach().to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()      # (Cout, 3, 3, Cin)
@@ -764,6 +782,109 @@ def conv3x3_bf16(x, wp, bias, cout, relu=False):
                     memory_format=torch.channels_last)
     conv3x3_bf16_levels([[x]], wp, bias, cout, [[y]], relu=relu)
     return y
+
+
+def _cl_pix_stride(t, what):
+    """pixel stride (elements) of a channels-last bf16 (B, C, H, W) tensor or channel slice of one"""
+    if t.dtype != torch.bfloat16 or t.dim() != 4 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise TypeError('%s needs channels-last bf16 tensors' % what)
+    st = t.stride(3) if t.shape[3] > 1 else (t.stride(2) if t.shape[2] > 1 else
+                                             (t.stride(0) if t.shape[0] > 1 else t.shape[1]))
+    if st < t.shape[1] or (t.shape[2] > 1 and t.shape[3] > 1 and t.stride(2) != t.shape[3] * st) or \
+            (t.shape[0] > 1 and t.stride(0) != t.shape[2] * t.shape[3] * st):
+        raise TypeError('%s: tensor is not a dense channels-last (slice)' % what)
+    return int(st)
+
+
+def _wgrad_desc(xs, dys, cin, cout):
+    groups, L = len(xs), len(xs[0])
+    x0, d0 = xs[0][0], dys[0][0]
+    _require_gpu(x0, 'x')
+    _require_gpu(d0, 'dy')
+    what = 'conv3x3_bf16_wgrad_levels'
+    d = _lib.Conv3x3Desc()
+    d.num_levels, d.batch, d.groups = L, int(x0.shape[0]), groups
+    d.cin, d.cout = int(cin), int(cout)
+    d.x_stride, d.y_stride = _cl_pix_stride(x0, what), _cl_pix_stride(d0, what)
+    for l in range(L):
+        d.H[l], d.W[l] = int(xs[0][l].shape[2]), int(xs[0][l].shape[3])
+        for g in range(groups):
+            x, dy = xs[g][l], dys[g][l]
+            if x.shape[1] != cin or dy.shape[1] != cout or x.shape[2:] != dy.shape[2:] or x.shape[0] != d.batch \
+                    or dy.shape[0] != d.batch or tuple(x.shape[2:]) != (d.H[l], d.W[l]) \
+                    or _cl_pix_stride(x, what) != d.x_stride or _cl_pix_stride(dy, what) != d.y_stride:
+                raise ValueError('%s: inconsistent tensors at group %d level %d' % (what, g, l))
+            d.x[g][l], d.y[g][l] = x.data_ptr(), dy.data_ptr()
+    return d
+
+
+def conv3x3_bf16_wgrad_plan(xs, dys, cin, cout):
+    """-> (tiles, slice_tiles, slices) of the weight-gradient launch for these tensors: the
+    128-pixel tiles of all levels and images, the tiles one split-K slice accumulates, the slices"""
+    d = _wgrad_desc(xs, dys, cin, cout)
+    t, st, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _lib.check(_lib.lib().ia_conv3x3_bf16_wgrad_plan(C.byref(d), C.byref(t), C.byref(st), C.byref(n)),
+               'ia_conv3x3_bf16_wgrad_plan')
+    return t.value, st.value, n.value
+
+
+def conv3x3_bf16_wgrad_levels(xs, dys, cin, cout, workspace=None):
+    """Weight gradient of the bf16 3x3 convolution (csrc/conv3x3_bf16_bwd.hip): xs / dys lists over
+    groups of lists over levels of channels-last bf16 (B, cin, H, W) inputs and (B, cout, H, W)
+    output gradients (channel slices of wider tensors allowed) -> fp32 (groups * cout, cin, 3, 3),
+    summed over levels, images and pixels in fp32 in a fixed order.  workspace: a uint8 tensor of
+    at least the queried size (default: the shared per-stream workspace); it need not be
+    initialised."""
+    d = _wgrad_desc(xs, dys, cin, cout)
+    nbytes = int(_lib.lib().ia_conv3x3_bf16_wgrad_workspace_bytes(C.byref(d)))
+    if nbytes == 0:
+        raise _lib.IouAwareLibraryError('conv3x3_bf16_wgrad_levels: unsupported sizes (cin % 32 == 0, cout >= 1)')
+    dev = xs[0][0].device
+    ws = _workspace(dev, nbytes) if workspace is None else workspace
+    dw = torch.empty((len(xs) * int(cout), int(cin), 3, 3), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ia_conv3x3_bf16_wgrad_levels(C.byref(d), _ptr(dw), _ptr(ws), ws.numel() * ws.element_size(),
+                                                       _stream()), 'ia_conv3x3_bf16_wgrad_levels')
+    return dw
+
+
+def relu_bwd_bias_grad_bf16_rows(dev, dy_ptr, dy_stride, y_ptr, y_stride, rows, n, g_ptr, g_stride, bias_grad):
+    """ia_relu_bwd_bias_grad_bf16 on (rows, n) bf16 matrices given by address (int or None) and row
+    stride in elements -> db fp32 (n,) or None.  The caller keeps the tensors behind the addresses
+    alive and on the current stream."""
+    db = ws = None
+    nbytes = 0
+    if bias_grad:
+        db = torch.empty(n, dtype=torch.float32, device=dev)
+        nbytes = int(_lib.lib().ia_relu_bwd_bias_grad_bf16_workspace_bytes(rows, n))
+        ws = _workspace(dev, nbytes)
+    _lib.check(_lib.lib().ia_relu_bwd_bias_grad_bf16(
+        C.c_void_p(dy_ptr), dy_stride, C.c_void_p(y_ptr or 0), y_stride, rows, n, C.c_void_p(g_ptr or 0),
+        g_stride, _ptr(db), _ptr(ws), nbytes, _stream()), 'ia_relu_bwd_bias_grad_bf16')
+    return db
+
+
+def relu_bwd_bias_grad_bf16(dy, y=None, bias_grad=True, out=None):
+    """channels-last bf16 (B, C, H, W) tensors or channel slices of wider ones: g = dy where y > 0
+    (else a zero with dy's sign, as dy * (y > 0)); y None: no mask.  g is written to `out` (same
+    shape, its own pixel stride -- e.g. the leading channels of a wider zeroed tensor) or a new
+    tensor; with y None and no `out` dy itself is returned.  db: fp32 (C,) column sums of g (None
+    unless bias_grad), summed in a fixed order.  -> (g, db)"""
+    _require_gpu(dy, 'dy')
+    what = 'relu_bwd_bias_grad_bf16'
+    B, Cn, H, Wd = dy.shape
+    g = out
+    if g is None and y is not None:
+        g = torch.empty((B, Cn, H, Wd), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+    if g is None and not bias_grad:
+        return dy, None
+    for t in (y, g):
+        if t is not None and tuple(t.shape) != tuple(dy.shape):
+            raise ValueError('%s: shapes differ' % what)
+    db = relu_bwd_bias_grad_bf16_rows(
+        dy.device, dy.data_ptr(), _cl_pix_stride(dy, what), None if y is None else y.data_ptr(),
+        0 if y is None else _cl_pix_stride(y, what), B * H * Wd, Cn, None if g is None else g.data_ptr(),
+        0 if g is None else _cl_pix_stride(g, what), bias_grad)
+    return (dy if g is None else g), db
 
 
 _LT_WS_BYTES = 64 << 20

@@ -7,6 +7,8 @@
                                                              config, or CONFIG=<an mmdet config file
                                                              with model / train_cfg / test_cfg>
     TRAIN_WINOGRAD=0    the head's module route (bbox_head.train_winograd = False)
+    TRAIN_BF16=1        the RetinaNet heads' bf16 route (bbox_head.train_bf16 = True: bf16 activations on
+                        the MFMA convolutions, fp32 master weights; iouaware/conv3x3_bf16_train.py)
     ITERS=n             timed iterations (default 5)"""
 import sys, os, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -37,7 +39,10 @@ else:
         model.train_cfg = TRAIN_CFG
 if os.environ.get('TRAIN_WINOGRAD') is not None:
     model.bbox_head.train_winograd = bool(int(os.environ['TRAIN_WINOGRAD']))
-print('model %s  head %s  train_winograd %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd))
+if os.environ.get('TRAIN_BF16') is not None:
+    model.bbox_head.train_bf16 = bool(int(os.environ['TRAIN_BF16']))
+print('model %s  head %s  train_winograd %s  train_bf16 %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd,
+                                                               getattr(model.bbox_head, 'train_bf16', False)))
 opt = build_optimizer(model, dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001))
 img = torch.randn(B, 3, 800, 1344, device='cuda')
 if os.environ.get('FUSE'):
