@@ -879,6 +879,35 @@ int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const f
                            const float *beta, int relu, const void *saved, size_t saved_bytes,
                            const void *workspace, size_t workspace_bytes, float *dgamma,
                            float *dbeta, void *stream);
+/* The five training entries for dtype IA_F32 / IA_BF16 (everything else as above).  IA_F32: the
+ * entries above, same bits.  IA_BF16: x[l], y[l], dy[l], dx[l] (batch, H_l, W_l, channels) bf16
+ * channels-last; the forward pair is ia_groupnorm_stats_dt(IA_BF16) + ia_groupnorm_apply_to_dt.  A
+ * thread's 16-byte column is 8 channels of one group.  x and dy widen exactly to fp32, so:
+ *   y  = bf16(relu?(float(x) * s + t)): the bits ia_groupnorm_apply_dt(IA_BF16) leaves in x;
+ *   g  = dy where the forward's fp32 pre-activation float(x) * s + t > 0 (y is not needed);
+ *   sum g and sum g * x per channel in fp64 (exact products), the (mean, rstd), channel and group
+ *     rows and the parameter-gradient pass of the fp32 node (dgamma / dbeta stay fp32);
+ *   dx = bf16(s * g + (c1 + ((x - mean_hi) - mean_lo) * c2)): the fp32 entry's expression on the
+ *     widened values, ONE round-to-nearest-even.
+ * What IA_BF16 covers: channels a power of two, 8 <= channels <= 1024; 1 <= groups <= 256, groups
+ * divides channels and channels / groups % 8 == 0; all pointers 16-byte aligned.  The size queries
+ * return 0 for anything else (and for any other dtype); the launches then return IA_E_ARG.     */
+size_t ia_groupnorm_saved_bytes_dt(const ia_wino_geom *g, int channels, int groups, int dtype);
+int ia_groupnorm_apply_to_dt(const ia_wino_geom *g, const void *const *x, void *const *y, int dtype,
+                             int channels, int groups, const float *gamma, const float *beta,
+                             float eps, int relu, const void *workspace, size_t workspace_bytes,
+                             void *saved, size_t saved_bytes, void *stream);
+size_t ia_groupnorm_bwd_workspace_bytes_dt(const ia_wino_geom *g, int channels, int groups,
+                                           int dtype);
+int ia_groupnorm_bwd_reduce_dt(const ia_wino_geom *g, const void *const *x, const void *const *dy,
+                               int dtype, int channels, int groups, const float *gamma,
+                               const float *beta, int relu, const void *saved, size_t saved_bytes,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int ia_groupnorm_bwd_apply_dt(const ia_wino_geom *g, const void *const *x, const void *const *dy,
+                              void *const *dx, int dtype, int channels, int groups,
+                              const float *gamma, const float *beta, int relu, const void *saved,
+                              size_t saved_bytes, const void *workspace, size_t workspace_bytes,
+                              float *dgamma, float *dbeta, void *stream);
 /* The FCOS regression epilogue bbox_pred = exp(scale_l * x) (iou_aware_fcos_head.py:105) in place
  * on per-level (batch, H_l, W_l, channels) fp32 tensors (channels % 4 == 0, 16-byte aligned);
  * scales: (num_levels) fp32 device array (the head's Scale parameters).                      */

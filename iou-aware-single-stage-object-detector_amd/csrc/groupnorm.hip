@@ -612,6 +612,229 @@ __global__ void __launch_bounds__(kGnThreads) k_gn_bwd_params(const double2 *cpa
     }
 }
 
+// ------------------------------------------------------------------ training node, bf16
+// The same three kernels on (B, H_l, W_l, channels) bf16 channels-last x, dy, y and dx (the towers of
+// the bf16 training route, conv3x3_bf16.hip in front and behind): GnTrainArgs::x / dy / out then
+// carry the bf16 base pointers.  A thread's 16-byte column is 8 channels (inside one group: channels
+// / groups % 8 == 0).  x and dy widen exactly, so every expression is the fp32 kernel's on the stored
+// values: the mask is the forward's fp32 pre-activation float(x) * s + t > 0 (y is not kept), sum g
+// and sum g * x are exact products in fp64, and y and dx are rounded ONCE to bf16 (nearest even).
+// The (mean, rstd) rows, the workspace rows and k_gn_bwd_params are those of the fp32 node.
+__device__ __forceinline__ const uint16_t *gn_image_bf16(const float *base, int b, int HW,
+                                                         int channels)
+{
+    return reinterpret_cast<const uint16_t *>(base) + (size_t)b * HW * channels;
+}
+
+// the column's 8 per-channel (s, t): quads 2 v and 2 v + 1 of gn_scale_shift
+__device__ __forceinline__ void gn_scale_shift8(const float *gamma, const float *beta, int v,
+                                                double mean, double rstd, float (&sc)[8],
+                                                float (&sh)[8])
+{
+    float4 sa, sb, ta, tb;
+    gn_scale_shift(gamma, beta, 2 * v, mean, rstd, sa, ta);
+    gn_scale_shift(gamma, beta, 2 * v + 1, mean, rstd, sb, tb);
+    sc[0] = sa.x; sc[1] = sa.y; sc[2] = sa.z; sc[3] = sa.w;
+    sc[4] = sb.x; sc[5] = sb.y; sc[6] = sb.z; sc[7] = sb.w;
+    sh[0] = ta.x; sh[1] = ta.y; sh[2] = ta.z; sh[3] = ta.w;
+    sh[4] = tb.x; sh[5] = tb.y; sh[6] = tb.z; sh[7] = tb.w;
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_apply_to_bf16(GnTrainArgs a)
+{
+    __shared__ double s_mean[256], s_rstd[256];
+    __shared__ float4 s_scale[256], s_shift[256];      // per 4 channels
+    const GnTrainBlock k = gn_train_block<false>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double ts = 0.0, tss = 0.0;
+        const double2 *pp = a.part + (size_t)k.row0 * a.groups + g;
+        for (int c = 0; c < k.nch; ++c) {
+            const double2 q = pp[(size_t)c * a.groups];
+            ts += q.x;
+            tss += q.y;
+        }
+        const double n = (double)k.HW * cpg;
+        const double mean = ts / n;
+        double var = tss / n - mean * mean;
+        var = var > 0.0 ? var : 0.0;
+        const double rstd = 1.0 / sqrt(var + (double)a.eps);
+        s_mean[g] = mean;
+        s_rstd[g] = rstd;
+        if (k.chunk == 0)
+            a.saved[(size_t)(k.l * a.batch + k.b) * a.groups + g] = make_double2(mean, rstd);
+    }
+    __syncthreads();
+    for (int q = tid; q < (a.channels >> 2); q += kGnThreads) {
+        const int g = (4 * q) / cpg;
+        float4 sc, sh;
+        gn_scale_shift(a.gamma, a.beta, q, s_mean[g], s_rstd[g], sc, sh);
+        s_scale[q] = sc;
+        s_shift[q] = sh;
+    }
+    __syncthreads();
+    const int vc = a.channels >> 3;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const float4 sa = s_scale[2 * v], sb = s_scale[2 * v + 1];
+    const float4 ta = s_shift[2 * v], tb = s_shift[2 * v + 1];
+    const float sc[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+    const float sh[8] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w};
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const uint4 *x = reinterpret_cast<const uint4 *>(gn_image_bf16(k.x, k.b, k.HW, a.channels)) + v;
+    uint4 *y = reinterpret_cast<uint4 *>(
+                   const_cast<uint16_t *>(gn_image_bf16(k.out, k.b, k.HW, a.channels))) + v;
+#pragma unroll 2
+    for (int p = p0 + r; p < p1; p += rows) {
+        float f[8];
+        bf16x8_to_f32(x[(size_t)p * vc], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            f[j] = f[j] * sc[j] + sh[j];
+            if (a.relu) f[j] = f[j] > 0.0f ? f[j] : 0.0f;
+        }
+        y[(size_t)p * vc] = f32_to_bf16x8(f);
+    }
+}
+
+// g = dy where the forward's fp32 pre-activation is positive (all of dy without the ReLU)
+__device__ __forceinline__ void gn_masked8(const float (&x)[8], float (&g)[8], const float (&sc)[8],
+                                           const float (&sh)[8], int relu)
+{
+    if (relu) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = (x[j] * sc[j] + sh[j]) > 0.0f ? g[j] : 0.0f;
+    }
+}
+
+// LDS: a column's 8 channels x 2 sums x 256 threads in doubles would be 32 KB on top of s_ch's 16 KB;
+// the threads of a column are added in two halves instead (channels 0..3, then 4..7 of every column,
+// through the fp32 kernel's 16 KB): the same fixed order per channel, one more barrier pair, and
+// five workgroups per CU instead of three.
+__global__ void __launch_bounds__(kGnThreads) k_gn_bwd_reduce_bf16(GnTrainArgs a)
+{
+    __shared__ double s_acc[8][kGnThreads];     // [2 * j + (0: g, 1: g x)][thread], j = channel & 3
+    __shared__ double2 s_ch[1024];              // per channel gamma * (sum g, sum g xh)
+    const GnTrainBlock k = gn_train_block<true>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    const int vc = a.channels >> 3;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const double2 *saved = a.saved + (size_t)(k.l * a.batch + k.b) * a.groups;
+    float sc[8], sh[8];
+    {
+        const double2 mr = saved[(8 * v) / cpg];
+        gn_scale_shift8(a.gamma, a.beta, v, mr.x, mr.y, sc, sh);
+    }
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const uint4 *x = reinterpret_cast<const uint4 *>(gn_image_bf16(k.x, k.b, k.HW, a.channels)) + v;
+    const uint4 *dy = reinterpret_cast<const uint4 *>(gn_image_bf16(k.dy, k.b, k.HW, a.channels)) + v;
+    double sg[8], sx[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sg[j] = sx[j] = 0.0;
+#pragma unroll 2
+    for (int p = p0 + r; p < p1; p += rows) {
+        float q[8], g[8];
+        bf16x8_to_f32(x[(size_t)p * vc], q);
+        bf16x8_to_f32(dy[(size_t)p * vc], g);
+        gn_masked8(q, g, sc, sh, a.relu);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double gj = g[j];
+            sg[j] += gj;
+            sx[j] += gj * (double)q[j];
+        }
+    }
+    const size_t row = (size_t)(k.row0 + k.chunk);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h) __syncthreads();                 // the first half's sums are read
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s_acc[2 * j][tid] = sg[4 * h + j];
+            s_acc[2 * j + 1][tid] = sx[4 * h + j];
+        }
+        __syncthreads();
+        for (int i = tid; i < (a.channels >> 1); i += kGnThreads) {
+            const int cv = i >> 2, j = i & 3;
+            const int c = 8 * cv + 4 * h + j;
+            double tg = 0.0, tx = 0.0;
+            for (int rr = 0; rr < rows; ++rr) {
+                tg += s_acc[2 * j][rr * vc + cv];
+                tx += s_acc[2 * j + 1][rr * vc + cv];
+            }
+            const double2 mr = saved[c / cpg];
+            const double th = mr.y * (tx - mr.x * tg);          // sum g * xh
+            a.cpart[row * a.channels + c] = make_double2(tg, th);
+            const double gm = (double)a.gamma[c];
+            s_ch[c] = make_double2(gm * tg, gm * th);
+        }
+    }
+    __syncthreads();
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int j = 0; j < cpg; ++j) {
+            const double2 q = s_ch[g * cpg + j];
+            t1 += q.x;
+            t2 += q.y;
+        }
+        a.gpart[row * a.groups + g] = make_double2(t1, t2);
+    }
+}
+
+__global__ void __launch_bounds__(kGnThreads) k_gn_bwd_apply_bf16(GnTrainArgs a)
+{
+    __shared__ double2 s_mr[256];
+    __shared__ float4 s_k[256];                 // per group (mean_hi, mean_lo, c1, c2)
+    const GnTrainBlock k = gn_train_block<true>(a, blockIdx.x);
+    const int tid = threadIdx.x;
+    const int cpg = a.channels / a.groups;
+    const double2 *saved = a.saved + (size_t)(k.l * a.batch + k.b) * a.groups;
+    for (int g = tid; g < a.groups; g += kGnThreads) {
+        double t1 = 0.0, t2 = 0.0;
+        const double2 *pp = a.gpart + (size_t)k.row0 * a.groups + g;
+        for (int c = 0; c < k.nch; ++c) {
+            const double2 q = pp[(size_t)c * a.groups];
+            t1 += q.x;
+            t2 += q.y;
+        }
+        const double n = (double)k.HW * cpg;
+        const double2 mr = saved[g];
+        const float mh = (float)mr.x;
+        s_mr[g] = mr;
+        s_k[g] = make_float4(mh, (float)(mr.x - (double)mh), (float)(-mr.y * (t1 / n)),
+                             (float)(-mr.y * mr.y * (t2 / n)));
+    }
+    __syncthreads();
+    const int vc = a.channels >> 3;
+    const int rows = kGnThreads / vc;
+    const int v = tid % vc, r = tid / vc;
+    const int grp = (8 * v) / cpg;
+    float sc[8], sh[8];
+    gn_scale_shift8(a.gamma, a.beta, v, s_mr[grp].x, s_mr[grp].y, sc, sh);
+    const float4 kk = s_k[grp];
+    const int p0 = k.chunk * IA_GN_CHUNK;
+    const int p1 = min(p0 + IA_GN_CHUNK, k.HW);
+    const uint4 *x = reinterpret_cast<const uint4 *>(gn_image_bf16(k.x, k.b, k.HW, a.channels)) + v;
+    const uint4 *dy = reinterpret_cast<const uint4 *>(gn_image_bf16(k.dy, k.b, k.HW, a.channels)) + v;
+    uint4 *dx = reinterpret_cast<uint4 *>(
+                    const_cast<uint16_t *>(gn_image_bf16(k.out, k.b, k.HW, a.channels))) + v;
+#pragma unroll 2
+    for (int p = p0 + r; p < p1; p += rows) {
+        float q[8], g[8], o[8];
+        bf16x8_to_f32(x[(size_t)p * vc], q);
+        bf16x8_to_f32(dy[(size_t)p * vc], g);
+        gn_masked8(q, g, sc, sh, a.relu);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = sc[j] * g[j] + (kk.z + ((q[j] - kk.x) - kk.y) * kk.w);
+        dx[(size_t)p * vc] = f32_to_bf16x8(o);
+    }
+}
+
 static void gn_train_args(const GnArgs &s, GnTrainArgs &a)
 {
     a.num_levels = s.num_levels; a.batch = s.batch; a.channels = s.channels; a.groups = s.groups;
@@ -814,11 +1037,49 @@ int ia_groupnorm_apply(const ia_wino_geom *g, float *const *x, int channels, int
 }
 
 
-size_t ia_groupnorm_saved_bytes(const ia_wino_geom *g, int channels, int groups)
+// The training entries for dtype IA_F32 / IA_BF16: one body each, the non-_dt names forward IA_F32.
+size_t ia_groupnorm_saved_bytes_dt(const ia_wino_geom *g, int channels, int groups, int dtype)
 {
     ia::GnArgs a;
-    if (ia::gn_args(g, channels, groups, a)) return 0;
+    if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
     return ((size_t)a.num_levels * a.batch * groups * sizeof(double2) + 255) / 256 * 256;
+}
+
+size_t ia_groupnorm_saved_bytes(const ia_wino_geom *g, int channels, int groups)
+{
+    return ia_groupnorm_saved_bytes_dt(g, channels, groups, IA_F32);
+}
+
+int ia_groupnorm_apply_to_dt(const ia_wino_geom *g, const void *const *x, void *const *y, int dtype,
+                             int channels, int groups, const float *gamma, const float *beta,
+                             float eps, int relu, const void *workspace, size_t workspace_bytes,
+                             void *saved, size_t saved_bytes, void *stream)
+{
+    ia::GnArgs s;
+    int rc = ia::gn_args_dt(g, channels, groups, dtype, s);
+    if (rc) return rc;
+    if (!workspace || !saved || !gamma || !beta || !(eps >= 0.0f)) return IA_E_ARG;
+    if (((uintptr_t)workspace & 15u) || ((uintptr_t)saved & 15u)) return IA_E_ARG;
+    ia::GnTrainArgs a;
+    ia::gn_train_args(s, a);
+    if (!ia::gn_level_ptrs(a.num_levels, reinterpret_cast<const float *const *>(x), a.x) ||
+        !ia::gn_level_ptrs(a.num_levels, reinterpret_cast<const float *const *>(y),
+                           const_cast<const float **>(a.out)))
+        return IA_E_ARG;
+    for (int l = 0; l < a.num_levels; ++l)
+        if (x[l] == y[l]) return IA_E_ARG;             // out of place: ia_groupnorm_apply otherwise
+    if (workspace_bytes < ia_groupnorm_workspace_bytes_dt(g, channels, groups, dtype) ||
+        saved_bytes < ia_groupnorm_saved_bytes_dt(g, channels, groups, dtype))
+        return IA_E_WORKSPACE;
+    a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu ? 1 : 0;
+    a.part = static_cast<const double2 *>(workspace);
+    a.saved = static_cast<double2 *>(saved);
+    const dim3 grid((unsigned)a.blk_off[IA_MAX_LEVELS]), block(ia::kGnThreads);
+    if (dtype == IA_BF16)
+        hipLaunchKernelGGL(ia::k_gn_apply_to_bf16, grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(ia::k_gn_apply_to, grid, block, 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
 }
 
 int ia_groupnorm_apply_to(const ia_wino_geom *g, const float *const *x, float *const *y,
@@ -826,52 +1087,42 @@ int ia_groupnorm_apply_to(const ia_wino_geom *g, const float *const *x, float *c
                           float eps, int relu, const void *workspace, size_t workspace_bytes,
                           void *saved, size_t saved_bytes, void *stream)
 {
-    ia::GnArgs s;
-    int rc = ia::gn_args(g, channels, groups, s);
-    if (rc) return rc;
-    if (!workspace || !saved || !gamma || !beta || !(eps >= 0.0f)) return IA_E_ARG;
-    if (((uintptr_t)workspace & 15u) || ((uintptr_t)saved & 15u)) return IA_E_ARG;
-    ia::GnTrainArgs a;
-    ia::gn_train_args(s, a);
-    if (!ia::gn_level_ptrs(a.num_levels, x, a.x) ||
-        !ia::gn_level_ptrs(a.num_levels, y, const_cast<const float **>(a.out)))
-        return IA_E_ARG;
-    for (int l = 0; l < a.num_levels; ++l)
-        if (x[l] == y[l]) return IA_E_ARG;             // out of place: ia_groupnorm_apply otherwise
-    if (workspace_bytes < ia_groupnorm_workspace_bytes(g, channels, groups) ||
-        saved_bytes < ia_groupnorm_saved_bytes(g, channels, groups))
-        return IA_E_WORKSPACE;
-    a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu ? 1 : 0;
-    a.part = static_cast<const double2 *>(workspace);
-    a.saved = static_cast<double2 *>(saved);
-    hipLaunchKernelGGL(ia::k_gn_apply_to, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
-                       dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
-    return ia::hip_status(hipGetLastError());
+    return ia_groupnorm_apply_to_dt(g, reinterpret_cast<const void *const *>(x),
+                                    reinterpret_cast<void *const *>(y), IA_F32, channels, groups,
+                                    gamma, beta, eps, relu, workspace, workspace_bytes, saved,
+                                    saved_bytes, stream);
 }
 
-size_t ia_groupnorm_bwd_workspace_bytes(const ia_wino_geom *g, int channels, int groups)
+size_t ia_groupnorm_bwd_workspace_bytes_dt(const ia_wino_geom *g, int channels, int groups,
+                                           int dtype)
 {
     ia::GnArgs a;
-    if (ia::gn_args(g, channels, groups, a)) return 0;
+    if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
     const size_t rows = (size_t)a.blk_off[IA_MAX_LEVELS];
     return (rows * ((size_t)groups + channels) * sizeof(double2) + 255) / 256 * 256;
 }
 
-static int gn_bwd_args(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+size_t ia_groupnorm_bwd_workspace_bytes(const ia_wino_geom *g, int channels, int groups)
+{
+    return ia_groupnorm_bwd_workspace_bytes_dt(g, channels, groups, IA_F32);
+}
+
+static int gn_bwd_args(const ia_wino_geom *g, const void *const *x, const void *const *dy, int dtype,
                        int channels, int groups, const float *gamma, const float *beta,
                        const void *saved, size_t saved_bytes, int relu, void *workspace,
                        size_t workspace_bytes, ia::GnTrainArgs &a)
 {
     ia::GnArgs s;
-    int rc = ia::gn_args(g, channels, groups, s);
+    int rc = ia::gn_args_dt(g, channels, groups, dtype, s);
     if (rc) return rc;
     if (!workspace || !saved || !gamma || !beta) return IA_E_ARG;
     if (((uintptr_t)workspace & 15u) || ((uintptr_t)saved & 15u)) return IA_E_ARG;
     ia::gn_train_args(s, a);
-    if (!ia::gn_level_ptrs(a.num_levels, x, a.x) || !ia::gn_level_ptrs(a.num_levels, dy, a.dy))
+    if (!ia::gn_level_ptrs(a.num_levels, reinterpret_cast<const float *const *>(x), a.x) ||
+        !ia::gn_level_ptrs(a.num_levels, reinterpret_cast<const float *const *>(dy), a.dy))
         return IA_E_ARG;
-    if (workspace_bytes < ia_groupnorm_bwd_workspace_bytes(g, channels, groups) ||
-        saved_bytes < ia_groupnorm_saved_bytes(g, channels, groups))
+    if (workspace_bytes < ia_groupnorm_bwd_workspace_bytes_dt(g, channels, groups, dtype) ||
+        saved_bytes < ia_groupnorm_saved_bytes_dt(g, channels, groups, dtype))
         return IA_E_WORKSPACE;
     a.gamma = gamma; a.beta = beta; a.relu = relu ? 1 : 0;
     a.saved = const_cast<double2 *>(static_cast<const double2 *>(saved));
@@ -880,37 +1131,55 @@ static int gn_bwd_args(const ia_wino_geom *g, const float *const *x, const float
     return 0;
 }
 
+int ia_groupnorm_bwd_reduce_dt(const ia_wino_geom *g, const void *const *x, const void *const *dy,
+                               int dtype, int channels, int groups, const float *gamma,
+                               const float *beta, int relu, const void *saved, size_t saved_bytes,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    ia::GnTrainArgs a;
+    int rc = gn_bwd_args(g, x, dy, dtype, channels, groups, gamma, beta, saved, saved_bytes, relu,
+                         workspace, workspace_bytes, a);
+    if (rc) return rc;
+    const dim3 grid((unsigned)a.blk_off[IA_MAX_LEVELS]), block(ia::kGnThreads);
+    if (dtype == IA_BF16)
+        hipLaunchKernelGGL(ia::k_gn_bwd_reduce_bf16, grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(ia::k_gn_bwd_reduce, grid, block, 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
 int ia_groupnorm_bwd_reduce(const ia_wino_geom *g, const float *const *x, const float *const *dy,
                             int channels, int groups, const float *gamma, const float *beta,
                             int relu, const void *saved, size_t saved_bytes, void *workspace,
                             size_t workspace_bytes, void *stream)
 {
-    ia::GnTrainArgs a;
-    int rc = gn_bwd_args(g, x, dy, channels, groups, gamma, beta, saved, saved_bytes, relu,
-                         workspace, workspace_bytes, a);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ia::k_gn_bwd_reduce, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
-                       dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
-    return ia::hip_status(hipGetLastError());
+    return ia_groupnorm_bwd_reduce_dt(g, reinterpret_cast<const void *const *>(x),
+                                      reinterpret_cast<const void *const *>(dy), IA_F32, channels,
+                                      groups, gamma, beta, relu, saved, saved_bytes, workspace,
+                                      workspace_bytes, stream);
 }
 
-int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const float *const *dy,
-                           float *const *dx, int channels, int groups, const float *gamma,
-                           const float *beta, int relu, const void *saved, size_t saved_bytes,
-                           const void *workspace, size_t workspace_bytes, float *dgamma,
-                           float *dbeta, void *stream)
+int ia_groupnorm_bwd_apply_dt(const ia_wino_geom *g, const void *const *x, const void *const *dy,
+                              void *const *dx, int dtype, int channels, int groups,
+                              const float *gamma, const float *beta, int relu, const void *saved,
+                              size_t saved_bytes, const void *workspace, size_t workspace_bytes,
+                              float *dgamma, float *dbeta, void *stream)
 {
     ia::GnTrainArgs a;
-    int rc = gn_bwd_args(g, x, dy, channels, groups, gamma, beta, saved, saved_bytes, relu,
+    int rc = gn_bwd_args(g, x, dy, dtype, channels, groups, gamma, beta, saved, saved_bytes, relu,
                          const_cast<void *>(workspace), workspace_bytes, a);
     if (rc) return rc;
     if (dx) {                                           // NULL: parameter gradients only
-        if (!ia::gn_level_ptrs(a.num_levels, dx, const_cast<const float **>(a.out)))
+        if (!ia::gn_level_ptrs(a.num_levels, reinterpret_cast<const float *const *>(dx),
+                               const_cast<const float **>(a.out)))
             return IA_E_ARG;
         for (int l = 0; l < a.num_levels; ++l)
             if (dx[l] == dy[l] || dx[l] == x[l]) return IA_E_ARG;
-        hipLaunchKernelGGL(ia::k_gn_bwd_apply, dim3((unsigned)a.blk_off[IA_MAX_LEVELS]),
-                           dim3(ia::kGnThreads), 0, (hipStream_t)stream, a);
+        const dim3 grid((unsigned)a.blk_off[IA_MAX_LEVELS]), block(ia::kGnThreads);
+        if (dtype == IA_BF16)
+            hipLaunchKernelGGL(ia::k_gn_bwd_apply_bf16, grid, block, 0, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL(ia::k_gn_bwd_apply, grid, block, 0, (hipStream_t)stream, a);
         rc = ia::hip_status(hipGetLastError());
         if (rc) return rc;
     }
@@ -921,6 +1190,19 @@ int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const f
         rc = ia::hip_status(hipGetLastError());
     }
     return rc;
+}
+
+int ia_groupnorm_bwd_apply(const ia_wino_geom *g, const float *const *x, const float *const *dy,
+                           float *const *dx, int channels, int groups, const float *gamma,
+                           const float *beta, int relu, const void *saved, size_t saved_bytes,
+                           const void *workspace, size_t workspace_bytes, float *dgamma,
+                           float *dbeta, void *stream)
+{
+    return ia_groupnorm_bwd_apply_dt(g, reinterpret_cast<const void *const *>(x),
+                                     reinterpret_cast<const void *const *>(dy),
+                                     reinterpret_cast<void *const *>(dx), IA_F32, channels, groups,
+                                     gamma, beta, relu, saved, saved_bytes, workspace,
+                                     workspace_bytes, dgamma, dbeta, stream);
 }
 
 }  // extern "C"

@@ -249,6 +249,15 @@ SIGNATURES = {
     'ia_groupnorm_bwd_apply': (_i, [_WG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_void_p), _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp,
                                     _vp, _vp]),
+    'ia_groupnorm_saved_bytes_dt': (_sz, [_WG, _i, _i, _i]),
+    'ia_groupnorm_apply_to_dt': (_i, [_WG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp,
+                                      _f, _i, _vp, _sz, _vp, _sz, _vp]),
+    'ia_groupnorm_bwd_workspace_bytes_dt': (_sz, [_WG, _i, _i, _i]),
+    'ia_groupnorm_bwd_reduce_dt': (_i, [_WG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp,
+                                        _i, _vp, _sz, _vp, _sz, _vp]),
+    'ia_groupnorm_bwd_apply_dt': (_i, [_WG, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz,
+                                       _vp, _vp, _vp]),
     'ia_scale_exp_levels': (_i, [_WG, C.POINTER(C.c_void_p), _i, _vp, _vp]),
     'ia_scale_exp_levels_dt': (_i, [_WG, C.POINTER(C.c_void_p), _i, _i, _vp, _vp]),
     'ia_point_workspace_bytes': (_sz, [_PG, _i]),

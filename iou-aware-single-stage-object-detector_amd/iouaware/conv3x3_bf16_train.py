@@ -1,5 +1,6 @@
-"""Mixed-precision training of the RetinaNet heads: bf16 activations and gradients on this library's
-MFMA convolution kernels, fp32 master weights and fp32 weight / bias gradients (opt-in:
+"""Mixed-precision training of the RetinaNet and FCOS heads: bf16 activations and gradients on this
+library's MFMA convolution kernels (and, in the FCOS towers, its bf16 GroupNorm + ReLU node), fp32
+master weights and fp32 weight / bias / GroupNorm parameter gradients (opt-in:
 `head.train_bf16 = True`).
 
 Reference: mmdet/models/anchor_heads/retina_head.py:79-90 / iou_aware_retina_head.py:171-219 (4 + 4
@@ -20,6 +21,12 @@ width is the next multiple of 32 (736, 64).  Two things keep the padding harmles
 output tensors are allocated zero-filled (their padding is never written), and in backward g is
 written into a ONCE-ZEROED buffer of the padded width that is kept per shape (the mask kernel writes
 the real channels only) while the adjoint weight carries ZERO ROWS for the padded channels.
+Without ReLU, bias gradient and padding (the FCOS tower convolutions) g is dy itself: no copy.
+
+The FCOS heads (fcos_head_forward; reference fcos_head.py / iou_aware_fcos_head.py: 4 + 4
+ConvModules of 3x3 convolution without bias + GroupNorm + ReLU): per tower layer one convolution
+node for both towers and ONE fcos_ops.groupnorm_relu_bf16 node on the 2F-channel activation; the
+output convolutions write fp32 NCHW maps for the fused loss node.
 """
 import collections
 import ctypes as C
@@ -77,6 +84,14 @@ def _cl_bf16(t):
         return t
     except TypeError:
         return t.contiguous(memory_format=_CL)
+
+
+def _addressable(groups):
+    """whether the convolution kernels can read these per-group level lists as an input: 16-byte
+    pixels and one pixel stride for all of them"""
+    ts = [t for g in groups for t in g]
+    strides = set(ops._cl_pix_stride(t, 'conv3x3_bf16_train') for t in ts)
+    return len(strides) == 1 and strides.pop() % 8 == 0 and all(t.data_ptr() % 16 == 0 for t in ts)
 
 
 def _storage(t):
@@ -161,17 +176,27 @@ class _Bf16ConvLevels(torch.autograd.Function):
             dyg = [[_cl_bf16(d) for d in dys[g * L:(g + 1) * L]] for g in range(groups)]
             want_b = ctx.has_bias and ctx.needs_input_grad[1]
             need_x = any(ctx.needs_input_grad[4:])
-            # ---- g = dy masked by the ReLU, db.  g lives in tensors of the padded width: a buffer that
-            # was zeroed once when there is padding (only the real channels are ever written)
-            gb = _zeroed_levels(xg[0], ge * P, ce) if P != ce else _alloc_levels(xg[0], ge * P)
-            gk = [[t[:, g * P:g * P + ce] for t in gb] for g in range(ge)]
             # the incoming gradients of two groups as ONE (B, 2 * cout, H, W) tensor per level when they
             # are neighbouring channel slices of one storage (the next layer's input gradients are): one
             # pass.  Never for separate allocations that merely lie side by side: see _mask_and_bias_grad
             whole = groups == 2 and P == ce and all(
                 b.data_ptr() == a.data_ptr() + 2 * cout and a.stride() == b.stride() and _storage(a) == _storage(b)
                 and ops._cl_pix_stride(a, 'conv3x3_bf16_train') >= 2 * cout for a, b in zip(dyg[0], dyg[1]))
-            if whole:
+            # ---- g = dy masked by the ReLU, db.  Nothing to mask, no bias gradient and no padding (every
+            # GroupNorm tower convolution): g IS dy, read where it lies -- when the kernels can address
+            # it (16-byte pixels, one pixel stride; one convolution with 2 * cout outputs needs the two
+            # towers' gradients as one tensor).  Otherwise g lives in tensors of the padded width: a buffer
+            # that was zeroed once when there is padding (only the real channels are ever written)
+            direct = not ctx.relu and not want_b and P == ce and (whole or not shared) and _addressable(dyg)
+            db = None
+            if direct:
+                gk = [_wide(dyg[0], 2 * cout)] if shared else dyg
+            else:
+                gb = _zeroed_levels(xg[0], ge * P, ce) if P != ce else _alloc_levels(xg[0], ge * P)
+                gk = [[t[:, g * P:g * P + ce] for t in gb] for g in range(ge)]
+            if direct:
+                pass
+            elif whole:
                 db = _mask_and_bias_grad(_wide(dyg[0], 2 * cout), ybufs, gb, 2 * cout, want_b)
             else:
                 parts = []
@@ -282,3 +307,94 @@ def head_forward(head, feats):
     if not head.iou_branch:
         return cls, reg
     return cls, reg, [t[:, n[0]:n[0] + n[1]] for t in ri]
+
+
+# ------------------------------------------------------------------ FCOS heads
+def fcos_head_supported(head, sizes, batch):
+    """the module side of fcos_usable: what fcos_head_forward computes for this head on per-level
+    (H, W) feature sizes.  No device needed (the library's size queries run on the host)."""
+    from . import _lib, fcos_ops
+    from .winograd_train import _fcos_tower_layer, _library_loads
+    towers = list(head.cls_convs) + list(head.reg_convs)
+    outs = [head.fcos_cls, head.fcos_centerness, head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else [])
+    F_ = head.feat_channels
+    if head.in_channels % 32 or F_ % 32 or not towers or len(head.cls_convs) != len(head.reg_convs) \
+            or not 1 <= len(sizes) <= min(len(head.scales), 8):
+        return False
+    if not all(_fcos_tower_layer(m, F_) for m in towers):
+        return False
+    if any(mc.norm.num_groups != mr.norm.num_groups or mc.norm.eps != mr.norm.eps
+           for mc, mr in zip(head.cls_convs, head.reg_convs)):
+        return False                      # one GroupNorm node for both towers of a layer
+    if not all(_plain(c) and c.in_channels == F_ for c in outs):
+        return False
+    if not _library_loads():
+        return False
+    if not all(fcos_ops.groupnorm_bf16_supported(sizes, batch, 2 * F_, 2 * n)
+               and fcos_ops.groupnorm_bf16_supported(sizes, batch, F_, n)       # (the per-tower fallback)
+               for n in set(m.norm.num_groups for m in towers)):
+        return False
+    d = _lib.Conv3x3Desc()
+    d.num_levels, d.batch, d.groups = len(sizes), int(batch), 2
+    d.cin = d.cout = d.x_stride = d.y_stride = int(F_)
+    for l, (h, w) in enumerate(sizes):
+        d.H[l], d.W[l] = int(h), int(w)
+    return int(_lib.lib().ia_conv3x3_bf16_wgrad_workspace_bytes(C.byref(d))) > 0
+
+
+def fcos_usable(feats, head):
+    """what fcos_head_forward covers: CUDA fp32 / bf16 features with autograd on, channel counts the
+    MFMA kernels take, towers of 3x3 convolution without bias + GroupNorm + ReLU with whole 16-byte
+    columns per group, and a library whose weight-gradient and GroupNorm kernels accept the sizes"""
+    feats = list(feats)
+    return (torch.is_grad_enabled() and len(feats) > 0
+            and all(x.is_cuda and x.dtype in (torch.float32, _BF) and x.dim() == 4
+                    and x.shape[1] == head.in_channels for x in feats)
+            and fcos_head_supported(head, [tuple(x.shape[-2:]) for x in feats], feats[0].shape[0]))
+
+
+def _packed_outputs(convs, feat):
+    """several output convolutions of one tower as one bf16 node (columns padded with zero weight and
+    bias to an even count: the forward kernel stores channel pairs) -> per convolution the list of
+    per-level fp32 NCHW-contiguous maps"""
+    n = [c.out_channels for c in convs]
+    pad = sum(n) % 2
+    w0, b0 = convs[0].weight, convs[0].bias
+    if len(convs) == 1 and not pad:
+        w, b = w0, b0
+    else:
+        w = torch.cat([c.weight for c in convs] + ([w0.new_zeros((pad,) + tuple(w0.shape[1:]))] if pad else []))
+        b = torch.cat([c.bias for c in convs] + ([b0.new_zeros(pad)] if pad else []))
+    ys = conv_levels([feat], w, b)[0]
+    res, off = [], 0
+    for k in n:
+        res.append([t[:, off:off + k].to(torch.float32, memory_format=torch.contiguous_format) for t in ys])
+        off += k
+    return res
+
+
+def fcos_head_forward(head, feats):
+    """_FCOSHeadBase.forward (multi_apply(forward_single)) in bf16: the features cast once to bf16
+    channels-last; per tower layer one convolution node for both towers (the first as one convolution
+    with 2F outputs on the shared input, the others as two groups on the channel halves), no bias, no
+    ReLU, and ONE GroupNorm + ReLU node on the 2F-channel activation (2 x num_groups groups, the
+    towers' gamma / beta concatenated); fcos_cls | fcos_centerness as one output convolution on the
+    cls half (81 -> 82 columns), fcos_reg [| fcos_iou] as one on the reg half (5 -> 6; 4 in the plain
+    head).  The outputs become fp32 NCHW maps and bbox_pred = exp(scale_l * reg) runs in torch in
+    fp32: the reference's tuple (cls[L], bbox[L], centerness[L][, iou[L]]), which the fused loss node
+    takes."""
+    from .fcos_ops import groupnorm_relu_bf16_towers
+    xs = [x.to(dtype=_BF, memory_format=_CL) for x in feats]
+    cur = [xs, xs]
+    for mc, mr in zip(head.cls_convs, head.reg_convs):
+        cur = conv_levels(cur, torch.cat([mc.conv.weight, mr.conv.weight]), None, relu=False)
+        gc, gr = mc.norm, mr.norm
+        cur = list(groupnorm_relu_bf16_towers(cur[0], cur[1], torch.cat([gc.weight, gr.weight]),
+                                              torch.cat([gc.bias, gr.bias]), 2 * gc.num_groups, gc.eps))
+    cls_feat, reg_feat = cur
+    cls, ctr = _packed_outputs([head.fcos_cls, head.fcos_centerness], cls_feat)
+    ri = _packed_outputs([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []), reg_feat)
+    bbox = [scale(t).exp() for t, scale in zip(ri[0], head.scales)]
+    if not head.iou_branch:
+        return cls, bbox, ctr
+    return cls, bbox, ctr, ri[1]

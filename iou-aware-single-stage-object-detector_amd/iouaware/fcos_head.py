@@ -6,7 +6,9 @@ constructor kwargs, parameter names and method signatures.
     modules.  In training with `train_winograd = True` (opt-in; where
     winograd_train.fcos_usable holds) forward instead runs every tower convolution as one
     Winograd autograd node over all levels and every GroupNorm + ReLU as one HIP node with a HIP
-    backward (fcos_ops.groupnorm_relu); at inference `fuse.fuse_inference(winograd=True)` swaps
+    backward (fcos_ops.groupnorm_relu); with `train_bf16 = True` (opt-in, tried first; where
+    conv3x3_bf16_train.fcos_usable holds) the towers run in bf16 on the MFMA convolution node
+    and the bf16 GroupNorm node (fcos_ops.groupnorm_relu_bf16); at inference `fuse.fuse_inference(winograd=True)` swaps
     in the Winograd runner with the in-place HIP GroupNorm + ReLU (winograd.WinogradFCOSHead)
     and, for bf16 channels-last features, the MFMA convolution towers with the bf16 GroupNorm +
     ReLU (conv3x3_bf16.Bf16ConvFCOSHead);
@@ -94,12 +96,22 @@ class _FCOSHeadBase(nn.Module):
     # training: all-levels Winograd towers + HIP GroupNorm when set and usable.  Off by default: the
     # whole-iteration comparison against the module route is not measured yet
     train_winograd = False
+    # training: bf16 activations on the MFMA convolution kernels and the bf16 GroupNorm node, fp32
+    # master weights (conv3x3_bf16_train.fcos_head_forward).  Off by default: it changes the
+    # training numerics
+    train_bf16 = False
 
     def forward(self, feats):
         """-> (cls_scores[L], bbox_preds[L] (exponentiated distances), centernesses[L][, ious[L]]).
         With `train_winograd = True`, in training on a ROCm device every tower convolution runs once for all levels on the
         Winograd path and every GroupNorm + ReLU as one HIP node, each with its own backward
-        (winograd_train.fcos_head_forward) -- same parameters, same outputs to fp32 rounding."""
+        (winograd_train.fcos_head_forward) -- same parameters, same outputs to fp32 rounding.
+        `train_bf16 = True` is tried first: the same towers in bf16 (conv3x3_bf16_train.
+        fcos_head_forward), fp32 maps out; what it does not cover takes the next route."""
+        if self.training and self.train_bf16:
+            from . import conv3x3_bf16_train
+            if conv3x3_bf16_train.fcos_usable(feats, self):
+                return conv3x3_bf16_train.fcos_head_forward(self, feats)
         if self.training and self.train_winograd:
             from . import winograd_train
             if winograd_train.fcos_usable(feats, self):

@@ -1,7 +1,8 @@
 """torch front-end of the FCOS kernels (csrc/groupnorm.hip, csrc/pointdecode.hip,
 csrc/pointloss.hip): the point heads' post-conv paths (ia_point_get_bboxes: IoU-aware;
 ia_point_ctr_get_bboxes: plain FCOS, the centerness map in the third slot), the towers'
-GroupNorm + ReLU (in place for inference, groupnorm_relu: the autograd node), and the training
+GroupNorm + ReLU (in place for inference; groupnorm_relu / groupnorm_relu_bf16: the fp32 and bf16
+autograd nodes), and the training
 side: point targets and the all-levels loss node.
 Device tensors only, launched on the current torch stream, like ops.py."""
 import ctypes as C
@@ -213,9 +214,10 @@ def scale_exp_(xs, scales):
     return xs
 
 
-def _gn_check(name, xs, gamma, beta, dtype=torch.float32):
-    """the argument contract of groupnorm_relu_ / groupnorm_relu: ValueError before the device is
-    touched -> channels.  dtype: what the levels hold (the training node: fp32 only)"""
+def _gn_check(name, xs, gamma, beta, dtype=torch.float32, takes=None):
+    """the argument contract of groupnorm_relu_ / groupnorm_relu / groupnorm_relu_bf16: ValueError
+    before the device is touched -> channels.  dtype: what the levels hold (the fp32 training node:
+    fp32 only; the bf16 one: bf16 only)"""
     if not xs or len(xs) > _lib.IA_MAX_LEVELS:
         raise ValueError('1..%d levels' % _lib.IA_MAX_LEVELS)
     ch = int(xs[0].shape[1]) if xs[0].dim() == 4 else -1
@@ -224,7 +226,7 @@ def _gn_check(name, xs, gamma, beta, dtype=torch.float32):
                 or x.shape[0] != xs[0].shape[0] or x.device != xs[0].device \
                 or not x.is_contiguous(memory_format=torch.channels_last):
             raise ValueError('%s takes %s channels-last (B, %d, H, W) levels on one device'
-                             % (name, 'fp32' if dtype == torch.float32 else 'fp32 or bf16', ch))
+                             % (name, takes or ('fp32' if dtype == torch.float32 else 'fp32 or bf16'), ch))
     for t in (gamma, beta):
         if t.dtype != torch.float32 or t.numel() != ch or not t.is_contiguous() or t.device != xs[0].device:
             raise ValueError('gamma / beta: (%d,) fp32 on the device' % ch)
@@ -313,6 +315,164 @@ def groupnorm_relu(xs, gamma, beta, groups, eps=1e-5, relu=True):
     xs = list(xs)
     _gn_check('groupnorm_relu', xs, gamma, beta)
     return list(_GroupNormReluFn.apply(gamma, beta, int(groups), float(eps), bool(relu), *xs))
+
+
+# ------------------------------------------------------------------ the bf16 training node
+_CL = torch.channels_last
+
+
+def _gn_upstream_bf16(d):
+    """an upstream gradient as the bf16 kernels read it: bf16, channels-last, 16-byte aligned -- taken
+    as it is when autograd hands it over that way (what the bf16 convolution node's backward
+    returns), a copy otherwise"""
+    if d.dtype == torch.bfloat16 and d.is_contiguous(memory_format=_CL) and d.data_ptr() % 16 == 0:
+        return d
+    d = d.to(torch.bfloat16).contiguous(memory_format=_CL)
+    return d.clone(memory_format=_CL) if d.data_ptr() % 16 else d
+
+
+def _halves_of_one(a, b):
+    """whether a and b are the channel halves [0, F) and [F, 2F) of ONE dense channels-last
+    (B, 2F, H, W) bf16 tensor: views of one storage, b right behind a in every pixel.  Never true for
+    separate allocations that merely lie side by side."""
+    F_ = a.shape[1]
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.dim() != 4 or a.shape != b.shape \
+            or a.stride() != b.stride() or a.device != b.device \
+            or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr() \
+            or b.data_ptr() != a.data_ptr() + 2 * F_ or a.data_ptr() % 16:
+        return False
+    return _wide(a).is_contiguous(memory_format=_CL)
+
+
+def _wide(a):
+    """the (B, 2F, H, W) tensor that starts where the channel half `a` starts"""
+    return a.as_strided((a.shape[0], 2 * a.shape[1], a.shape[2], a.shape[3]), a.stride())
+
+
+def _empty_cl(like):
+    B, ch, h, w = like.shape
+    return torch.empty((B, h, w, ch), dtype=like.dtype, device=like.device).permute(0, 3, 1, 2)
+
+
+class _GroupNormReluBf16Fn(torch.autograd.Function):
+    """_GroupNormReluFn on bf16 channels-last levels (k_gn_stats_bf16, k_gn_apply_to_bf16,
+    k_gn_bwd_reduce_bf16, k_gn_bwd_apply_bf16, k_gn_bwd_params): 2 launches forward, 2 (+ 1 for the
+    parameter gradients) backward; keeps x and the fp64 (mean, rstd), not y.
+
+    halves == 2: the inputs are 2 x L channel halves (tower-major) of L dense (B, 2F, H, W) tensors
+    (_halves_of_one holds for every level: the caller checks) and the node runs on the wide tensors;
+    its outputs, and the input gradients it returns, are again the two halves of one tensor per
+    level, so that the bf16 convolution nodes on either side keep addressing both towers in one
+    pass."""
+
+    @staticmethod
+    def forward(ctx, gamma, beta, groups, eps, relu, halves, *xs):
+        L_ = len(xs) // halves
+        wide = [_wide(x) for x in xs[:L_]] if halves == 2 else list(xs)
+        ch = int(wide[0].shape[1])
+        g = _wino_geom(wide)
+        L = _lib.lib()
+        dt = _lib.IA_BF16
+        nbytes = L.ia_groupnorm_workspace_bytes_dt(C.byref(g), ch, groups, dt)
+        nsaved = L.ia_groupnorm_saved_bytes_dt(C.byref(g), ch, groups, dt)
+        nbwd = L.ia_groupnorm_bwd_workspace_bytes_dt(C.byref(g), ch, groups, dt)
+        if nbytes == 0 or nsaved == 0 or nbwd == 0:
+            raise _lib.IouAwareLibraryError('unsupported bf16 GroupNorm geometry (channels %d, groups %d)'
+                                            % (ch, groups))
+        dev = wide[0].device
+        gamma_, beta_ = gamma.detach(), beta.detach()
+        ws = _gn_workspace(dev, max(nbytes, nbwd))
+        saved = torch.empty(int(nsaved), dtype=torch.uint8, device=dev)
+        ys = [_empty_cl(x) for x in wide]
+        px = _level_ptrs(wide)
+        _lib.check(L.ia_groupnorm_stats_dt(C.byref(g), px, dt, ch, groups, _ptr(ws), nbytes, _stream()),
+                   'ia_groupnorm_stats_dt')
+        _lib.check(L.ia_groupnorm_apply_to_dt(C.byref(g), px, _level_ptrs(ys), dt, ch, groups, _ptr(gamma_),
+                                              _ptr(beta_), eps, int(relu), _ptr(ws), nbytes, _ptr(saved),
+                                              nsaved, _stream()), 'ia_groupnorm_apply_to_dt')
+        ctx.geom, ctx.cfg, ctx.sizes, ctx.halves = g, (ch, groups, int(relu)), (nsaved, nbwd), halves
+        ctx.save_for_backward(gamma, beta, saved, *wide)
+        if halves == 2:
+            F_ = ch // 2
+            return tuple([y[:, :F_] for y in ys] + [y[:, F_:] for y in ys])
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        gamma, beta, saved = ctx.saved_tensors[:3]
+        xs = ctx.saved_tensors[3:]
+        ch, groups, relu = ctx.cfg
+        nsaved, nbwd = ctx.sizes
+        g, L, dev, dt = ctx.geom, _lib.lib(), xs[0].device, _lib.IA_BF16
+        gamma_, beta_ = gamma.detach(), beta.detach()
+        if ctx.halves == 2:
+            # the two towers' gradients as one tensor per level: in place where they are the halves of
+            # one (the next convolution node's input gradients are), one copy otherwise
+            n = len(xs)
+            dys = [_wide(a) if _halves_of_one(a, b) else torch.cat((a.to(torch.bfloat16), b.to(torch.bfloat16)), 1)
+                   for a, b in zip(dys[:n], dys[n:])]
+        dys = [_gn_upstream_bf16(d) for d in dys]
+        ws = _gn_workspace(dev, nbwd)
+        px, pdy = _level_ptrs(xs), _level_ptrs(dys)
+        _lib.check(L.ia_groupnorm_bwd_reduce_dt(C.byref(g), px, pdy, dt, ch, groups, _ptr(gamma_), _ptr(beta_),
+                                                relu, _ptr(saved), nsaved, _ptr(ws), nbwd, _stream()),
+                   'ia_groupnorm_bwd_reduce_dt')
+        need_x = any(ctx.needs_input_grad[6:])
+        dxs = [_empty_cl(x) for x in xs] if need_x else None
+        dgamma = torch.empty(ch, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dbeta = torch.empty(ch, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        if need_x or dgamma is not None or dbeta is not None:
+            _lib.check(L.ia_groupnorm_bwd_apply_dt(C.byref(g), px, pdy, _level_ptrs(dxs) if need_x else None,
+                                                   dt, ch, groups, _ptr(gamma_), _ptr(beta_), relu,
+                                                   _ptr(saved), nsaved, _ptr(ws), nbwd, _ptr(dgamma),
+                                                   _ptr(dbeta), _stream()), 'ia_groupnorm_bwd_apply_dt')
+        if not need_x:
+            gx = (None,) * (ctx.halves * len(xs))
+        elif ctx.halves == 2:
+            F_ = ch // 2
+            gx = tuple([d[:, :F_] for d in dxs] + [d[:, F_:] for d in dxs])
+        else:
+            gx = tuple(dxs)
+        return (dgamma, dbeta, None, None, None, None) + gx
+
+
+def groupnorm_bf16_supported(sizes, batch, channels, groups):
+    """whether the bf16 GroupNorm training kernels cover per-level (H, W) sizes at this batch, channel
+    and group count (the library's own answer: its workspace query; whole 16-byte columns inside a
+    group, i.e. channels / groups % 8 == 0)"""
+    g = winograd._wino_geom([tuple(int(v) for v in s) for s in sizes], int(batch))
+    return _lib.lib().ia_groupnorm_bwd_workspace_bytes_dt(C.byref(g), int(channels), int(groups),
+                                                          _lib.IA_BF16) != 0
+
+
+def groupnorm_relu_bf16(xs, gamma, beta, groups, eps=1e-5, relu=True):
+    """groupnorm_relu for bf16 training: xs[l] (B, ch, H_l, W_l) bf16 channels-last, gamma / beta (ch,)
+    fp32 -> list of new bf16 channels-last tensors, y = bf16(relu?(float(x) * s + t)) with fp64
+    statistics of the stored values (the bits of groupnorm_relu_ on a copy).  One autograd node with
+    gradients for every x_l (bf16, rounded once), gamma and beta (fp32), for those that require them.
+    The upstream gradient is read as it is when it is bf16 channels-last."""
+    xs = list(xs)
+    _gn_check('groupnorm_relu_bf16', xs, gamma, beta, torch.bfloat16, 'bf16')
+    return list(_GroupNormReluBf16Fn.apply(gamma, beta, int(groups), float(eps), bool(relu), 1, *xs))
+
+
+def groupnorm_relu_bf16_towers(xa, xb, gamma, beta, groups, eps=1e-5, relu=True):
+    """two towers at once: xa[l] / xb[l] (B, F, H_l, W_l) bf16, gamma / beta (2F,) fp32 (the towers'
+    parameters concatenated), groups = the sum of both towers' groups -> (ya, yb).  Where every level's
+    xa[l] and xb[l] are the channel halves of one dense channels-last tensor (the bf16 convolution
+    node's outputs) this is ONE node on the 2F-channel tensors whose outputs and input gradients are
+    halves of one tensor again; otherwise one node per tower on contiguous copies."""
+    xa, xb = list(xa), list(xb)
+    if len(xa) != len(xb) or not xa or len(xa) > _lib.IA_MAX_LEVELS:
+        raise ValueError('1..%d levels per tower' % _lib.IA_MAX_LEVELS)
+    if all(_halves_of_one(a, b) for a, b in zip(xa, xb)):
+        _gn_check('groupnorm_relu_bf16_towers', [_wide(a) for a in xa], gamma, beta, torch.bfloat16, 'bf16')
+        out = _GroupNormReluBf16Fn.apply(gamma, beta, int(groups), float(eps), bool(relu), 2, *(xa + xb))
+        return list(out[:len(xa)]), list(out[len(xa):])
+    F_ = int(xa[0].shape[1])
+    return tuple(groupnorm_relu_bf16([x.contiguous(memory_format=_CL) for x in xs], gamma[k * F_:(k + 1) * F_],
+                                     beta[k * F_:(k + 1) * F_], int(groups) // 2, eps, relu)
+                 for k, xs in enumerate((xa, xb)))
 
 
 # ------------------------------------------------------------------ training

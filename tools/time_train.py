@@ -7,8 +7,10 @@
                                                              config, or CONFIG=<an mmdet config file
                                                              with model / train_cfg / test_cfg>
     TRAIN_WINOGRAD=0    the head's module route (bbox_head.train_winograd = False)
-    TRAIN_BF16=1        the RetinaNet heads' bf16 route (bbox_head.train_bf16 = True: bf16 activations on
-                        the MFMA convolutions, fp32 master weights; iouaware/conv3x3_bf16_train.py)
+    TRAIN_BF16=1        the heads' bf16 route (bbox_head.train_bf16 = True: bf16 activations on the MFMA
+                        convolutions -- and, in the FCOS towers, the bf16 GroupNorm node --, fp32 master
+                        weights; iouaware/conv3x3_bf16_train.py)
+The result line names the head route that ran (bf16 / winograd / module).
     ITERS=n             timed iterations (default 5)"""
 import sys, os, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -43,6 +45,18 @@ if os.environ.get('TRAIN_BF16') is not None:
     model.bbox_head.train_bf16 = bool(int(os.environ['TRAIN_BF16']))
 print('model %s  head %s  train_winograd %s  train_bf16 %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd,
                                                                getattr(model.bbox_head, 'train_bf16', False)))
+# which head route runs: count the calls of the route functions
+from iouaware import conv3x3_bf16_train, winograd_train
+ROUTE = []
+def _count(mod, name, tag):
+    real = getattr(mod, name)
+    def spy(*a, **k):
+        ROUTE.append(tag)
+        return real(*a, **k)
+    setattr(mod, name, spy)
+for _name in ('head_forward', 'fcos_head_forward'):
+    _count(conv3x3_bf16_train, _name, 'bf16')
+    _count(winograd_train, _name, 'winograd')
 opt = build_optimizer(model, dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001))
 img = torch.randn(B, 3, 800, 1344, device='cuda')
 if os.environ.get('FUSE'):
@@ -56,9 +70,11 @@ gtb = [torch.from_numpy(x).cuda() for x in gts]; gtl = [torch.from_numpy(x).cuda
 metas = [synth.img_meta(800, 1333, 800, 1344) for _ in range(B)]
 for _ in range(3): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats(); t = time.time(); n = int(os.environ.get('ITERS', 5))
+del ROUTE[:]
 for _ in range(n): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); dt = (time.time() - t) / n
-print('B=%d  %.1f ms/iter  %.1f img/s  loss %s  mem %.1f GB' % (B, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
+route = '+'.join(sorted(set(ROUTE))) if ROUTE else 'module'
+print('B=%d  head route %s  %.1f ms/iter  %.1f img/s  loss %s  mem %.1f GB' % (B, route, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
 if os.environ.get('TRAIN_ONLY'):
     sys.exit(0)
 # loss part alone (targets + 3 losses fwd + bwd) on fixed head outputs
