@@ -651,6 +651,25 @@ int ia_grouped_conv3x3_nhwc(const float *x, const float *wpack, const float *bia
                             int batch, int H, int W, int channels, int groups, int stride, int relu,
                             void *stream);
 
+/* The bf16 twin (csrc/gconv_bf16.hip): channels-last bf16 in and out, fp32 accumulation on
+ * v_mfma_f32_16x16x32_bf16, fp32 bias (+ ReLU) in fp32, one round-to-nearest-even to bf16 at the
+ * store.  A wavefront owns 32 consecutive channels: channels % 32 == 0, 4 / 8 / 16 / 32 channels
+ * per group, stride 1 or 2, x / y / wpack 16-byte aligned, batch * Ho <= INT32_MAX; anything else
+ * is IA_E_ARG before the device is touched.
+ * ia_grouped_conv3x3_pack_bf16 is HOST code: fp32 weight (C, C/groups, 3, 3) and optional fp32
+ * per-output-channel scale -> wpack (host pointer) of ia_grouped_conv3x3_packed_bytes_bf16 bytes
+ * (0 for an unsupported shape), laid out (C/32, 9, 2, 64, 8):
+ *   wpack[(((sg * 9 + t) * 2 + co) * 64 + lane) * 8 + j] = bf16(scale[o] * weight[o][in % Cg][t])
+ *   with o = 32 sg + 16 co + (lane & 15), in = 32 sg + 8 (lane >> 4) + j, the product in fp32 and
+ *   rounded to nearest even once; 0 where o and in lie in different groups.
+ * Copy wpack to the device once.                                                            */
+size_t ia_grouped_conv3x3_packed_bytes_bf16(int channels, int groups);
+int ia_grouped_conv3x3_pack_bf16(const float *weight, const float *scale, int channels, int groups,
+                                 uint16_t *wpack);
+int ia_grouped_conv3x3_bf16_nhwc(const uint16_t *x, const uint16_t *wpack, const float *bias,
+                                 uint16_t *y, int batch, int H, int W, int channels, int groups,
+                                 int stride, int relu, void *stream);
+
 /* mmdet.ops.sigmoid_focal_loss: sigmoid_focal_loss_cuda.forward / .backward
  * (mmdet/ops/sigmoid_focal_loss/src/sigmoid_focal_loss_cuda.cu:23-63,65-105;
  * binding sigmoid_focal_loss.cpp:17-43).  logits (N,C) fp32, targets (N) int64,

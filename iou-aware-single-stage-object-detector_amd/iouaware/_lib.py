@@ -207,6 +207,9 @@ SIGNATURES = {
                                    _vp]),
     'ia_grouped_conv3x3_pack': (_i, [_vp, _vp, _i, _i, _vp]),
     'ia_grouped_conv3x3_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'ia_grouped_conv3x3_packed_bytes_bf16': (C.c_size_t, [_i, _i]),
+    'ia_grouped_conv3x3_pack_bf16': (_i, [_vp, _vp, _i, _i, _vp]),
+    'ia_grouped_conv3x3_bf16_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_sigmoid_focal_loss_fwd': (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),
     'ia_sigmoid_focal_loss_bwd': (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
     'ia_sigmoid_focal_loss_fwd_dt': (_i, [_vp, _i, _vp, _i, _i, _f, _f, _vp, _vp]),

@@ -131,6 +131,9 @@ class ResNet(nn.Module):
                      50: (Bottleneck, (3, 4, 6, 3)), 101: (Bottleneck, (3, 4, 23, 3)),
                      152: (Bottleneck, (3, 8, 36, 3))}
     _groups, _base_width = 1, 4
+    # ResNeXt in bf16 inference: conv2 on the bf16 MFMA kernel of csrc/gconv_bf16.hip (False: the
+    # library's grouped convolution + an affine pass).  Read by fuse_inference.
+    gconv_bf16 = True
 
     def __init__(self, depth, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
                  out_indices=(0, 1, 2, 3), style='pytorch', frozen_stages=-1, conv_cfg=None,

@@ -178,6 +178,17 @@ def _bottleneck_run(self, x, h1=None, nxt=None):
             out = ops.channel_affine_act_(out, f['s1'], f['b1'], relu=True)
         out = ops.grouped_conv3x3(out, gw, f['b2'], self.conv2.groups, self.conv2.stride[0],
                                   relu=True)
+    elif gw is not None and out.dtype == torch.bfloat16 and self.conv2.in_channels % 32 == 0 \
+            and out.is_contiguous(memory_format=torch.channels_last) and self._ia_gconv_bf16:
+        # ResNeXt in bf16: the same layer on the bf16 MFMA kernel of csrc/gconv_bf16.hip (weights
+        # packed at the first bf16 call: BN scale folded in fp32, rounded to bf16 once)
+        if pre is not None:
+            out = ops.channel_affine_act_(out, f['s1'], f['b1'], relu=True)
+        wp = f.get('_gconv2_bf16')
+        if wp is None:
+            wp = f['_gconv2_bf16'] = ops.pack_grouped_weight_bf16(self.conv2.weight, f['s2'])
+        out = ops.grouped_conv3x3_bf16(out, wp, f['b2'], self.conv2.groups, self.conv2.stride[0],
+                                       relu=True)
     elif wino is not None and wino.usable(out):
         # (conv1's BN + ReLU on load,) conv2 + its folded BN + ReLU in the Winograd path
         out = wino(out, pre=pre)
@@ -643,11 +654,19 @@ def fuse_inference(model, winograd=False, train=False):
         for m in model.modules():
             if type(m).__name__ == 'FPN':
                 fpn_convs.update(id(c) for c in m.fpn_convs)
+    # the backbone's `gconv_bf16` switch (bf16 ResNeXt: grouped conv2 on csrc/gconv_bf16.hip) is read
+    # here for its bottlenecks; a bottleneck fused on its own takes the class default
+    gconv_bf16 = {}
+    for m in model.modules():
+        if isinstance(m, ResNet):
+            gconv_bf16.update((id(b), bool(m.gconv_bf16)) for b in m.modules() if isinstance(b, Bottleneck))
     for m in model.modules():
         fwd = _forward_for(m, winograd)
         if fwd is None:
             continue
         m._ia_opts = (bool(winograd), id(m) in fpn_convs, bool(train and winograd))
+        if isinstance(m, Bottleneck):
+            m._ia_gconv_bf16 = gconv_bf16.get(id(m), bool(ResNet.gconv_bf16))
         if not _fold(m):
             del m._ia_opts
             continue
@@ -681,7 +700,8 @@ def unfuse_inference(model):
         if hasattr(m, '_ia_layer'):
             del m._ia_layer
             m.__dict__.pop('forward', None)
-        for attr in ('_ia_fused', '_ia_wino', '_ia_c3', '_ia_opts', '_ia_stamp', '_ia_dirty', '_ia_stamp_slots'):
+        for attr in ('_ia_fused', '_ia_wino', '_ia_c3', '_ia_opts', '_ia_stamp', '_ia_dirty', '_ia_stamp_slots',
+                     '_ia_gconv_bf16'):
             if hasattr(m, attr):
                 delattr(m, attr)
                 for name in ('forward', '_stem', '_stages'):

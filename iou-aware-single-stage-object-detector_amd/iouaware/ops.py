@@ -1272,6 +1272,51 @@ def grouped_conv3x3(x, wpack, bias, groups, stride=1, relu=False):
     return y
 
 
+def pack_grouped_weight_bf16(weight, scale=None):
+    """(C, C/groups, 3, 3) grouped conv weight (+ per-output-channel scale, folded in fp32 and rounded
+    to bf16 once) -> the per-lane MFMA operand layout of csrc/gconv_bf16.hip as a flat bf16 tensor on
+    the weight's device.  Host-side arrangement (once per fold), through the C-ABI helper."""
+    w = weight.detach().to('cpu', torch.float32).contiguous()
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError('pack_grouped_weight_bf16 needs a (C, C/groups, 3, 3) weight')
+    Cn, cg = int(w.shape[0]), int(w.shape[1])
+    groups = Cn // max(cg, 1)
+    nbytes = _lib.lib().ia_grouped_conv3x3_packed_bytes_bf16(Cn, groups) if groups * cg == Cn else 0
+    if nbytes == 0:
+        raise ValueError('grouped_conv3x3_bf16 covers 4 / 8 / 16 / 32 channels per group and a '
+                         'multiple of 32 channels, not %d channels in %d groups' % (Cn, groups))
+    out = torch.empty(nbytes // 2, dtype=torch.int16)
+    sc = None if scale is None else scale.detach().to('cpu', torch.float32).contiguous()
+    _lib.check(_lib.lib().ia_grouped_conv3x3_pack_bf16(w.data_ptr(), None if sc is None else sc.data_ptr(),
+                                                       Cn, groups, out.data_ptr()),
+               'ia_grouped_conv3x3_pack_bf16')
+    return out.view(torch.bfloat16).to(weight.device)
+
+
+def grouped_conv3x3_bf16(x, wpack, bias, groups, stride=1, relu=False):
+    """channels-last bf16 (B, C, H, W) -> (B, C, Ho, Wo) bf16, grouped 3x3 / pad 1 conv + fp32 bias
+    (+ReLU), fp32 accumulation, one rounding at the store (csrc/gconv_bf16.hip)"""
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('grouped_conv3x3_bf16 needs a channels-last bf16 tensor')
+    _require_gpu(x, 'x')
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()
+                             or bias.numel() != x.shape[1]):
+        raise ValueError('grouped_conv3x3_bf16 needs a contiguous fp32 bias of C values')
+    B, Cn, H, W = x.shape
+    groups = int(groups)
+    if wpack.dtype != torch.bfloat16 or not wpack.is_contiguous() \
+            or wpack.numel() * 2 != _lib.lib().ia_grouped_conv3x3_packed_bytes_bf16(Cn, groups):
+        raise ValueError('grouped_conv3x3_bf16: wpack is not pack_grouped_weight_bf16 of a '
+                         '%d-channel, %d-group weight' % (Cn, groups))
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    y = torch.empty((B, Cn, Ho, Wo), dtype=torch.bfloat16, device=x.device,
+                    memory_format=torch.channels_last)
+    _lib.check(_lib.lib().ia_grouped_conv3x3_bf16_nhwc(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), B, H, W,
+                                                       Cn, groups, int(stride), int(bool(relu)),
+                                                       _stream()), 'ia_grouped_conv3x3_bf16_nhwc')
+    return y
+
+
 def test_math(op, x, y=None):
     _require_gpu(x, 'x')
     x = x.contiguous()
