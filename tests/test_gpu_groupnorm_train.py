@@ -38,6 +38,7 @@ DEV = torch.device('cuda:0')
 GN_TOL_SHIFTED = 2e-4         # tests/test_gpu_fcos.py: |mean| / std = 200, absolute, output scale ~ 1
 MAIN = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]       # 800 x 1344, strides 8..128
 ODD = [(23, 37), (11, 19), (3, 5)]                               # 11 x 19 = 209 < one chunk of 256
+EIGHT = [(9, 11), (5, 7), (4, 5), (3, 3), (2, 3), (2, 2), (1, 2), (1, 1)]       # IA_MAX_LEVELS levels
 
 CASES = {
     # name: (sizes, batch, channels, groups, relu, gamma trainable)
@@ -47,7 +48,13 @@ CASES = {
     'batch1': (MAIN, 1, 256, 32, True, True),
     'norelu': (ODD, 2, 256, 32, False, True),
     'frozen': (ODD, 2, 256, 32, True, False),
+    # the edges of the supported geometry: 256 columns per pixel and every per-channel LDS slot;
+    # one column per pixel (256 pixels per pass, two full chunks and a partial one); eight levels
+    'max-channels': ([(5, 7), (2, 3)], 2, 1024, 256, True, True),
+    'min-channels': ([(19, 29)], 2, 4, 1, True, True),
+    'eight-levels': (EIGHT, 2, 32, 4, True, True),
 }
+EDGES = ('max-channels', 'min-channels', 'eight-levels')
 
 
 def _data(seed, sizes, batch, ch, shifted):
@@ -126,13 +133,14 @@ def test_node_against_fp64(case, shifted):
 
 def test_forward_bits_are_those_of_the_in_place_kernels():
     from iouaware import fcos_ops
-    xs, _, gamma, beta = _data(12, ODD, 2, 256, False)
-    dev = [_cl(x) for x in xs]
-    with torch.no_grad():
-        ys = fcos_ops.groupnorm_relu(dev, gamma.to(DEV), beta.to(DEV), 32)
-    assert all(torch.equal(d.cpu(), x) for d, x in zip(dev, xs))           # x untouched
-    fcos_ops.groupnorm_relu_(dev, gamma.to(DEV), beta.to(DEV), 32)
-    assert all(torch.equal(y, d) for y, d in zip(ys, dev))
+    for sizes, batch, ch, groups in [(ODD, 2, 256, 32)] + [CASES[c][:4] for c in EDGES]:
+        xs, _, gamma, beta = _data(12, sizes, batch, ch, False)
+        dev = [_cl(x) for x in xs]
+        with torch.no_grad():
+            ys = fcos_ops.groupnorm_relu(dev, gamma.to(DEV), beta.to(DEV), groups)
+        assert all(torch.equal(d.cpu(), x) for d, x in zip(dev, xs))       # x untouched
+        fcos_ops.groupnorm_relu_(dev, gamma.to(DEV), beta.to(DEV), groups)
+        assert all(torch.equal(y, d) for y, d in zip(ys, dev))
 
 
 def test_bits_repeat_and_do_not_depend_on_the_batch():
