@@ -414,6 +414,19 @@ int ia_im2col3x3_nhwc(const void *x, void *col, int B, int H, int W, int C, int 
 int ia_conv1x1_strided(const void *x, const void *W_kn, const float *bias, const void *residual,
                        void *D, int B, int H, int W, int k, int n, int stride, int relu, int dtype,
                        void *workspace, size_t workspace_bytes, void *stream);
+/* The adjoint of ia_im2col3x3_nhwc in gather form -- the input gradient of the strided 3x3
+ * training node (iouaware/train_fuse.py, conv3x3_strided), after dcol = g . W_kn^T:
+ *   dx[b][yi][xi][c] = sum over the taps (dy, dx), tap = dy * 3 + dx, for which (yi + 1 - dy) and
+ *   (xi + 1 - dx) are multiples of `stride` and the quotients (yo, xo) lie inside Ho x Wo, of
+ *   dcol[(b, yo, xo)][tap * C + c]
+ * for the channels-last dx (B, H, W, C) and the (B * Ho * Wo, 9 * C) row-major dcol.  The terms are
+ * added in ascending tap order, each in one fp32 add, without atomics: the same bits in every run.
+ * Every element of dx is written exactly once, 0.0f where no tap reads the pixel (strides 3 / 4);
+ * dx needs no initialisation.  dtype IA_F32 only, C a multiple of 4, both pointers 16-byte aligned,
+ * stride 1..4; anything else: IA_E_ARG.  Reads dcol once and writes dx once
+ * (9 * C * B * Ho * Wo * 4 + B * H * W * C * 4 bytes).                                           */
+int ia_col2im3x3_nhwc(const void *dcol, void *dx, int B, int H, int W, int C, int stride, int dtype,
+                      void *stream);
 
 /* How the library kernel of a new GEMM shape is chosen.
  *   2  FROZEN (default): the entry of the tuning table below, else the library heuristic's first

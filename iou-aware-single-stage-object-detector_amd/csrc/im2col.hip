@@ -52,6 +52,66 @@ __global__ __launch_bounds__(256) void k_im2col3x3(Im2colArgs a)
     }
 }
 
+// The adjoint of k_im2col3x3 (the input gradient of the training node, iouaware/train_fuse.py) in
+// GATHER form: every input pixel collects the taps that read it,
+//   dx[b][yi][xi][c] = sum over (dy, dx) with (yi + 1 - dy) = S * yo, (xi + 1 - dx) = S * xo, (yo, xo)
+//                      inside Ho x Wo, of  dcol[(b, yo, xo)][(dy * 3 + dx) * C + c]
+// in ascending tap order, one fp32 add per term, no atomics; every dx element is written exactly
+// once (0.0f where no tap reads the pixel: strides 3 / 4).  Only dy = (yi + 1) mod S (+ S, + 2 S) can
+// qualify, so a pixel has at most NJ x NJ candidate taps, NJ = ceil(3 / S): 9 / 4 / 1 / 1.
+// HBM-bound: dcol read once, dx written once.  One image row per blockIdx.x (the pixel is decoded
+// once per thread, with one division of the block-uniform row index by H and none in the tap loop:
+// S is a template parameter), a group of min(64, C / 4) lanes per pixel walking its C contiguous
+// channels 16 bytes per lane; the candidates' element offsets are 64-bit and fixed before the
+// channel loop, a candidate that does not qualify loads dcol's first run (always there) and is not
+// added.
+struct Col2imArgs {
+    const float4 *dcol;
+    float4 *dx;
+    int32_t H, W, Ho, Wo;
+    int32_t cv;          // 16-byte vectors per pixel (C / 4)
+    int32_t shift;       // log2 of the lanes per pixel: min(64, cv) rounded down to a power of two
+};
+
+template <int S>
+__global__ __launch_bounds__(256) void k_col2im3x3(Col2imArgs a)
+{
+    constexpr int NJ = (S + 2) / S;
+    const int lane = threadIdx.x & 63;
+    const int lanes = 1 << a.shift, sub = lane >> a.shift, l = lane & (lanes - 1);
+    const int per_wave = 64 >> a.shift;
+    const int xi = ((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6)) * per_wave + sub;
+    if (xi >= a.W) return;
+    const int row = (int)blockIdx.x;                      // b * H + yi
+    const int b = row / a.H, yi = row - b * a.H;
+    const int dy0 = (yi + 1) % S, dx0 = (xi + 1) % S;
+    int64_t off[NJ * NJ];
+    bool ok[NJ * NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int dy = dy0 + j * S, ny = yi + 1 - dy, yo = ny / S;
+        const bool oky = dy < 3 && ny >= 0 && yo < a.Ho;
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) {
+            const int dx = dx0 + i * S, nx = xi + 1 - dx, xo = nx / S;
+            const bool in = oky && dx < 3 && nx >= 0 && xo < a.Wo;
+            ok[j * NJ + i] = in;
+            off[j * NJ + i] = in ? ((((int64_t)b * a.Ho + yo) * a.Wo + xo) * 9 + (dy * 3 + dx)) * a.cv : 0;
+        }
+    }
+    float4 *dst = a.dx + ((int64_t)row * a.W + xi) * a.cv;
+    for (int c = l; c < a.cv; c += lanes) {
+        float4 v[NJ * NJ];
+#pragma unroll
+        for (int t = 0; t < NJ * NJ; ++t) v[t] = a.dcol[off[t] + c];
+        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int t = 0; t < NJ * NJ; ++t)
+            if (ok[t]) { acc.x += v[t].x; acc.y += v[t].y; acc.z += v[t].z; acc.w += v[t].w; }
+        dst[c] = acc;
+    }
+}
+
 }  // namespace ia
 
 extern "C" size_t ia_im2col3x3_bytes(int B, int H, int W, int C, int stride, int dtype)
@@ -82,5 +142,33 @@ extern "C" int ia_im2col3x3_nhwc(const void *x, void *col, int B, int H, int W, 
     const int64_t blocks = (a.runs + per_block - 1) / per_block;
     if (blocks > 2147483647LL) return IA_E_ARG;
     hipLaunchKernelGGL(ia::k_im2col3x3, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+extern "C" int ia_col2im3x3_nhwc(const void *dcol, void *dx, int B, int H, int W, int C, int stride,
+                                 int dtype, void *stream)
+{
+    if (!dcol || !dx || B < 1 || H < 1 || W < 1 || C < 1 || stride < 1 || stride > 4) return IA_E_ARG;
+    if (dtype != IA_F32 || C % 4) return IA_E_ARG;
+    if (((uintptr_t)dcol | (uintptr_t)dx) & 15) return IA_E_ARG;
+    ia::Col2imArgs a;
+    a.dcol = (const float4 *)dcol; a.dx = (float4 *)dx;
+    a.H = H; a.W = W;
+    a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
+    a.cv = C / 4;
+    a.shift = 0;
+    while (a.shift < 6 && (2 << a.shift) <= a.cv) ++a.shift;
+    const int64_t rows = (int64_t)B * H;
+    const int per_block = 4 * (64 >> a.shift);
+    const int chunks = (W + per_block - 1) / per_block;
+    if (rows > 2147483647LL || chunks > 65535) return IA_E_ARG;
+    const dim3 grid((unsigned)rows, (unsigned)chunks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (stride) {
+    case 1: hipLaunchKernelGGL(ia::k_col2im3x3<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(ia::k_col2im3x3<2>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(ia::k_col2im3x3<3>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(ia::k_col2im3x3<4>, grid, block, 0, s, a); break;
+    }
     return ia::hip_status(hipGetLastError());
 }

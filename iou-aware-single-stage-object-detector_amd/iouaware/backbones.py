@@ -134,6 +134,10 @@ class ResNet(nn.Module):
     # ResNeXt in bf16 inference: conv2 on the bf16 MFMA kernel of csrc/gconv_bf16.hip (False: the
     # library's grouped convolution + an affine pass).  Read by fuse_inference.
     gconv_bf16 = True
+    # training, opt-in: the stride-2 conv2 of a fused training block (train_fuse.bottleneck_forward)
+    # on the im2col / col2im node instead of the framework's convolution -- the same bits in every
+    # run.  Read by fuse_inference, like gconv_bf16.
+    train_strided = False
 
     def __init__(self, depth, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
                  out_indices=(0, 1, 2, 3), style='pytorch', frozen_stages=-1, conv_cfg=None,

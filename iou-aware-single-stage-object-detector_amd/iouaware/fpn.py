@@ -14,6 +14,11 @@ from .registry import NECKS
 
 @NECKS.register_module
 class FPN(nn.Module):
+    # training, opt-in: the extra strided 3x3 levels (P6 / P7) of the fused training route
+    # (train_fuse.fpn_forward) on the im2col / col2im node instead of the framework's convolution --
+    # the same bits in every run.  Read at every forward.
+    train_strided = False
+
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1,
                  add_extra_convs=False, extra_convs_on_inputs=True, relu_before_extra_convs=False,
                  conv_cfg=None, norm_cfg=None, activation=None):

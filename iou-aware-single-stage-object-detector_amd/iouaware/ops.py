@@ -1080,6 +1080,69 @@ def conv3x3_im2col(x, w_kn, bias=None, stride=2, relu=False):
     return out
 
 
+def im2col3x3(x, stride):
+    """the column matrix of a channels-last fp32 (B, C, H, W) tensor: a (B * Ho * Wo, 9 * C) VIEW OF
+    THE COLUMN BUFFER of this (device, stream) -- the buffer conv3x3_im2col and conv3x3_dcol write
+    as well; it holds the result until the next of these calls on the stream (the training node's
+    weight gradient, train_fuse.conv3x3_strided, recomputes col with it instead of saving it)"""
+    _require_gpu(x, 'x')
+    B, Cc, H, W = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise TypeError('im2col3x3 needs a channels-last fp32 activation')
+    stride = int(stride)
+    if Cc % 4 or not 1 <= stride <= 4:
+        raise ValueError('im2col3x3: C a multiple of 4, stride 1..4')
+    rows = B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+    nbytes = rows * 9 * Cc * 4
+    col = _col_buffer(x.device, nbytes)
+    _lib.check(_lib.lib().ia_im2col3x3_nhwc(_ptr(x), _ptr(col), B, H, W, Cc, stride, IA_F32, _stream()),
+               'ia_im2col3x3_nhwc')
+    return col[:nbytes].view(torch.float32).view(rows, 9 * Cc)
+
+
+def conv3x3_dcol(g, w_kn):
+    """dcol = g . w_kn^T: the gradient of the column matrix of conv3x3_im2col from the channels-last
+    fp32 output gradient g (B, Cout, Ho, Wo) and the forward's (9 * C, Cout) weight, read through the
+    library's transpose flag (ia_linear_bias_act_wt; no transposed copy) -> a (B * Ho * Wo, 9 * C)
+    VIEW OF THE COLUMN BUFFER (see im2col3x3): consume it (col2im3x3) before the next call that
+    writes the buffer -- on one stream that is program order"""
+    _require_gpu(g, 'g')
+    B, n, Ho, Wo = g.shape
+    if g.dtype != torch.float32 or not g.is_contiguous(memory_format=torch.channels_last):
+        raise TypeError('conv3x3_dcol needs a channels-last fp32 gradient')
+    if w_kn.dim() != 2 or w_kn.shape[1] != n or w_kn.shape[0] % 9 or not w_kn.is_contiguous() \
+            or w_kn.dtype != torch.float32:
+        raise ValueError('weight must be the contiguous fp32 (9 * C, Cout) matrix of the forward')
+    rows, k9 = B * Ho * Wo, int(w_kn.shape[0])
+    nbytes = rows * k9 * 4
+    col = _col_buffer(g.device, nbytes)
+    _ensure_gemm_table()
+    ws = _workspace(g.device, _LT_WS_BYTES)
+    _lib.check(_lib.lib().ia_linear_bias_act_wt(_ptr(g), _ptr(w_kn), None, None, _ptr(col), rows, n, k9, 0,
+                                                _ptr(ws), _LT_WS_BYTES, _stream()),
+               'ia_linear_bias_act_wt (dcol)')
+    return col[:nbytes].view(torch.float32).view(rows, k9)
+
+
+def col2im3x3(dcol, B, H, W, C, stride):
+    """the adjoint of im2col (csrc/im2col.hip, k_col2im3x3): dcol (B * Ho * Wo, 9 * C) fp32 -> the
+    channels-last fp32 (B, C, H, W) input gradient of a 3x3 / pad 1 / stride `stride` convolution;
+    every input pixel gathers its taps in ascending tap order (no atomics: the same bits in every
+    run) and every element is written, zeros where no tap reads the pixel"""
+    _require_gpu(dcol, 'dcol')
+    B, H, W, C, stride = int(B), int(H), int(W), int(C), int(stride)
+    if not 1 <= stride <= 4 or min(B, H, W, C) < 1 or C % 4:
+        raise ValueError('col2im3x3: stride 1..4, positive sizes, C a multiple of 4')
+    rows = B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+    if dcol.dtype != torch.float32 or not dcol.is_contiguous() or dcol.numel() != rows * 9 * C:
+        raise ValueError('col2im3x3: dcol must be a contiguous fp32 (B * Ho * Wo, 9 * C) matrix')
+    dx = torch.empty((B, C, H, W), dtype=torch.float32, device=dcol.device,
+                     memory_format=torch.channels_last)
+    _lib.check(_lib.lib().ia_col2im3x3_nhwc(_ptr(dcol), _ptr(dx), B, H, W, C, stride, IA_F32, _stream()),
+               'ia_col2im3x3_nhwc')
+    return dx
+
+
 def conv3x3_weight_kn(weight, scale=None):
     """(Cout, Cin, 3, 3) convolution weight (x per-output-channel scale) -> the (9 * Cin, Cout) GEMM
     operand of conv3x3_im2col: row (dy * 3 + dx) * Cin + c"""

@@ -21,7 +21,11 @@ channels-last activation:
                    alone would occupy a handful of compute units)
     3x3, stride 1  winograd_train.wino_conv_levels: F(4x4,3x3) forward, input gradient and
                    Winograd-domain weight gradient
-    3x3, stride 2  (three per network) torch's convolution on the folded weight
+    3x3, stride 2  (three per network, and the FPN's P6 / P7) torch's convolution on the folded
+                   weight; with `ResNet.train_strided` / `FPN.train_strided` set (opt-in)
+                   `Conv3x3Strided`: im2col + GEMM forward (ops.conv3x3_im2col, the inference
+                   kernels), dx = col2im(g . w_kn^T), dw = g^T . col with col recomputed --
+                   fixed reduction orders, the same bits in every run
 
 The fold `w * s`, `beta - mean * s` is one more autograd node on the parameters (`FoldBN`, one
 kernel forward, one backward), which carries d(w*s), db back to w, gamma and beta; nothing of
@@ -166,6 +170,63 @@ def conv1x1_fork(x, w_nk, bias=None, relu=False):
     return Conv1x1Fork.apply(x, w_nk, bias, relu)
 
 
+# ------------------------------------------------------------------ 3x3 convolution with a stride
+class Conv3x3Strided(torch.autograd.Function):
+    """relu?( conv3x3(x, weight, stride, pad 1) + bias ) on a channels-last fp32 activation as
+    im2col + one library GEMM (ops.conv3x3_im2col, csrc/im2col.hip), and its adjoints.  Every sum
+    has a fixed order -- the library convolution's kernels for these shapes add split reductions
+    with atomics, forward and backward, and give other bits in every run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, relu):
+        x = _cl(x)
+        w_kn = ops.conv3x3_weight_kn(weight)                         # (9 Cin, Cout), row tap * Cin + c
+        y = ops.conv3x3_im2col(x, w_kn, None if bias is None else bias.detach().contiguous(),
+                               stride=stride, relu=relu)
+        ctx.stride, ctx.relu, ctx.xshape = int(stride), bool(relu), tuple(x.shape)
+        # x is kept for the weight gradient alone (col is built from it again in backward)
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, w_kn, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_kn, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g, db = WT.relu_bwd_bias_grad(dy, y if ctx.relu else None, bias_grad=need_b)
+        B, cin, H, W = ctx.xshape
+        dx = dw = None
+        # dcol and the recomputed col are both views of the ONE column buffer of this stream
+        # (ops._col_buffer): GEMM -> col2im -> im2col -> weight product are launched in this order
+        # on this stream, so col2im has read dcol before im2col overwrites it, and the product has
+        # read col before anything else can write the buffer
+        if need_x:
+            dcol = ops.conv3x3_dcol(g, w_kn)                         # (P, Cout) . (Cout, 9 Cin)
+            dx = ops.col2im3x3(dcol, B, H, W, cin, ctx.stride)
+        if need_w:
+            # col is not kept from the forward (310 MB for stage 2 at batch 4) but built again;
+            # g^T . col, the P-long reduction cut into slices added in a fixed order
+            # (weight_grad_1x1) -> (Cout, 9 Cin) = the weight in (Cout, 3, 3, Cin) order
+            col = ops.im2col3x3(x, ctx.stride)
+            dw = weight_grad_1x1(_rows(g), col).view(g.shape[1], 3, 3, cin).permute(0, 3, 1, 2)
+        return dx, dw, db, None, None
+
+
+def strided_conv_ok(conv):
+    """the module side of conv3x3_strided: a 3x3 / pad 1 / dilation 1 / groups 1 nn.Conv2d with one
+    stride of 2..4 in both directions and channel counts the 16-byte kernels take"""
+    return (type(conv) is torch.nn.Conv2d and tuple(conv.kernel_size) == (3, 3)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and conv.stride[0] == conv.stride[1] and 2 <= conv.stride[0] <= 4
+            and conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0
+            and conv.padding_mode == 'zeros' and conv.weight.dtype == torch.float32)
+
+
+def conv3x3_strided(x, weight, bias=None, stride=2, relu=False):
+    """x (B, Cin, H, W) fp32 CUDA, Cin % 4 == 0; weight (Cout, Cin, 3, 3) (a parameter or FoldBN's
+    output) -> channels-last (B, Cout, Ho, Wo)"""
+    return Conv3x3Strided.apply(x, weight, bias, stride, relu)
+
+
 # ------------------------------------------------------------------ eval-mode BatchNorm fold
 def _inv_std(bn):
     key = (bn.running_var.data_ptr(), bn.running_var._version)
@@ -302,6 +363,8 @@ def bottleneck_forward(m, x):
         out = conv1x1(x, _nk(w1), b1, None, True)
     if m.conv2.stride[0] == 1:
         out = WT.wino_conv_levels([out], w2, b2, relu=True)[0]
+    elif getattr(m, '_ia_train_strided', False) and strided_conv_ok(m.conv2):
+        out = conv3x3_strided(out, w2, b2, m.conv2.stride[0], True)
     else:
         out = F.relu(F.conv2d(out, w2, b2, m.conv2.stride, m.conv2.padding))
     if m.downsample is None:
@@ -359,8 +422,17 @@ def fpn_forward(m, inputs):
                 outs.append(F.max_pool2d(outs[-1], 1, stride=2))
         else:
             first = inputs[m.backbone_end_level - 1] if m.extra_convs_on_inputs else outs[-1]
-            outs.append(m.fpn_convs[n](first))
+            outs.append(_extra_conv(m, m.fpn_convs[n], first))
             for i in range(n + 1, m.num_outs):
                 src = F.relu(outs[-1]) if m.relu_before_extra_convs else outs[-1]
-                outs.append(m.fpn_convs[i](src))
+                outs.append(_extra_conv(m, m.fpn_convs[i], src))
     return tuple(outs)
+
+
+def _extra_conv(m, fc, x):
+    """an extra level of the FPN (P6 / P7: ConvModule, 3x3 with a stride): with `m.train_strided`
+    the strided node where it covers the convolution, else the module as before"""
+    if m.train_strided and not fc.with_norm and fc.activate_last and strided_conv_ok(fc.conv) \
+            and _act_ok(x):
+        return conv3x3_strided(x, fc.conv.weight, fc.conv.bias, fc.conv.stride[0], fc.with_activatation)
+    return fc(x)

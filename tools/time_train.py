@@ -10,7 +10,10 @@
     TRAIN_BF16=1        the heads' bf16 route (bbox_head.train_bf16 = True: bf16 activations on the MFMA
                         convolutions -- and, in the FCOS towers, the bf16 GroupNorm node --, fp32 master
                         weights; iouaware/conv3x3_bf16_train.py)
-The result line names the head route that ran (bf16 / winograd / module).
+    TRAIN_STRIDED=1     the stride-2 3x3 convolutions (conv2 of the first block of stages 2-4, P6 / P7) on
+                        the im2col / col2im node (backbone.train_strided = neck.train_strided = True;
+                        needs FUSE=1); 0: the framework's convolution
+The result line names the head route that ran (bf16 / winograd / module) and the TRAIN_STRIDED setting.
     ITERS=n             timed iterations (default 5)"""
 import sys, os, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -43,6 +46,9 @@ if os.environ.get('TRAIN_WINOGRAD') is not None:
     model.bbox_head.train_winograd = bool(int(os.environ['TRAIN_WINOGRAD']))
 if os.environ.get('TRAIN_BF16') is not None:
     model.bbox_head.train_bf16 = bool(int(os.environ['TRAIN_BF16']))
+STRIDED = bool(int(os.environ.get('TRAIN_STRIDED', '0')))
+if STRIDED:
+    model.backbone.train_strided = model.neck.train_strided = True      # the backbone's is read by fuse_inference below
 print('model %s  head %s  train_winograd %s  train_bf16 %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd,
                                                                getattr(model.bbox_head, 'train_bf16', False)))
 # which head route runs: count the calls of the route functions
@@ -74,7 +80,7 @@ del ROUTE[:]
 for _ in range(n): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); dt = (time.time() - t) / n
 route = '+'.join(sorted(set(ROUTE))) if ROUTE else 'module'
-print('B=%d  head route %s  %.1f ms/iter  %.1f img/s  loss %s  mem %.1f GB' % (B, route, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
+print('B=%d  head route %s  train_strided %d  %.1f ms/iter  %.1f img/s  loss %s  mem %.2f GB' % (B, route, STRIDED, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
 if os.environ.get('TRAIN_ONLY'):
     sys.exit(0)
 # loss part alone (targets + 3 losses fwd + bwd) on fixed head outputs
