@@ -34,6 +34,12 @@
 // entries: the box kernels carry the kind as a template parameter (IOU), and their IOU = false
 // instances are smooth-L1 alone -- no anchor, no decode, no IoU map read, no IoU gradient written;
 // the losses_iou entries of the result are 0.  Focal kernels, packed targets and slots are shared.
+//
+// The box kernels of the two layouts (k_box_ml: NCHW planes, k_box_nhwc: pixel rows with a stride)
+// keep block location, the `live` test, loads and stores; the per-anchor math is box_elem, the
+// fp64 block reduction box_block_reduce.  Host: ml_loss_args / nhwc_loss_args validate and fill
+// for forward and backward alike (backward = forward + gradient pointers); carve() alone knows
+// the workspace layout; a forward call is refused before its first enqueue.
 #include <string.h>
 #include "ia_loss.hpp"
 #include "ia_headloss.hpp"
@@ -134,7 +140,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
     const int cend = (cbeg + a.lv.cchunk[r.l] < C) ? (cbeg + a.lv.cchunk[r.l]) : C;
     const T *cls = static_cast<const T *>(a.cls[r.l]) + ((size_t)r.b * A + r.an) * C * HW;
     float *grad = BWD ? a.grad[r.l] + ((size_t)r.b * A + r.an) * C * HW : nullptr;
-    const float gs = BWD ? upstream(a.gin, a.res, a.lv.L, 0, r.l, a.loss_weight) : 1.0f;
+    const float gs = BWD ? upstream(a.tail.gin, a.tail.res, a.lv.L, 0, r.l, a.tail.loss_weight) : 1.0f;
     const bool vec = (HW & 3) == 0;
     // labels / weights of this anchor's 256 positions from the anchor-major packed copy
     // (k_pack_targets): two coalesced 16-byte loads per lane instead of eight 64-line gathers
@@ -159,8 +165,8 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
     for (int j = 0; j < 4; ++j) {
         const float w0 = (pos[j] < HW) ? wn[j] : 0.0f;                      // padding lanes weigh 0
         if (pos[j] >= HW) lab[j] = 0;
-        wn[j] = (a.alpha_neg * w0) * gs;
-        wp[j] = (a.alpha_pos * w0) * gs;
+        wn[j] = (a.tail.alpha_neg * w0) * gs;
+        wp[j] = (a.tail.alpha_pos * w0) * gs;
     }
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     constexpr int K = 8;                                   // class planes in flight per wavefront
@@ -266,7 +272,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
         }
         if (!BWD) total += __builtin_fmaf(acc[j] * kLn2, wn[j], fix);
     }
-    if (!BWD && __builtin_expect(a.big_logits != 0, 0)) {
+    if (!BWD && __builtin_expect(a.tail.big_logits != 0, 0)) {
         // exact tail for logits > kXMax (requested by the host when it cannot exclude them):
         // add (x - kXMax) per such negative element
         for (int c = cbeg; c < cend; ++c)
@@ -279,7 +285,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
     }
     if (!BWD) {
         const double d = wave_sum((double)total);
-        if (lane == 0) atomicAdd(a.sums + (size_t)(0 * a.lv.L + r.l) * IA_LOSS_SLOTS +
+        if (lane == 0) atomicAdd(a.tail.sums + (size_t)(0 * a.lv.L + r.l) * IA_LOSS_SLOTS +
                                      (blockIdx.x & kSlotMask), d);
     }
 }
@@ -327,10 +333,10 @@ __global__ void __launch_bounds__(256) k_pack_targets(PackArgs a)
 }
 
 // ------------------------------------------------------------------ smooth-L1 + IoU BCE, all levels
-struct BoxMLArgs {
-    HLLevels lv;
-    BaseAnchors ba;
-    const void *reg[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
+// what the box kernels of both layouts share behind their own addressing: targets, gradient maps
+// and scalars (the base anchors stay in front of the head-output pointers, where they have always
+// been in both argument blocks)
+struct BoxTail {
     const float *bt[IA_MAX_LEVELS], *bw[IA_MAX_LEVELS];
     float *g_reg[IA_MAX_LEVELS], *g_iou[IA_MAX_LEVELS];
     double *sums;
@@ -340,10 +346,79 @@ struct BoxMLArgs {
     int32_t attach;
 };
 
+struct BoxMLArgs {
+    HLLevels lv;
+    BaseAnchors ba;
+    const void *reg[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
+    BoxTail tail;
+};
+
+// One live anchor (an, position p of level l) of either layout.  Forward: its two loss terms;
+// backward: d(bbox_pred) = smooth-L1 part + the part through the attached IoU target, and
+// d(iou_pred).  xl is the IoU logit (not looked at without IOU).
+template <bool BWD, bool IOU>
+__device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba, int L, int l, int an, int p, int W, int stride,
+                                         const float (&wv)[4], const float (&dp)[4],
+                                         const float (&dt)[4], float xl, double &acc_l1,
+                                         double &acc_iou, float (&g_box)[4], float &g_iou)
+{
+    IouElem q;
+    if constexpr (IOU) {
+        const int y = p / W, x = p - y * W;
+        const float sx = (float)(x * stride), sy = (float)(y * stride);
+        const float *b4 = ba.v[l][an];
+        const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
+        q = iou_target_elem(anc, dp, dt, c.means, c.stds);
+    }
+    if (!BWD) {
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], c.beta) * wv[k];
+        acc_l1 = (double)s;
+        if constexpr (IOU) acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
+    } else {
+        const float gs1 = upstream(c.gin, c.res, L, 1, l, c.lw_bbox);
+        float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (IOU) {
+            const float gs2 = upstream(c.gin, c.res, L, 2, l, c.lw_iou);
+            g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
+            if (c.attach) iou_bce_box_grad(q, xl, wv[0], gs2, c.stds, gv);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float g = (smooth_l1_der(dp[k] - dt[k], c.beta) * wv[k]) * gs1;
+            // with the IoU term the add is unconditional (attach off: gv = 0, and x + 0.0f turns
+            // -0.0f into +0.0f); the plain RetinaHead kind (smooth-L1 alone) has no add
+            g_box[k] = IOU ? g + gv[k] : g;
+        }
+    }
+}
+
+// the workgroup's two fp64 sums -> slots of (loss, level); positives are rare: most workgroups
+// have nothing to add
+template <bool IOU>
+__device__ __forceinline__ void box_block_reduce(double *sums, int L, int l, double acc_l1, double acc_iou)
+{
+    __shared__ double red[2][4];
+    const bool any = __syncthreads_or((acc_l1 != 0.0) | (acc_iou != 0.0));
+    if (any) {
+        const double s1 = wave_sum(acc_l1), s2 = wave_sum(acc_iou);
+        const int w = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
+        __syncthreads();
+        if (threadIdx.x < (IOU ? 2 : 1)) {
+            const double s = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) +
+                             red[threadIdx.x][3];
+            if (s != 0.0)
+                atomicAdd(sums + (size_t)((1 + threadIdx.x) * L + l) * IA_LOSS_SLOTS +
+                              (blockIdx.x & kSlotMask), s);
+        }
+    }
+}
+
 template <typename T, bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
 {
-    __shared__ double red[2][4];
     const BlockRef r = locate_block<false>(a.lv, blockIdx.x);
     const int A = a.lv.A, W = a.lv.W[r.l], HW = a.lv.H[r.l] * W;
     const int p = r.p0 + threadIdx.x;
@@ -352,7 +427,7 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
         const size_t ba = (size_t)r.b * A + r.an;
         const size_t e = ba * HW + p;
         const size_t n = ((size_t)r.b * HW + p) * A + r.an;
-        const float4 wt4 = reinterpret_cast<const float4 *>(a.bw[r.l])[n];
+        const float4 wt4 = reinterpret_cast<const float4 *>(a.tail.bw[r.l])[n];
         const float wv[4] = {wt4.x, wt4.y, wt4.z, wt4.w};
         const bool live = (wv[0] != 0.0f) | (wv[1] != 0.0f) | (wv[2] != 0.0f) | (wv[3] != 0.0f);
         float g_box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g_iou = 0.0f;
@@ -360,69 +435,22 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
             const T *bp = static_cast<const T *>(a.reg[r.l]) + ba * 4 * HW + p;
             const float dp[4] = {load_f32<T>(bp), load_f32<T>(bp + (size_t)HW),
                                  load_f32<T>(bp + (size_t)2 * HW), load_f32<T>(bp + (size_t)3 * HW)};
-            const float4 tq = reinterpret_cast<const float4 *>(a.bt[r.l])[n];
+            const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[r.l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
-            if constexpr (IOU) {
-                const int y = p / W, x = p - y * W;
-                const float sx = (float)(x * a.lv.stride[r.l]), sy = (float)(y * a.lv.stride[r.l]);
-                const float *b4 = a.ba.v[r.l][r.an];
-                const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
-                const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
-                const float xl = load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e);
-                if (!BWD) {
-                    float s = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
-                    acc_l1 = (double)s;
-                    acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
-                } else {
-                    const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, r.l, a.lw_bbox);
-                    const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, r.l, a.lw_iou);
-                    g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
-                    float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
-                }
-            } else if (!BWD) {            // plain RetinaHead: smooth-L1 alone
-                float s = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
-                acc_l1 = (double)s;
-            } else {
-                const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, r.l, a.lw_bbox);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1;
-            }
+            const float xl = IOU ? load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e) : 0.0f;
+            box_elem<BWD, IOU>(a.tail, a.ba, a.lv.L, r.l, r.an, p, W, a.lv.stride[r.l], wv, dp, dt, xl,
+                               acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
-            float *go = a.g_reg[r.l] + ba * 4 * HW + p;
+            float *go = a.tail.g_reg[r.l] + ba * 4 * HW + p;
             go[0] = g_box[0];
             go[(size_t)HW] = g_box[1];
             go[(size_t)2 * HW] = g_box[2];
             go[(size_t)3 * HW] = g_box[3];
-            if constexpr (IOU) a.g_iou[r.l][e] = g_iou;
+            if constexpr (IOU) a.tail.g_iou[r.l][e] = g_iou;
         }
     }
-    if (!BWD) {
-        // positives are rare: most workgroups have nothing to add
-        const bool any = __syncthreads_or((acc_l1 != 0.0) | (acc_iou != 0.0));
-        if (any) {
-            const double s1 = wave_sum(acc_l1), s2 = wave_sum(acc_iou);
-            const int w = threadIdx.x >> 6;
-            if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
-            __syncthreads();
-            if (threadIdx.x < (IOU ? 2 : 1)) {
-                const double s = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) +
-                                 red[threadIdx.x][3];
-                if (s != 0.0)
-                    atomicAdd(a.sums + (size_t)((1 + threadIdx.x) * a.lv.L + r.l) * IA_LOSS_SLOTS +
-                                  (blockIdx.x & kSlotMask), s);
-            }
-        }
-    }
+    if (!BWD) box_block_reduce<IOU>(a.tail.sums, a.lv.L, r.l, acc_l1, acc_iou);
 }
 
 // ------------------------------------------------------------------ channels-last head outputs
@@ -448,10 +476,7 @@ struct FocalNhwcArgs {
     const int64_t *labels[IA_MAX_LEVELS];
     const float *lw[IA_MAX_LEVELS];
     float *grad[IA_MAX_LEVELS];
-    double *sums;
-    const float *gin, *res;
-    float alpha_pos, alpha_neg, loss_weight;
-    int32_t big_logits;
+    FocalTail tail;
 };
 
 template <bool BWD>
@@ -473,7 +498,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
     const int64_t pix0 = base0 / AC4;
     const int r0 = (int)(base0 - pix0 * AC4);
     const float inv_ac4 = 1.0f / (float)AC4, inv_c4 = 1.0f / (float)C4;
-    const float gs = BWD ? upstream(a.gin, a.res, a.lv.L, 0, l, a.loss_weight) : 1.0f;
+    const float gs = BWD ? upstream(a.tail.gin, a.tail.res, a.lv.L, 0, l, a.tail.loss_weight) : 1.0f;
     const float *cls = a.cls[l];
     const int64_t ps = a.ps_cls[l], pg = BWD ? a.ps_grad[l] : 0;
     // every load of the thread is issued before the first use (addresses clamped, no predicate):
@@ -511,7 +536,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
     for (int u = 0; u < kFocalU; ++u) {
         const int lab = labv[u];
         const float w0 = on[u] ? lwv[u] : 0.0f;
-        const float wn = (a.alpha_neg * w0) * gs, wp = (a.alpha_pos * w0) * gs;
+        const float wn = (a.tail.alpha_neg * w0) * gs, wp = (a.tail.alpha_pos * w0) * gs;
         const float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
         float t[4], rq[4], lg[4];
 #pragma unroll
@@ -543,7 +568,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
                     else { acc -= neg_val2(g); fix = pos_val(g, __builtin_fminf(x[k], kXMax)) * wp; }
                 }
         }
-        if (!BWD && a.big_logits) {                         // exact tail, on request (wave-uniform)
+        if (!BWD && a.tail.big_logits) {                         // exact tail, on request (wave-uniform)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (x[k] > kXMax && k != jp) fix += (x[k] - kXMax) * wn;
@@ -557,7 +582,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
         __syncthreads();
         if (threadIdx.x == 0)
-            atomicAdd(a.sums + (size_t)(0 * a.lv.L + l) * IA_LOSS_SLOTS + (blockIdx.x & kSlotMask),
+            atomicAdd(a.tail.sums + (size_t)(0 * a.lv.L + l) * IA_LOSS_SLOTS + (blockIdx.x & kSlotMask),
                       (red[0] + red[1]) + (red[2] + red[3]));
     }
 }
@@ -567,20 +592,13 @@ struct BoxNhwcArgs {
     BaseAnchors ba;
     const float *reg[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
     int64_t ps_reg[IA_MAX_LEVELS], ps_iou[IA_MAX_LEVELS], pg_reg[IA_MAX_LEVELS], pg_iou[IA_MAX_LEVELS];
-    const float *bt[IA_MAX_LEVELS], *bw[IA_MAX_LEVELS];
-    float *g_reg[IA_MAX_LEVELS], *g_iou[IA_MAX_LEVELS];
-    double *sums;
-    const float *gin, *res;
-    float means[4], stds[4];
-    float beta, lw_bbox, lw_iou;
-    int32_t attach;
+    BoxTail tail;
     int32_t g_pad[IA_MAX_LEVELS];         // bwd: zero-gradient channels behind d(iou) in the same pixel row
 };
 
 template <bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
 {
-    __shared__ double red[2][4];
     int o = 0;
     while ((int)blockIdx.x >= a.lv.bblk_off[o + 1]) ++o;
     const int l = a.lv.L - 1 - o;
@@ -592,82 +610,36 @@ __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
         const int64_t pix = n / A;
         const int an = (int)(n - pix * A);
         const int p = (int)(pix % HW);
-        const float4 wt4 = reinterpret_cast<const float4 *>(a.bw[l])[n];
+        const float4 wt4 = reinterpret_cast<const float4 *>(a.tail.bw[l])[n];
         const float wv[4] = {wt4.x, wt4.y, wt4.z, wt4.w};
         const bool live = (wv[0] != 0.0f) | (wv[1] != 0.0f) | (wv[2] != 0.0f) | (wv[3] != 0.0f);
         float g_box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g_iou = 0.0f;
         if (live) {
             const float4 d4 = *reinterpret_cast<const float4 *>(a.reg[l] + pix * a.ps_reg[l] + 4 * an);
             const float dp[4] = {d4.x, d4.y, d4.z, d4.w};
-            const float4 tq = reinterpret_cast<const float4 *>(a.bt[l])[n];
+            const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
-            if constexpr (IOU) {
-                const int y = p / W, x = p - y * W;
-                const float sx = (float)(x * a.lv.stride[l]), sy = (float)(y * a.lv.stride[l]);
-                const float *b4 = a.ba.v[l][an];
-                const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
-                const IouElem q = iou_target_elem(anc, dp, dt, a.means, a.stds);
-                const float xl = a.iou[l][pix * a.ps_iou[l] + an];
-                if (!BWD) {
-                    float s = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
-                    acc_l1 = (double)s;
-                    acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
-                } else {
-                    const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, l, a.lw_bbox);
-                    const float gs2 = upstream(a.gin, a.res, a.lv.L, 2, l, a.lw_iou);
-                    g_iou = ((sigmoidf_(xl) - q.t) * wv[0]) * gs2;
-                    float gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (a.attach) iou_bce_box_grad(q, xl, wv[0], gs2, a.stds, gv);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1 + gv[k];
-                }
-            } else if (!BWD) {            // plain RetinaHead: smooth-L1 alone
-                float s = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], a.beta) * wv[k];
-                acc_l1 = (double)s;
-            } else {
-                const float gs1 = upstream(a.gin, a.res, a.lv.L, 1, l, a.lw_bbox);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    g_box[k] = (smooth_l1_der(dp[k] - dt[k], a.beta) * wv[k]) * gs1;
-            }
+            const float xl = IOU ? a.iou[l][pix * a.ps_iou[l] + an] : 0.0f;
+            box_elem<BWD, IOU>(a.tail, a.ba, a.lv.L, l, an, p, W, a.lv.stride[l], wv, dp, dt, xl,
+                               acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
-            *reinterpret_cast<float4 *>(a.g_reg[l] + pix * a.pg_reg[l] + 4 * an) =
+            *reinterpret_cast<float4 *>(a.tail.g_reg[l] + pix * a.pg_reg[l] + 4 * an) =
                 make_float4(g_box[0], g_box[1], g_box[2], g_box[3]);
             if constexpr (IOU) {
-                a.g_iou[l][pix * a.pg_iou[l] + an] = g_iou;
+                a.tail.g_iou[l][pix * a.pg_iou[l] + an] = g_iou;
                 // d(reg) | d(iou) as slices of one wider tensor: its alignment channels behind the IoU
                 // slice get their zero gradient here (the last anchor's thread), not from a fill per level
                 if (an == A - 1)
-                    for (int k = 0; k < a.g_pad[l]; ++k) a.g_iou[l][pix * a.pg_iou[l] + A + k] = 0.0f;
+                    for (int k = 0; k < a.g_pad[l]; ++k) a.tail.g_iou[l][pix * a.pg_iou[l] + A + k] = 0.0f;
             } else {
                 // no IoU slice: the row is [reg 4A | padding], zeroed behind the reg slice
                 if (an == A - 1)
-                    for (int k = 0; k < a.g_pad[l]; ++k) a.g_reg[l][pix * a.pg_reg[l] + 4 * A + k] = 0.0f;
+                    for (int k = 0; k < a.g_pad[l]; ++k) a.tail.g_reg[l][pix * a.pg_reg[l] + 4 * A + k] = 0.0f;
             }
         }
     }
-    if (!BWD) {
-        const bool any = __syncthreads_or((acc_l1 != 0.0) | (acc_iou != 0.0));
-        if (any) {
-            const double s1 = wave_sum(acc_l1), s2 = wave_sum(acc_iou);
-            const int w = threadIdx.x >> 6;
-            if ((threadIdx.x & 63) == 0) { red[0][w] = s1; red[1][w] = s2; }
-            __syncthreads();
-            if (threadIdx.x < (IOU ? 2 : 1)) {
-                const double s = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) +
-                                 red[threadIdx.x][3];
-                if (s != 0.0)
-                    atomicAdd(a.sums + (size_t)((1 + threadIdx.x) * a.lv.L + l) * IA_LOSS_SLOTS +
-                                  (blockIdx.x & kSlotMask), s);
-            }
-        }
-    }
+    if (!BWD) box_block_reduce<IOU>(a.tail.sums, a.lv.L, l, acc_l1, acc_iou);
 }
 
 // ------------------------------------------------------------------ slots -> losses
@@ -708,6 +680,7 @@ __global__ void __launch_bounds__(64) k_headloss_finalize(FinArgs a)
     if (i == 0) a.res[kNumLoss * a.L + kNumLoss] = avg;
 }
 
+// ------------------------------------------------------------------ host: checks and arguments
 // the two kinds the node covers: sigmoid focal loss with (IoU-aware head) or without (plain
 // RetinaHead) the IoU term; the softmax kinds have no fused loss
 static bool sigmoid_kind(const ia_head_geom *g)
@@ -722,12 +695,13 @@ static bool iou_ptrs_ok(const ia_level_ptrs *p, int L, bool with_iou)
     return true;
 }
 
-int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
+// the geometry step of both level tables (HLLevels, NhwcLevels): ranges, kind, H / W / stride
+template <class LV>
+static int level_geometry(const ia_head_geom *g, int B, LV &lv)
 {
     if (!g || B < 1) return IA_E_ARG;
     if (g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS) return IA_E_ARG;
     if (g->num_anchors < 1 || g->num_anchors > IA_MAX_ANCHORS || g->num_classes < 1) return IA_E_ARG;
-    if (g->layout != IA_LAYOUT_NCHW) return IA_E_ARG;            // training kernels: NCHW only
     if (!sigmoid_kind(g)) return IA_E_ARG;                       // sigmoid focal loss only
     lv.L = g->num_levels; lv.B = B; lv.A = g->num_anchors; lv.C = g->num_classes;
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
@@ -735,6 +709,14 @@ int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
         if (on && (g->H[l] < 1 || g->W[l] < 1)) return IA_E_ARG;
         lv.H[l] = on ? g->H[l] : 0; lv.W[l] = on ? g->W[l] : 0; lv.stride[l] = on ? g->stride[l] : 0;
     }
+    return 0;
+}
+
+int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
+{
+    const int rc = level_geometry(g, B, lv);
+    if (rc) return rc;
+    if (g->layout != IA_LAYOUT_NCHW) return IA_E_ARG;            // training kernels: NCHW only
     int64_t off = 0, foff = 0, poff = 0;
     lv.blk_off[0] = lv.fblk_off[0] = 0;
     for (int l = 0; l <= IA_MAX_LEVELS; ++l) {
@@ -765,194 +747,14 @@ int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
     return 0;
 }
 
-
-int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s)
-{
-    const unsigned fgrid = (unsigned)fa.lv.fblk_off[fa.lv.L];
-    if (bwd) hipLaunchKernelGGL((k_focal_ml<float, true>), dim3(fgrid), dim3(64), 0, s, fa);
-    else hipLaunchKernelGGL((k_focal_ml<float, false>), dim3(fgrid), dim3(64), 0, s, fa);
-    return hip_status(hipGetLastError());
-}
-
-}  // namespace ia
-
-extern "C" {
-
-size_t ia_head_loss_workspace_bytes(const ia_head_geom *g, int batch)
-{
-    ia::HLLevels lv;
-    if (ia::fill_levels(g, batch, lv)) return 0;
-    // fp64 slots | packed labels (int32) | packed weights (fp32), 256-byte aligned pieces
-    const size_t slots = ((sizeof(double) * ia::kNumLoss * lv.L * IA_LOSS_SLOTS + 255) / 256) * 256;
-    const size_t pk = (((size_t)lv.pack_off[lv.L] * 4 + 255) / 256) * 256;
-    return slots + 2 * pk;
-}
-
-namespace ia {
-static void carve(const HLLevels &lv, void *workspace, double *&sums, int32_t *&lab_am, float *&w_am)
-{
-    const size_t slots = ((sizeof(double) * kNumLoss * lv.L * IA_LOSS_SLOTS + 255) / 256) * 256;
-    const size_t pk = (((size_t)lv.pack_off[lv.L] * 4 + 255) / 256) * 256;
-    char *w = static_cast<char *>(workspace);
-    sums = reinterpret_cast<double *>(w);
-    lab_am = reinterpret_cast<int32_t *>(w + slots);
-    w_am = reinterpret_cast<float *>(w + slots + pk);
-}
-}  // namespace ia
-
-int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
-                     const ia_head_targets *t, const ia_head_loss_cfg *cfg, void *workspace,
-                     size_t workspace_bytes, float *result, void *stream)
-{
-    using namespace ia;
-    if (!p || !t || !cfg || !workspace || !result || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
-    {
-        const size_t need = ia_head_loss_workspace_bytes(g, batch);
-        if (!need) return IA_E_ARG;
-        if (workspace_bytes < need) return IA_E_WORKSPACE;
-    }
-    double *sums;
-    FocalMLArgs fa;
-    int rc = fill_levels(g, batch, fa.lv);
-    if (rc) return rc;
-    if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;      // other gammas: per-level path
-    const int L = fa.lv.L;
-    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
-    if (!iou_ptrs_ok(p, L, with_iou)) return IA_E_ARG;
-    BoxMLArgs ba;
-    ba.lv = fa.lv;
-    memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
-    PackArgs pa;
-    pa.lv = fa.lv;
-    int32_t *lab_am; float *w_am;
-    carve(fa.lv, workspace, sums, lab_am, w_am);
-    pa.lab_am = lab_am; pa.w_am = w_am;
-    fa.lab_am = lab_am; fa.w_am = w_am;
-    pa.tile_off[0] = 0;
-    for (int l = 0; l < IA_MAX_LEVELS; ++l)
-        pa.tile_off[l + 1] = pa.tile_off[l] +
-            (l < L ? batch * ((fa.lv.H[l] * fa.lv.W[l] + 255) / 256) : 0);
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
-        const bool on = l < L;
-        if (on && (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
-                   !t->bbox_targets[l] || !t->bbox_weights[l]))
-            return IA_E_ARG;
-        fa.cls[l] = on ? p->cls[l] : nullptr;
-        pa.labels[l] = on ? t->labels[l] : nullptr;
-        pa.lw[l] = on ? t->label_weights[l] : nullptr;
-        fa.grad[l] = nullptr;
-        ba.reg[l] = on ? p->reg[l] : nullptr; ba.iou[l] = on ? p->iou[l] : nullptr;
-        ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
-        ba.g_reg[l] = ba.g_iou[l] = nullptr;
-    }
-    fa.sums = sums; fa.gin = fa.res = nullptr;
-    fa.big_logits = cfg->exact_large_logits ? 1 : 0;
-    fa.alpha_pos = cfg->alpha;
-    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);   // python: (1 - alpha) in double, then fp32
-    fa.loss_weight = cfg->loss_weight_cls;
-    ba.sums = sums; ba.gin = ba.res = nullptr;
-    for (int k = 0; k < 4; ++k) { ba.means[k] = g->means[k]; ba.stds[k] = g->stds[k]; }
-    ba.beta = cfg->beta; ba.lw_bbox = cfg->loss_weight_bbox; ba.lw_iou = 1.0f;
-    ba.attach = cfg->attach_iou_target ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS, s);
-    if (e != hipSuccess) return (int)e;
-    const unsigned grid = (unsigned)fa.lv.blk_off[L], fgrid = (unsigned)fa.lv.fblk_off[L];
-    hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)pa.tile_off[L]), dim3(256), 0, s, pa);
-    if (dtype == IA_F32) {
-        hipLaunchKernelGGL((k_focal_ml<float, false>), dim3(fgrid), dim3(64), 0, s, fa);
-        if (with_iou) hipLaunchKernelGGL((k_box_ml<float, false, true>), dim3(grid), dim3(256), 0, s, ba);
-        else hipLaunchKernelGGL((k_box_ml<float, false, false>), dim3(grid), dim3(256), 0, s, ba);
-    } else if (dtype == IA_BF16) {
-        hipLaunchKernelGGL((k_focal_ml<uint16_t, false>), dim3(fgrid), dim3(64), 0, s, fa);
-        if (with_iou) hipLaunchKernelGGL((k_box_ml<uint16_t, false, true>), dim3(grid), dim3(256), 0, s, ba);
-        else hipLaunchKernelGGL((k_box_ml<uint16_t, false, false>), dim3(grid), dim3(256), 0, s, ba);
-    } else return IA_E_ARG;
-    FinArgs f;
-    f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
-    if (!f.counts && !f.avg_dev && !(f.avg_host > 0.0f)) return IA_E_ARG;
-    f.lw[0] = cfg->loss_weight_cls; f.lw[1] = cfg->loss_weight_bbox; f.lw[2] = 1.0f;
-    f.L = L; f.B = batch; f.res = result;
-    hipLaunchKernelGGL(k_headloss_finalize, dim3(1), dim3(64), 0, s, f);
-    return hip_status(hipGetLastError());
-}
-
-int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
-                     const ia_head_targets *t, const ia_head_loss_cfg *cfg, const void *workspace,
-                     const float *result, const float *grad_result, const ia_level_ptrs *grads,
-                     void *stream)
-{
-    using namespace ia;
-    if (!p || !t || !cfg || !workspace || !result || !grad_result || !grads) return IA_E_ARG;
-    FocalMLArgs fa;
-    int rc = fill_levels(g, batch, fa.lv);
-    if (rc) return rc;
-    if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
-    const int L = fa.lv.L;
-    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
-    if (!iou_ptrs_ok(p, L, with_iou) || !iou_ptrs_ok(grads, L, with_iou)) return IA_E_ARG;
-    BoxMLArgs ba;
-    ba.lv = fa.lv;
-    memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
-        const bool on = l < L;
-        if (on && (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
-                   !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l]))
-            return IA_E_ARG;
-        fa.cls[l] = on ? p->cls[l] : nullptr;
-        fa.grad[l] = on ? (float *)grads->cls[l] : nullptr;
-        ba.reg[l] = on ? p->reg[l] : nullptr; ba.iou[l] = on ? p->iou[l] : nullptr;
-        ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
-        ba.g_reg[l] = on ? (float *)grads->reg[l] : nullptr;
-        ba.g_iou[l] = on ? (float *)grads->iou[l] : nullptr;
-    }
-    {
-        double *sums_unused; int32_t *lab_am; float *w_am;
-        carve(fa.lv, const_cast<void *>(workspace), sums_unused, lab_am, w_am);
-        fa.lab_am = lab_am; fa.w_am = w_am;               // the forward call's packed targets
-    }
-    fa.sums = nullptr; fa.gin = grad_result; fa.res = result;
-    fa.big_logits = 0;
-    fa.alpha_pos = cfg->alpha;
-    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);
-    fa.loss_weight = cfg->loss_weight_cls;
-    ba.sums = nullptr; ba.gin = grad_result; ba.res = result;
-    for (int k = 0; k < 4; ++k) { ba.means[k] = g->means[k]; ba.stds[k] = g->stds[k]; }
-    ba.beta = cfg->beta; ba.lw_bbox = cfg->loss_weight_bbox; ba.lw_iou = 1.0f;
-    ba.attach = cfg->attach_iou_target ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)fa.lv.blk_off[L], fgrid = (unsigned)fa.lv.fblk_off[L];
-    if (dtype == IA_F32) {
-        hipLaunchKernelGGL((k_focal_ml<float, true>), dim3(fgrid), dim3(64), 0, s, fa);
-        if (with_iou) hipLaunchKernelGGL((k_box_ml<float, true, true>), dim3(grid), dim3(256), 0, s, ba);
-        else hipLaunchKernelGGL((k_box_ml<float, true, false>), dim3(grid), dim3(256), 0, s, ba);
-    } else if (dtype == IA_BF16) {
-        hipLaunchKernelGGL((k_focal_ml<uint16_t, true>), dim3(fgrid), dim3(64), 0, s, fa);
-        if (with_iou) hipLaunchKernelGGL((k_box_ml<uint16_t, true, true>), dim3(grid), dim3(256), 0, s, ba);
-        else hipLaunchKernelGGL((k_box_ml<uint16_t, true, false>), dim3(grid), dim3(256), 0, s, ba);
-    } else return IA_E_ARG;
-    return hip_status(hipGetLastError());
-}
-
-
-namespace ia {
 static int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv)
 {
-    if (!g || B < 1) return IA_E_ARG;
-    if (g->num_levels < 1 || g->num_levels > IA_MAX_LEVELS) return IA_E_ARG;
-    if (g->num_anchors < 1 || g->num_anchors > IA_MAX_ANCHORS || g->num_classes < 4 ||
-        (g->num_classes & 3))
-        return IA_E_ARG;                                  // class quads: C % 4 == 0
-    if (!sigmoid_kind(g)) return IA_E_ARG;                       // sigmoid focal loss only
-    if ((int64_t)g->num_anchors * (g->num_classes / 4) > 8192) return IA_E_ARG;   // float-reciprocal division
-    lv.L = g->num_levels; lv.B = B; lv.A = g->num_anchors; lv.C = g->num_classes;
+    const int rc = level_geometry(g, B, lv);
+    if (rc) return rc;
+    if (lv.C & 3) return IA_E_ARG;                               // class quads: C % 4 == 0
+    if ((int64_t)lv.A * (lv.C / 4) > 8192) return IA_E_ARG;      // float-reciprocal division
     int64_t foff = 0, boff = 0;
     lv.fblk_off[0] = lv.bblk_off[0] = 0;
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
-        const bool on = l < lv.L;
-        if (on && (g->H[l] < 1 || g->W[l] < 1)) return IA_E_ARG;
-        lv.H[l] = on ? g->H[l] : 0; lv.W[l] = on ? g->W[l] : 0; lv.stride[l] = on ? g->stride[l] : 0;
-    }
     for (int o = 0; o < IA_MAX_LEVELS; ++o) {
         if (o < lv.L) {
             const int l = lv.L - 1 - o;
@@ -979,7 +781,253 @@ static int check_strides(const NhwcLevels &lv, const ia_level_pix_strides *st, c
     }
     return 0;
 }
+
+// What the four entries check alike, after the geometry (g is valid).  Backward is forward plus
+// the gradient pointers: grads / grad_result are NULL in a forward call.
+static int check_common(const ia_head_geom *g, const ia_level_ptrs *p, const ia_head_targets *t,
+                        const ia_head_loss_cfg *cfg, const float *result, bool bwd,
+                        const float *grad_result, const ia_level_ptrs *grads, bool &with_iou)
+{
+    if (!p || !t || !cfg || !result || (bwd && (!grad_result || !grads))) return IA_E_ARG;
+    if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;      // other gammas: per-level path
+    const int L = g->num_levels;
+    with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    if (!iou_ptrs_ok(p, L, with_iou) || (bwd && !iou_ptrs_ok(grads, L, with_iou))) return IA_E_ARG;
+    for (int l = 0; l < L; ++l) {
+        if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
+            !t->bbox_targets[l] || !t->bbox_weights[l])
+            return IA_E_ARG;
+        if (bwd && (!grads->cls[l] || !grads->reg[l])) return IA_E_ARG;
+    }
+    return 0;
+}
+// forward: the normaliser comes from the assignment's counts, a device scalar or the host
+static bool normaliser_ok(const ia_head_targets *t)
+{
+    return t->counts || t->avg_factor_dev || t->avg_factor > 0.0f;
+}
+
+FocalTail focal_tail(float alpha, float loss_weight, bool exact_large_logits, double *sums,
+                     const float *gin, const float *res)
+{
+    FocalTail f;
+    f.sums = sums; f.gin = gin; f.res = res;
+    f.alpha_pos = alpha;
+    f.alpha_neg = (float)(1.0 - (double)alpha);   // python: (1 - alpha) in double, then fp32
+    f.loss_weight = loss_weight;
+    f.big_logits = exact_large_logits ? 1 : 0;
+    return f;
+}
+// grads is NULL in a forward call
+static void fill_box_tail(BoxTail &b, BaseAnchors &ba, const ia_head_geom *g, const ia_head_targets *t,
+                          const ia_head_loss_cfg *cfg, const ia_level_ptrs *grads, double *sums,
+                          const float *gin, const float *res)
+{
+    memcpy(ba.v, g->base_anchors, sizeof(ba.v));
+        for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < g->num_levels;
+        b.bt[l] = on ? t->bbox_targets[l] : nullptr; b.bw[l] = on ? t->bbox_weights[l] : nullptr;
+        b.g_reg[l] = (on && grads) ? (float *)grads->reg[l] : nullptr;
+        b.g_iou[l] = (on && grads) ? (float *)grads->iou[l] : nullptr;
+    }
+    b.sums = sums; b.gin = gin; b.res = res;
+    for (int k = 0; k < 4; ++k) { b.means[k] = g->means[k]; b.stds[k] = g->stds[k]; }
+    b.beta = cfg->beta; b.lw_bbox = cfg->loss_weight_bbox; b.lw_iou = 1.0f;
+    b.attach = cfg->attach_iou_target ? 1 : 0;
+}
+
+// the workspace of the NCHW entries: fp64 slots | packed labels (int32) | packed weights (fp32),
+// 256-byte aligned pieces; the channels-last entries use the slots alone
+struct HLWorkspace { double *sums; int32_t *lab_am; float *w_am; size_t bytes; };
+static size_t slot_bytes(int L) { return sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS; }
+static HLWorkspace carve(const HLLevels &lv, const void *workspace)
+{
+    const size_t slots = ((slot_bytes(lv.L) + 255) / 256) * 256;
+    const size_t pk = (((size_t)lv.pack_off[lv.L] * 4 + 255) / 256) * 256;
+    char *w = static_cast<char *>(const_cast<void *>(workspace));
+    HLWorkspace r;
+    r.sums = reinterpret_cast<double *>(w);
+    r.lab_am = reinterpret_cast<int32_t *>(w + slots);
+    r.w_am = reinterpret_cast<float *>(w + slots + pk);
+    r.bytes = slots + 2 * pk;
+    return r;
+}
+
+// NCHW: what forward and backward check alike, and every kernel argument (backward reads the
+// forward call's packed targets from the same workspace)
+static int ml_loss_args(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                        const ia_head_targets *t, const ia_head_loss_cfg *cfg, const void *workspace,
+                        const float *result, bool bwd, const float *grad_result,
+                        const ia_level_ptrs *grads, FocalMLArgs &fa, BoxMLArgs &ba, HLWorkspace &ws,
+                        bool &with_iou)
+{
+    if (!workspace || (dtype != IA_F32 && dtype != IA_BF16)) return IA_E_ARG;
+    int rc = fill_levels(g, batch, fa.lv);
+    if (rc || (rc = check_common(g, p, t, cfg, result, bwd, grad_result, grads, with_iou))) return rc;
+    ws = carve(fa.lv, workspace);
+    ba.lv = fa.lv;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < fa.lv.L;
+        fa.cls[l] = on ? p->cls[l] : nullptr;
+        fa.grad[l] = (on && bwd) ? (float *)grads->cls[l] : nullptr;
+        ba.reg[l] = on ? p->reg[l] : nullptr; ba.iou[l] = on ? p->iou[l] : nullptr;
+    }
+    fa.lab_am = ws.lab_am; fa.w_am = ws.w_am;
+    double *sums = bwd ? nullptr : ws.sums;
+    fa.tail = focal_tail(cfg->alpha, cfg->loss_weight_cls, !bwd && cfg->exact_large_logits, sums, grad_result,
+                         bwd ? result : nullptr);
+    fill_box_tail(ba.tail, ba.ba, g, t, cfg, grads, sums, grad_result, bwd ? result : nullptr);
+    return 0;
+}
+
+// channels-last: the same, plus the pixel strides and the zero-gradient channels of a shared row
+static int nhwc_loss_args(const ia_head_geom *g, const ia_level_ptrs *p,
+                          const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
+                          const ia_head_loss_cfg *cfg, double *sums, const float *result, bool bwd,
+                          const float *grad_result, const ia_level_ptrs *grads,
+                          const ia_level_pix_strides *grad_strides, FocalNhwcArgs &fa,
+                          BoxNhwcArgs &ba, bool &with_iou)
+{
+    if (!strides || (bwd && !grad_strides)) return IA_E_ARG;
+    int rc = fill_levels_nhwc(g, batch, fa.lv);
+    if (rc || (rc = check_common(g, p, t, cfg, result, bwd, grad_result, grads, with_iou))) return rc;
+    if ((rc = check_strides(fa.lv, strides, p, with_iou)) ||
+        (bwd && (rc = check_strides(fa.lv, grad_strides, grads, with_iou))))
+        return rc;
+    ba.lv = fa.lv;
+    fa.tail = focal_tail(cfg->alpha, cfg->loss_weight_cls, !bwd && cfg->exact_large_logits, sums, grad_result,
+                         bwd ? result : nullptr);
+    fill_box_tail(ba.tail, ba.ba, g, t, cfg, grads, sums, grad_result, bwd ? result : nullptr);
+    const int A = fa.lv.A;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < fa.lv.L, gon = on && bwd;
+        fa.cls[l] = on ? (const float *)p->cls[l] : nullptr;
+        fa.ps_cls[l] = on ? strides->cls[l] : 0;
+        fa.grad[l] = gon ? (float *)grads->cls[l] : nullptr;
+        fa.ps_grad[l] = gon ? grad_strides->cls[l] : 0;
+        fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
+        ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
+        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
+        ba.pg_reg[l] = gon ? grad_strides->reg[l] : 0; ba.pg_iou[l] = (gon && with_iou) ? grad_strides->iou[l] : 0;
+        // both gradients in one pixel row that STARTS at reg (the caller says so: cfg->grad_rows_start_at_reg;
+        // a row [X | reg | iou | pad] looks the same from here, and zero-filling behind iou would run into the
+        // next pixel's X): the channels left up to the row's end get their zero gradient here
+        ba.g_pad[l] = 0;
+        if (gon && cfg->grad_rows_start_at_reg && with_iou) {
+            if (ba.tail.g_iou[l] != ba.tail.g_reg[l] + 4 * A || ba.pg_reg[l] != ba.pg_iou[l] ||
+                ba.pg_reg[l] < 5 * A || ba.pg_reg[l] - 5 * A > 64)
+                return IA_E_ARG;
+            ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 5 * A);
+        } else if (gon && cfg->grad_rows_start_at_reg) {
+            // without the IoU slice the row is [reg 4A | padding]
+            if (ba.pg_reg[l] - 4 * A > 64) return IA_E_ARG;                 // (>= 4A: check_strides)
+            ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 4 * A);
+        }
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------ host: launches
+// the instantiation switches: [dtype == IA_BF16][bwd] and [..][bwd][with_iou]
+static int launch_focal_ml(int dtype, bool bwd, const FocalMLArgs &fa, hipStream_t s)
+{
+    static void (*const k[2][2])(FocalMLArgs) = {{k_focal_ml<float, false>, k_focal_ml<float, true>},
+                                                 {k_focal_ml<uint16_t, false>, k_focal_ml<uint16_t, true>}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd], dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(64), 0, s, fa);
+    return hip_status(hipGetLastError());
+}
+int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s) { return launch_focal_ml(IA_F32, bwd, fa, s); }
+static int launch_box_ml(int dtype, bool bwd, bool with_iou, const BoxMLArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][2][2])(BoxMLArgs) = {
+        {{k_box_ml<float, false, false>, k_box_ml<float, false, true>},
+         {k_box_ml<float, true, false>, k_box_ml<float, true, true>}},
+        {{k_box_ml<uint16_t, false, false>, k_box_ml<uint16_t, false, true>},
+         {k_box_ml<uint16_t, true, false>, k_box_ml<uint16_t, true, true>}}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd][with_iou], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
+}
+static int launch_box_nhwc(bool bwd, bool with_iou, const BoxNhwcArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][2])(BoxNhwcArgs) = {{k_box_nhwc<false, false>, k_box_nhwc<false, true>},
+                                                 {k_box_nhwc<true, false>, k_box_nhwc<true, true>}};
+    hipLaunchKernelGGL(k[bwd][with_iou], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
+}
+static int launch_finalize(const double *sums, const ia_head_targets *t, const ia_head_loss_cfg *cfg,
+                           int L, int batch, float *result, hipStream_t s)
+{
+    FinArgs f;
+    f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
+    f.lw[0] = cfg->loss_weight_cls; f.lw[1] = cfg->loss_weight_bbox; f.lw[2] = 1.0f;
+    f.L = L; f.B = batch; f.res = result;
+    hipLaunchKernelGGL(k_headloss_finalize, dim3(1), dim3(64), 0, s, f);
+    return hip_status(hipGetLastError());
+}
+
 }  // namespace ia
+
+extern "C" {
+
+size_t ia_head_loss_workspace_bytes(const ia_head_geom *g, int batch)
+{
+    ia::HLLevels lv;
+    if (ia::fill_levels(g, batch, lv)) return 0;
+    return ia::carve(lv, nullptr).bytes;
+}
+
+int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                     const ia_head_targets *t, const ia_head_loss_cfg *cfg, void *workspace,
+                     size_t workspace_bytes, float *result, void *stream)
+{
+    using namespace ia;
+    if ((uintptr_t)workspace & 255u) return IA_E_ARG;
+    FocalMLArgs fa;
+    BoxMLArgs ba;
+    HLWorkspace ws;
+    bool with_iou;
+    int rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, false, nullptr, nullptr, fa, ba,
+                          ws, with_iou);
+    if (rc) return rc;
+    if (workspace_bytes < ws.bytes) return IA_E_WORKSPACE;
+    if (!normaliser_ok(t)) return IA_E_ARG;              // before the first enqueue
+    const int L = fa.lv.L;
+    PackArgs pa;
+    pa.lv = fa.lv;
+    pa.lab_am = ws.lab_am; pa.w_am = ws.w_am;
+    pa.tile_off[0] = 0;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < L;
+        pa.labels[l] = on ? t->labels[l] : nullptr;
+        pa.lw[l] = on ? t->label_weights[l] : nullptr;
+        pa.tile_off[l + 1] = pa.tile_off[l] + (on ? batch * ((fa.lv.H[l] * fa.lv.W[l] + 255) / 256) : 0);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.sums, 0, slot_bytes(L), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)pa.tile_off[L]), dim3(256), 0, s, pa);
+    if ((rc = launch_focal_ml(dtype, false, fa, s)) || (rc = launch_box_ml(dtype, false, with_iou, ba, s)))
+        return rc;
+    return launch_finalize(ws.sums, t, cfg, L, batch, result, s);
+}
+
+int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                     const ia_head_targets *t, const ia_head_loss_cfg *cfg, const void *workspace,
+                     const float *result, const float *grad_result, const ia_level_ptrs *grads,
+                     void *stream)
+{
+    using namespace ia;
+    FocalMLArgs fa;
+    BoxMLArgs ba;
+    HLWorkspace ws;
+    bool with_iou;
+    int rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, true, grad_result, grads, fa, ba,
+                          ws, with_iou);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_focal_ml(dtype, true, fa, s))) return rc;
+    return launch_box_ml(dtype, true, with_iou, ba, s);
+}
 
 int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
@@ -987,59 +1035,23 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           float *result, void *stream)
 {
     using namespace ia;
-    if (!p || !strides || !t || !cfg || !workspace || !result || ((uintptr_t)workspace & 255u))
-        return IA_E_ARG;
+    if (!workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
+    double *sums = static_cast<double *>(workspace);
     FocalNhwcArgs fa;
-    int rc = fill_levels_nhwc(g, batch, fa.lv);
+    BoxNhwcArgs ba;
+    bool with_iou;
+    int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, sums, result, false, nullptr, nullptr, nullptr,
+                            fa, ba, with_iou);
     if (rc) return rc;
     const int L = fa.lv.L;
-    if (workspace_bytes < sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS) return IA_E_WORKSPACE;
-    if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
-    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
-    if (!iou_ptrs_ok(p, L, with_iou)) return IA_E_ARG;
-    for (int l = 0; l < L; ++l)
-        if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
-            !t->bbox_targets[l] || !t->bbox_weights[l])
-            return IA_E_ARG;
-    if ((rc = check_strides(fa.lv, strides, p, with_iou))) return rc;
-    BoxNhwcArgs ba;
-    ba.lv = fa.lv;
-    memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
-    double *sums = static_cast<double *>(workspace);
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
-        const bool on = l < L;
-        fa.cls[l] = on ? (const float *)p->cls[l] : nullptr;
-        fa.ps_cls[l] = on ? strides->cls[l] : 0; fa.ps_grad[l] = 0; fa.grad[l] = nullptr;
-        fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
-        ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
-        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
-        ba.pg_reg[l] = ba.pg_iou[l] = 0;
-        ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
-        ba.g_reg[l] = ba.g_iou[l] = nullptr;
-    }
-    fa.sums = sums; fa.gin = fa.res = nullptr;
-    fa.big_logits = cfg->exact_large_logits ? 1 : 0;
-    fa.alpha_pos = cfg->alpha;
-    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);
-    fa.loss_weight = cfg->loss_weight_cls;
-    ba.sums = sums; ba.gin = ba.res = nullptr;
-    for (int k = 0; k < 4; ++k) { ba.means[k] = g->means[k]; ba.stds[k] = g->stds[k]; }
-    ba.beta = cfg->beta; ba.lw_bbox = cfg->loss_weight_bbox; ba.lw_iou = 1.0f;
-    ba.attach = cfg->attach_iou_target ? 1 : 0;
+    if (workspace_bytes < slot_bytes(L)) return IA_E_WORKSPACE;
+    if (!normaliser_ok(t)) return IA_E_ARG;              // before the first enqueue
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS, s);
+    hipError_t e = hipMemsetAsync(sums, 0, slot_bytes(L), s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((k_focal_nhwc<false>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) ba.g_pad[l] = 0;
-    if (with_iou) hipLaunchKernelGGL((k_box_nhwc<false, true>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
-    else hipLaunchKernelGGL((k_box_nhwc<false, false>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
-    FinArgs f;
-    f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
-    if (!f.counts && !f.avg_dev && !(f.avg_host > 0.0f)) return IA_E_ARG;
-    f.lw[0] = cfg->loss_weight_cls; f.lw[1] = cfg->loss_weight_bbox; f.lw[2] = 1.0f;
-    f.L = L; f.B = batch; f.res = result;
-    hipLaunchKernelGGL(k_headloss_finalize, dim3(1), dim3(64), 0, s, f);
-    return hip_status(hipGetLastError());
+    if ((rc = launch_box_nhwc(false, with_iou, ba, s))) return rc;
+    return launch_finalize(sums, t, cfg, L, batch, result, s);
 }
 
 int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
@@ -1049,67 +1061,15 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           void *stream)
 {
     using namespace ia;
-    if (!p || !strides || !t || !cfg || !result || !grad_result || !grads || !grad_strides)
-        return IA_E_ARG;
     FocalNhwcArgs fa;
-    int rc = fill_levels_nhwc(g, batch, fa.lv);
-    if (rc) return rc;
-    const int L = fa.lv.L;
-    if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;
-    const bool with_iou = g->cls_activation == IA_CLS_SIGMOID;
-    if (!iou_ptrs_ok(p, L, with_iou) || !iou_ptrs_ok(grads, L, with_iou)) return IA_E_ARG;
-    for (int l = 0; l < L; ++l)
-        if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
-            !t->bbox_targets[l] || !t->bbox_weights[l] || !grads->cls[l] || !grads->reg[l])
-            return IA_E_ARG;
-    if ((rc = check_strides(fa.lv, strides, p, with_iou)) ||
-        (rc = check_strides(fa.lv, grad_strides, grads, with_iou)))
-        return rc;
     BoxNhwcArgs ba;
-    ba.lv = fa.lv;
-    memcpy(ba.ba.v, g->base_anchors, sizeof(ba.ba.v));
-    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
-        const bool on = l < L;
-        fa.cls[l] = on ? (const float *)p->cls[l] : nullptr;
-        fa.ps_cls[l] = on ? strides->cls[l] : 0;
-        fa.grad[l] = on ? (float *)grads->cls[l] : nullptr;
-        fa.ps_grad[l] = on ? grad_strides->cls[l] : 0;
-        fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
-        ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
-        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
-        ba.pg_reg[l] = on ? grad_strides->reg[l] : 0; ba.pg_iou[l] = (on && with_iou) ? grad_strides->iou[l] : 0;
-        ba.bt[l] = on ? t->bbox_targets[l] : nullptr; ba.bw[l] = on ? t->bbox_weights[l] : nullptr;
-        ba.g_reg[l] = on ? (float *)grads->reg[l] : nullptr;
-        ba.g_iou[l] = on ? (float *)grads->iou[l] : nullptr;
-        // both gradients in one pixel row that STARTS at reg (the caller says so: cfg->grad_rows_start_at_reg;
-        // a row [X | reg | iou | pad] looks the same from here, and zero-filling behind iou would run into the
-        // next pixel's X): the channels left up to the row's end get their zero gradient here
-        ba.g_pad[l] = 0;
-        if (on && cfg->grad_rows_start_at_reg && with_iou) {
-            if (ba.g_iou[l] != ba.g_reg[l] + 4 * fa.lv.A || ba.pg_reg[l] != ba.pg_iou[l] ||
-                ba.pg_reg[l] < 5 * fa.lv.A || ba.pg_reg[l] - 5 * fa.lv.A > 64)
-                return IA_E_ARG;
-            ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 5 * fa.lv.A);
-        } else if (on && cfg->grad_rows_start_at_reg) {
-            // without the IoU slice the row is [reg 4A | padding]
-            if (ba.pg_reg[l] - 4 * fa.lv.A > 64) return IA_E_ARG;          // (>= 4A: check_strides)
-            ba.g_pad[l] = (int32_t)(ba.pg_reg[l] - 4 * fa.lv.A);
-        }
-    }
-    fa.sums = nullptr; fa.gin = grad_result; fa.res = result;
-    fa.big_logits = 0;
-    fa.alpha_pos = cfg->alpha;
-    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);
-    fa.loss_weight = cfg->loss_weight_cls;
-    ba.sums = nullptr; ba.gin = grad_result; ba.res = result;
-    for (int k = 0; k < 4; ++k) { ba.means[k] = g->means[k]; ba.stds[k] = g->stds[k]; }
-    ba.beta = cfg->beta; ba.lw_bbox = cfg->loss_weight_bbox; ba.lw_iou = 1.0f;
-    ba.attach = cfg->attach_iou_target ? 1 : 0;
+    bool with_iou;
+    int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, nullptr, result, true, grad_result, grads,
+                            grad_strides, fa, ba, with_iou);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((k_focal_nhwc<true>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
-    if (with_iou) hipLaunchKernelGGL((k_box_nhwc<true, true>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
-    else hipLaunchKernelGGL((k_box_nhwc<true, false>), dim3((unsigned)fa.lv.bblk_off[L]), dim3(256), 0, s, ba);
-    return hip_status(hipGetLastError());
+    hipLaunchKernelGGL((k_focal_nhwc<true>), dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(256), 0, s, fa);
+    return launch_box_nhwc(true, with_iou, ba, s);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // What the all-levels head-loss kernels of headloss.hip share with the point-head loss
-// (pointloss.hip): the level / launch-order table, the focal kernel's arguments and its launcher.
+// (pointloss.hip): the level / launch-order table, the focal kernel's arguments with their scalar
+// tail (FocalTail, filled by focal_tail() for every caller) and the focal launcher.
 // The kernels themselves stay in headloss.hip (one translation unit owns their device code);
 // pointloss.hip runs the focal kernel through launch_focal_ml_f32 with A = 1.
 #pragma once
@@ -19,18 +20,27 @@ struct HLLevels {
     int32_t pack_off[IA_MAX_LEVELS + 1];  // prefix of B*A*HW: element offset of a level in the packed targets
 };
 
-struct FocalMLArgs {
-    HLLevels lv;
-    const void *cls[IA_MAX_LEVELS];
-    const int32_t *lab_am;                // packed targets: anchor-major labels / weights,
-    const float *w_am;                    // level l at pack_off[l], then (B, A, HW)
-    float *grad[IA_MAX_LEVELS];
+// the scalar tail of every focal kernel's arguments (k_focal_ml, k_focal_nhwc)
+struct FocalTail {
     double *sums;                         // fwd: [3][L][IA_LOSS_SLOTS]
     const float *gin, *res;               // bwd
     float alpha_pos, alpha_neg, loss_weight;
     int32_t big_logits;                   // evaluate the exact tail for logits > kXMax (fwd)
 };
 
+struct FocalMLArgs {
+    HLLevels lv;
+    const void *cls[IA_MAX_LEVELS];
+    const int32_t *lab_am;                // packed targets: anchor-major labels / weights,
+    const float *w_am;                    // level l at pack_off[l], then (B, A, HW)
+    float *grad[IA_MAX_LEVELS];
+    FocalTail tail;
+};
+
+// forward: sums and the exact_large_logits switch, gin = res = NULL; backward: sums = NULL;
+// headloss.hip
+FocalTail focal_tail(float alpha, float loss_weight, bool exact_large_logits, double *sums,
+                     const float *gin, const float *res);
 // geometry -> table (IA_E_ARG for what the kernels do not cover); headloss.hip
 int fill_levels(const ia_head_geom *g, int B, HLLevels &lv);
 // k_focal_ml<float, bwd> over fa.lv.fblk_off[L] wavefronts; headloss.hip

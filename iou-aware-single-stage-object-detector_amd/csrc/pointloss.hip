@@ -365,11 +365,7 @@ static int point_loss_args(const ia_point_head_geom *g, const ia_point_level_ptr
         ba.g_reg[l] = ba.g_ctr[l] = ba.g_iou[l] = nullptr;
     }
     fa.lab_am = ws.lab32; fa.w_am = ws.w32;
-    fa.sums = nullptr; fa.gin = fa.res = nullptr;
-    fa.big_logits = 0;
-    fa.alpha_pos = cfg->alpha;
-    fa.alpha_neg = (float)(1.0 - (double)cfg->alpha);   // python: (1 - alpha) in double, then fp32
-    fa.loss_weight = 1.0f;
+    fa.tail = focal_tail(cfg->alpha, 1.0f, false, nullptr, nullptr, nullptr);
     ba.lab32 = ws.lab32;
     ba.sums = nullptr; ba.res = ba.gin = nullptr; ba.fgin = nullptr;
     ba.attach = cfg->attach_iou_target ? 1 : 0;
@@ -443,8 +439,8 @@ int ia_point_head_loss_fwd(const ia_point_head_geom *g, const ia_point_level_ptr
     if (rc) return rc;
     if (workspace_bytes < ws.bytes) return IA_E_WORKSPACE;
     const int L = fa.lv.L;
-    fa.sums = ws.sums;
-    fa.big_logits = cfg->exact_large_logits ? 1 : 0;
+    fa.tail.sums = ws.sums;
+    fa.tail.big_logits = cfg->exact_large_logits ? 1 : 0;
     ba.sums = ws.sums + (size_t)L * IA_LOSS_SLOTS;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(ws.sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s);
@@ -490,7 +486,7 @@ int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptr
         ba.g_ctr[l] = (float *)grads->ctr[l];
         ba.g_iou[l] = (float *)grads->iou[l];
     }
-    fa.gin = ws.fgin; fa.res = ws.fres;
+    fa.tail.gin = ws.fgin; fa.tail.res = ws.fres;
     ba.res = result; ba.gin = grad_result; ba.fgin = ws.fgin;
     hipStream_t s = (hipStream_t)stream;
     const unsigned grid = (unsigned)fa.lv.blk_off[L];

@@ -332,6 +332,177 @@ def test_head_loss_entries_check_the_iou_pointers_and_the_kind():
                 assert (out[2 * L:3 * L] == 0.0).all() and out[3 * L + 2] == 0.0
 
 
+class _Abi:
+    """the set-up of the test above for the C-ABI tests below: one level set, B = 1, five live
+    anchors on level 0, valid device buffers throughout; here the head outputs are channels-last
+    with random box deltas and IoU logits, and the upstream gradients differ per entry"""
+
+    def __init__(self):
+        from iouaware import _lib, ops
+        self._lib, self.ops, self.lib = _lib, ops, _lib.lib()
+        self.sizes = sizes = synth.level_shapes(64, 96)
+        self.B, self.A, self.Cn, self.L = 1, synth.A, synth.C, len(sizes)
+        B, A, Cn, L = self.B, self.A, self.Cn, self.L
+        base = G.product_base_anchors()
+        self.geoms = {ib: ops.HeadGeometry(sizes, synth.STRIDES, base, Cn, softmax=False, iou_branch=ib)
+                      for ib in (False, True)}
+        gen = torch.Generator(device='cuda').manual_seed(5)
+        rnd = lambda ch, sc: [torch.randn(B, h, w, ch, device='cuda', generator=gen) * sc   # noqa: E731
+                              for h, w in sizes]                   # (B, H, W, ch): pixel rows
+        self.maps = (rnd(A * Cn, 1.0), rnd(A * 4, 0.2), rnd(A, 1.0))
+        self.g_cls = self.rows(A * Cn, 0.0)
+        n = lambda h, w: h * w * A                                 # noqa: E731
+        self.t = ([torch.zeros(B, n(h, w), dtype=torch.int64, device='cuda') for h, w in sizes],
+                  [torch.ones(B, n(h, w), device='cuda') for h, w in sizes],
+                  [torch.zeros(B, n(h, w), 4, device='cuda') for h, w in sizes],
+                  [torch.zeros(B, n(h, w), 4, device='cuda') for h, w in sizes])
+        self.t[3][0][0, :5] = 1.0                                  # five live anchors on level 0
+        self.t[2][0][0, :5] = 0.3
+        self.ht = _lib.HeadTargets()
+        for l in range(L):
+            self.ht.labels[l], self.ht.label_weights[l] = self.t[0][l].data_ptr(), self.t[1][l].data_ptr()
+            self.ht.bbox_targets[l], self.ht.bbox_weights[l] = self.t[2][l].data_ptr(), self.t[3][l].data_ptr()
+        self.ht.avg_factor = 1.0
+        self.res = torch.zeros(3 * L + 4, device='cuda')
+        self.gin = torch.arange(1, 3 * L + 4, device='cuda', dtype=torch.float32) * 0.25
+        self.nbytes = self.lib.ia_head_loss_workspace_bytes(self.geoms[True].ref(), B)
+        self.ws = torch.zeros(self.nbytes, dtype=torch.uint8, device='cuda')
+
+    def rows(self, width, fill):
+        """per level one buffer of pixel rows of `width` floats"""
+        return [torch.full((self.B, h, w, width), fill, device='cuda') for h, w in self.sizes]
+
+    def _ptrs(self, cls, reg, iou):
+        """lists of (pointer, pixel stride) per level; iou = None: no IoU maps"""
+        p, st = self._lib.LevelPtrs(), self._lib.LevelPixStrides()
+        for l in range(self.L):
+            (p.cls[l], st.cls[l]), (p.reg[l], st.reg[l]) = cls[l], reg[l]
+            if iou is not None:
+                p.iou[l], st.iou[l] = iou[l]
+        return p, st
+
+    def _inputs(self, with_iou):
+        at = lambda ts: [(t.data_ptr(), t.shape[-1]) for t in ts]   # noqa: E731
+        return self._ptrs(at(self.maps[0]), at(self.maps[1]), at(self.maps[2]) if with_iou else None)
+
+    def _cfg(self, flag=0):
+        return self._lib.HeadLossCfg(2.0, 0.25, 1.0, 0.11, 1.0, 1, 0, flag)
+
+    def fwd_nhwc(self, with_iou):
+        p, st = self._inputs(with_iou)
+        hc = self._cfg()
+        return self.lib.ia_head_loss_fwd_nhwc(self.geoms[with_iou].ref(), C.byref(p), C.byref(st), self.B,
+                                              C.byref(self.ht), C.byref(hc), self.ops._ptr(self.ws),
+                                              self.nbytes, self.ops._ptr(self.res), self.ops._stream())
+
+    def fwd(self, with_iou):
+        """the NCHW entry on the same values"""
+        nchw = [[t.permute(0, 3, 1, 2).contiguous() for t in ts] for ts in self.maps]
+        p = self._lib.LevelPtrs()
+        for l in range(self.L):
+            p.cls[l], p.reg[l] = nchw[0][l].data_ptr(), nchw[1][l].data_ptr()
+            p.iou[l] = nchw[2][l].data_ptr() if with_iou else None
+        hc = self._cfg()
+        return self.lib.ia_head_loss_fwd(self.geoms[with_iou].ref(), C.byref(p), self._lib.IA_F32, self.B,
+                                         C.byref(self.ht), C.byref(hc), self.ops._ptr(self.ws),
+                                         self.nbytes, self.ops._ptr(self.res), self.ops._stream())
+
+    def bwd_nhwc(self, flag, reg, iou):
+        """reg / iou: the gradient maps as lists of (pointer, pixel stride); iou = None: no-IoU kind"""
+        with_iou = iou is not None
+        p, st = self._inputs(with_iou)
+        gp, gst = self._ptrs([(t.data_ptr(), t.shape[-1]) for t in self.g_cls], reg, iou)
+        hc = self._cfg(flag)
+        return self.lib.ia_head_loss_bwd_nhwc(self.geoms[with_iou].ref(), C.byref(p), C.byref(st), self.B,
+                                              C.byref(self.ht), C.byref(hc), self.ops._ptr(self.res),
+                                              self.ops._ptr(self.gin), C.byref(gp), C.byref(gst),
+                                              self.ops._stream())
+
+
+SENTINEL = 7.25
+
+
+def _same_bits(x, y):
+    return torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize('with_iou', [True, False])
+def test_bwd_nhwc_grad_rows_start_at_reg_contradictions_and_padding(with_iou):
+    """cfg->grad_rows_start_at_reg set: a gradient row that contradicts it is IA_E_ARG (checked
+    before memory is touched) -- iou not at reg + 4A, unequal strides, more than 64 channels
+    behind reg | iou (behind reg for the no-IoU kind); the matching row returns 0, its padding
+    channels read back exactly 0.0f and its reg | iou channels carry the bits of the call with
+    separate gradient tensors.  Rows: 5A + 3 floats with the IoU branch; without it 4A + 4, the
+    narrowest padded row the entry takes -- 4A + 3 floats is no multiple of 16 bytes, which the
+    entry refuses for every reg stride (include/iouaware.h: strides 16-byte aligned)."""
+    s = _Abi()
+    A = s.A
+    used = 5 * A if with_iou else 4 * A
+    assert s.fwd_nhwc(with_iou) == 0
+
+    def call(width, iou_off=4 * A, iou_stride_plus=0):
+        rows = s.rows(width, SENTINEL)
+        reg = [(t.data_ptr(), width) for t in rows]
+        iou = [(t.data_ptr() + 4 * iou_off, width + iou_stride_plus) for t in rows] if with_iou else None
+        return s.bwd_nhwc(1, reg, iou), rows
+
+    if with_iou:
+        assert call(used + 3, iou_off=4 * A + 1)[0] == IA_E_ARG       # grads.iou != grads.reg + 4A
+        assert call(used + 3, iou_stride_plus=4)[0] == IA_E_ARG       # strides differ
+        assert call(used + 67)[0] == IA_E_ARG                         # 67 channels behind reg | iou
+        width = used + 3
+    else:
+        assert call(used + 68)[0] == IA_E_ARG                         # 68 channels behind reg
+        assert call(used + 3)[0] == IA_E_ARG                          # 39 floats: not 16-byte rows
+        width = used + 4
+    rc, rows = call(width)
+    assert rc == 0
+    g_reg, g_iou = s.rows(4 * A, SENTINEL), s.rows(A, SENTINEL)       # the call without the flag
+    assert s.bwd_nhwc(0, [(t.data_ptr(), 4 * A) for t in g_reg],
+                      [(t.data_ptr(), A) for t in g_iou] if with_iou else None) == 0
+    torch.cuda.synchronize()
+    assert float(g_reg[0].abs().max()) > 0
+    for l in range(s.L):
+        assert _same_bits(rows[l][..., used:], torch.zeros_like(rows[l][..., used:])), l
+        assert _same_bits(rows[l][..., :4 * A], g_reg[l]), l
+        if with_iou:
+            assert _same_bits(rows[l][..., 4 * A:used], g_iou[l]), l
+
+
+def test_bwd_nhwc_without_the_flag_writes_the_reg_and_iou_slices_alone():
+    """cfg->grad_rows_start_at_reg clear, gradient rows [X (4) | reg | iou | pad (3)] filled with a
+    sentinel: after the call X and pad of every pixel still hold it, and reg | iou carry the bits
+    of the call with separate gradient tensors"""
+    s = _Abi()
+    A = s.A
+    assert s.fwd_nhwc(True) == 0
+    g_reg, g_iou = s.rows(4 * A, SENTINEL), s.rows(A, SENTINEL)
+    assert s.bwd_nhwc(0, [(t.data_ptr(), 4 * A) for t in g_reg], [(t.data_ptr(), A) for t in g_iou]) == 0
+    width = 4 + 5 * A + 3
+    rows = s.rows(width, SENTINEL)
+    assert s.bwd_nhwc(0, [(t.data_ptr() + 4 * 4, width) for t in rows],
+                      [(t.data_ptr() + 4 * (4 + 4 * A), width) for t in rows]) == 0
+    torch.cuda.synchronize()
+    assert float(g_reg[0].abs().max()) > 0 and float(g_iou[0].abs().max()) > 0
+    for l in range(s.L):
+        r = rows[l]
+        assert bool((r[..., :4] == SENTINEL).all()) and bool((r[..., 4 + 5 * A:] == SENTINEL).all()), l
+        assert _same_bits(r[..., 4:4 + 4 * A], g_reg[l]) and _same_bits(r[..., 4 + 4 * A:4 + 5 * A], g_iou[l]), l
+
+
+@pytest.mark.parametrize('entry', ['fwd', 'fwd_nhwc'])
+def test_forward_entries_refuse_a_missing_normaliser_before_any_launch(entry):
+    """counts = NULL, avg_factor_dev = NULL, avg_factor = 0: IA_E_ARG, and nothing was enqueued --
+    workspace and result still hold the bytes they were filled with"""
+    s = _Abi()
+    s.ht.avg_factor = 0.0
+    s.ws.fill_(0xA5)
+    s.res.view(torch.uint8).fill_(0xA5)
+    assert getattr(s, entry)(True) == IA_E_ARG
+    torch.cuda.synchronize()
+    assert bool((s.ws == 0xA5).all()) and bool((s.res.view(torch.uint8) == 0xA5).all())
+
+
 # ------------------------------------------------------------------ 12: Winograd training head
 def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp(min=1e-30))
