@@ -1102,6 +1102,44 @@ int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptr
                            void *workspace, const float *result, const float *grad_result,
                            const ia_point_level_ptrs *grads, void *stream);
 
+/* ------------------------------------------------------------------ FCOS training: loss on channels-last rows
+ * The same loss on the head outputs as the HIP tower routes leave them: fp32 or bf16 (dtype IA_F32 /
+ * IA_BF16, one for all maps and gradients) pixel rows.  Element (b, p, c) of a map sits at
+ * (b * H_l W_l + p) * stride + c, stride in ELEMENTS per map and level; maps may be channel slices of one
+ * wider tensor (ctr == cls + C in the same row).  cls and reg pointers and their byte strides are 16-byte
+ * (fp32) / 8-byte (bf16) aligned, C % 4 == 0; anything else is IA_E_ARG.  iou: all set or all NULL.
+ * g->layout is not consulted.  t->packed is not read (the labels are read as they are).
+ * reg_scale (device, L floats) or NULL.  Non-NULL: the reg map holds the RAW fcos_reg output x and the
+ * kernels form d_k = exp(reg_scale[l] * x_k) in fp32 (the library's exp); the backward returns
+ * dL/dx_k = g_k * reg_scale[l] * d_k in the reg gradient and grad_scale[l] = sum_{b,p,k} g_k d_k x_k
+ * (fp64 partial sums, one fp32 rounding; exactly 0 for a level without positives).  NULL: reg holds the
+ * distances and grad_scale must be NULL (one without the other: IA_E_ARG).
+ * bf16: inputs widened (exact), the fp32 arithmetic of the fp32 kernels, gradients rounded to nearest
+ * even once; result, grad_result, reg_scale, grad_scale are fp32.
+ * workspace (256-byte aligned, ia_point_head_loss_nhwc_workspace_bytes; 0: unsupported geometry / batch):
+ * written by the forward call, read and written by the backward call -- keep it between the two.
+ * grad_rows_packed: the caller states that each level's gradient rows are [cls C | ctr | pad] and
+ * [reg 4 | iou? | pad] (grads->ctr == grads->cls + C, grads->iou == grads->reg + 4, equal strides within a
+ * row; pointers that contradict it: IA_E_ARG): the backward then also writes +0 into every remaining
+ * channel of both rows.  Without it only the map slices are written.
+ * Every argument error is returned before anything is enqueued.                                    */
+typedef struct ia_point_pix_strides {
+    int64_t cls[IA_MAX_LEVELS], reg[IA_MAX_LEVELS], ctr[IA_MAX_LEVELS], iou[IA_MAX_LEVELS];
+} ia_point_pix_strides;
+size_t ia_point_head_loss_nhwc_workspace_bytes(const ia_point_head_geom *g, int batch);
+int ia_point_head_loss_fwd_nhwc(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
+                                const ia_point_pix_strides *strides, int dtype, int batch,
+                                const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                                const float *reg_scale, void *workspace, size_t workspace_bytes,
+                                float *result, void *stream);
+int ia_point_head_loss_bwd_nhwc(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
+                                const ia_point_pix_strides *strides, int dtype, int batch,
+                                const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                                const float *reg_scale, void *workspace, size_t workspace_bytes,
+                                const float *result, const float *grad_result,
+                                const ia_point_level_ptrs *grads, const ia_point_pix_strides *grad_strides,
+                                int grad_rows_packed, float *grad_scale, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

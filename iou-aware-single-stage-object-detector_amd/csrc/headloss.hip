@@ -459,27 +459,12 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
 // (cls_score.permute(0, 2, 3, 1).reshape(-1, C), iou_aware_retina_head.py:236-240) -- the targets
 // (anchor-major n = (b, p, a)) index it directly, no packed copy, and every load / store is a
 // 16-byte piece of a contiguous run.  reg / iou may be channel slices of one wider tensor
-// (pix_stride > A*4 / A).  fp32 only.
-struct NhwcLevels {
-    int32_t L, B, A, C;
-    int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
-    int32_t fblk_off[IA_MAX_LEVELS + 1];      // focal: blocks of kFocalChunks float4 chunks, launch order
-    int32_t bblk_off[IA_MAX_LEVELS + 1];      // box: blocks of 256 anchors, launch order
-};
-constexpr int kFocalU = 4;                    // float4 chunks per thread
-constexpr int kFocalChunks = 256 * kFocalU;   // per block
-
-struct FocalNhwcArgs {
-    NhwcLevels lv;
-    const float *cls[IA_MAX_LEVELS];
-    int64_t ps_cls[IA_MAX_LEVELS], ps_grad[IA_MAX_LEVELS];   // pixel strides (elements)
-    const int64_t *labels[IA_MAX_LEVELS];
-    const float *lw[IA_MAX_LEVELS];
-    float *grad[IA_MAX_LEVELS];
-    FocalTail tail;
-};
-
-template <bool BWD>
+// (pix_stride > A*4 / A).  The anchor heads' entries are fp32 only; the point heads (pointloss.hip) run
+// the focal kernel on fp32 or bf16 rows with unit label weights.
+// T: storage type of logits and gradient (float, or uint16_t = bf16 widened on load, the fp32 gradient
+// rounded to nearest even once on store); UNITW: every label weight is 1, a.lw is not read (the point
+// heads, A = 1)
+template <bool BWD, typename T, bool UNITW>
 __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
 {
     __shared__ double red[4];
@@ -499,7 +484,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
     const int r0 = (int)(base0 - pix0 * AC4);
     const float inv_ac4 = 1.0f / (float)AC4, inv_c4 = 1.0f / (float)C4;
     const float gs = BWD ? upstream(a.tail.gin, a.tail.res, a.lv.L, 0, l, a.tail.loss_weight) : 1.0f;
-    const float *cls = a.cls[l];
+    const T *cls = static_cast<const T *>(a.cls[l]);
     const int64_t ps = a.ps_cls[l], pg = BWD ? a.ps_grad[l] : 0;
     // every load of the thread is issued before the first use (addresses clamped, no predicate):
     // a load next to its use, or under `on ? load : 0`, compiles to load + s_waitcnt vmcnt(0)
@@ -511,7 +496,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
     int64_t goff[kFocalU];
     bool on[kFocalU];
     const int32_t *labels = reinterpret_cast<const int32_t *>(a.labels[l]);   // low words: labels < 2^31
-    const float *lwp = a.lw[l];
+    const float *lwp = UNITW ? nullptr : a.lw[l];
 #pragma unroll
     for (int u = 0; u < kFocalU; ++u) {
         int j = (int)threadIdx.x + 256 * u;
@@ -524,11 +509,13 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
         const int an = (int)(((float)r + 0.5f) * inv_c4);
         const int64_t anchor = pix * A + an;
         cq[u] = r - an * C4;
-        typedef float F4 __attribute__((ext_vector_type(4)));
-        const F4 q = __builtin_nontemporal_load(reinterpret_cast<const F4 *>(cls + pix * ps + 4 * r));
-        v[u] = make_float4(q.x, q.y, q.z, q.w);
+        using V = typename MLPack<T>::V;
+        const V q = __builtin_nontemporal_load(reinterpret_cast<const V *>(cls + pix * ps + 4 * r));
+        float x4[4];
+        MLPack<T>::unpack(q, x4);
+        v[u] = make_float4(x4[0], x4[1], x4[2], x4[3]);
         labv[u] = labels[2 * anchor];
-        lwv[u] = lwp[anchor];
+        lwv[u] = UNITW ? 1.0f : lwp[anchor];
         goff[u] = pix * pg + 4 * r;
     }
     double total = 0.0;
@@ -574,7 +561,12 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
                 if (x[k] > kXMax && k != jp) fix += (x[k] - kXMax) * wn;
         }
         if (BWD) {
-            if (on[u]) *reinterpret_cast<float4 *>(a.grad[l] + goff[u]) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            if constexpr (sizeof(T) == 4) {
+                if (on[u]) *reinterpret_cast<float4 *>(static_cast<float *>(a.grad[l]) + goff[u]) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            } else {
+                if (on[u]) *reinterpret_cast<uint2 *>(static_cast<uint16_t *>(a.grad[l]) + goff[u]) =
+                    make_uint2(f32_to_bf16(o4[0]) | (f32_to_bf16(o4[1]) << 16), f32_to_bf16(o4[2]) | (f32_to_bf16(o4[3]) << 16));
+            }
         } else total += (double)__builtin_fmaf(acc * kLn2, wn, fix);
     }
     if (!BWD) {
@@ -747,7 +739,7 @@ int fill_levels(const ia_head_geom *g, int B, HLLevels &lv)
     return 0;
 }
 
-static int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv)
+int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv)
 {
     const int rc = level_geometry(g, B, lv);
     if (rc) return rc;
@@ -901,9 +893,9 @@ static int nhwc_loss_args(const ia_head_geom *g, const ia_level_ptrs *p,
     const int A = fa.lv.A;
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
         const bool on = l < fa.lv.L, gon = on && bwd;
-        fa.cls[l] = on ? (const float *)p->cls[l] : nullptr;
+        fa.cls[l] = on ? p->cls[l] : nullptr;
         fa.ps_cls[l] = on ? strides->cls[l] : 0;
-        fa.grad[l] = gon ? (float *)grads->cls[l] : nullptr;
+        fa.grad[l] = gon ? const_cast<void *>(grads->cls[l]) : nullptr;
         fa.ps_grad[l] = gon ? grad_strides->cls[l] : 0;
         fa.labels[l] = on ? t->labels[l] : nullptr; fa.lw[l] = on ? t->label_weights[l] : nullptr;
         ba.reg[l] = on ? (const float *)p->reg[l] : nullptr; ba.iou[l] = on ? (const float *)p->iou[l] : nullptr;
@@ -952,6 +944,14 @@ static int launch_box_nhwc(bool bwd, bool with_iou, const BoxNhwcArgs &ba, hipSt
     static void (*const k[2][2])(BoxNhwcArgs) = {{k_box_nhwc<false, false>, k_box_nhwc<false, true>},
                                                  {k_box_nhwc<true, false>, k_box_nhwc<true, true>}};
     hipLaunchKernelGGL(k[bwd][with_iou], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
+}
+int launch_focal_nhwc_unit(const FocalNhwcArgs &fa, int dtype, bool bwd, hipStream_t s)
+{
+    static void (*const k[2][2])(FocalNhwcArgs) = {
+        {k_focal_nhwc<false, float, true>, k_focal_nhwc<true, float, true>},
+        {k_focal_nhwc<false, uint16_t, true>, k_focal_nhwc<true, uint16_t, true>}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd], dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(256), 0, s, fa);
     return hip_status(hipGetLastError());
 }
 static int launch_finalize(const double *sums, const ia_head_targets *t, const ia_head_loss_cfg *cfg,
@@ -1049,7 +1049,7 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(sums, 0, slot_bytes(L), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_focal_nhwc<false>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
+    hipLaunchKernelGGL((k_focal_nhwc<false, float, false>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
     if ((rc = launch_box_nhwc(false, with_iou, ba, s))) return rc;
     return launch_finalize(sums, t, cfg, L, batch, result, s);
 }
@@ -1068,7 +1068,7 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                             grad_strides, fa, ba, with_iou);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((k_focal_nhwc<true>), dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(256), 0, s, fa);
+    hipLaunchKernelGGL((k_focal_nhwc<true, float, false>), dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(256), 0, s, fa);
     return launch_box_nhwc(true, with_iou, ba, s);
 }
 

@@ -2,7 +2,7 @@
 // (pointloss.hip): the level / launch-order table, the focal kernel's arguments with their scalar
 // tail (FocalTail, filled by focal_tail() for every caller) and the focal launcher.
 // The kernels themselves stay in headloss.hip (one translation unit owns their device code);
-// pointloss.hip runs the focal kernel through launch_focal_ml_f32 with A = 1.
+// pointloss.hip runs the focal kernels through launch_focal_ml_f32 / launch_focal_nhwc_unit with A = 1.
 #pragma once
 #include "ia_internal.hpp"
 
@@ -37,6 +37,26 @@ struct FocalMLArgs {
     FocalTail tail;
 };
 
+// the channels-last kernels' level table (k_focal_nhwc, k_box_nhwc) and the focal kernel's arguments
+struct NhwcLevels {
+    int32_t L, B, A, C;
+    int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
+    int32_t fblk_off[IA_MAX_LEVELS + 1];      // focal: blocks of kFocalChunks float4 chunks, launch order
+    int32_t bblk_off[IA_MAX_LEVELS + 1];      // box: blocks of 256 anchors, launch order
+};
+constexpr int kFocalU = 4;                    // float4 chunks per thread
+constexpr int kFocalChunks = 256 * kFocalU;   // per block
+
+struct FocalNhwcArgs {
+    NhwcLevels lv;
+    const void *cls[IA_MAX_LEVELS];           // fp32 or bf16 (the kernel's storage type)
+    int64_t ps_cls[IA_MAX_LEVELS], ps_grad[IA_MAX_LEVELS];   // pixel strides (elements)
+    const int64_t *labels[IA_MAX_LEVELS];
+    const float *lw[IA_MAX_LEVELS];           // not read by the unit-weight instances
+    void *grad[IA_MAX_LEVELS];
+    FocalTail tail;
+};
+
 // forward: sums and the exact_large_logits switch, gin = res = NULL; backward: sums = NULL;
 // headloss.hip
 FocalTail focal_tail(float alpha, float loss_weight, bool exact_large_logits, double *sums,
@@ -45,5 +65,10 @@ FocalTail focal_tail(float alpha, float loss_weight, bool exact_large_logits, do
 int fill_levels(const ia_head_geom *g, int B, HLLevels &lv);
 // k_focal_ml<float, bwd> over fa.lv.fblk_off[L] wavefronts; headloss.hip
 int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s);
+
+// geometry -> channels-last table (C % 4 == 0); headloss.hip
+int fill_levels_nhwc(const ia_head_geom *g, int B, NhwcLevels &lv);
+// k_focal_nhwc<bwd, float | bf16, unit label weights> (fa.lw is not read); headloss.hip
+int launch_focal_nhwc_unit(const FocalNhwcArgs &fa, int dtype, bool bwd, hipStream_t s);
 
 }  // namespace ia

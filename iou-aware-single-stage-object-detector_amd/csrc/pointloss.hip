@@ -22,6 +22,15 @@
 //   fp64 sums into the IA_LOSS_SLOTS scheme; backward: d bbox_pred (IoU-loss part + the part
 //   through the attached IoU target in one store), d centerness, d iou for every point.
 // * k_point_finalize -- slots -> the six result floats; n = 0 decided here, on the device.
+//
+// Channels-last rows (ia_point_head_loss_*_nhwc): the head outputs as the two HIP tower routes leave
+// them, fp32 or bf16 pixel rows [cls C | ctr | pad] and [reg 4 | iou? | pad] addressed by pixel strides,
+// the reg row optionally raw (d = exp(scale_l * x) formed here).
+//   forward : k_focal_nhwc<fwd, T, unit weights>  k_point_box_nhwc<T, fwd>  k_point_finalize   (3 launches)
+//   backward: k_point_box_nhwc<T, bwd>  k_focal_nhwc<bwd, T, unit weights>  [k_point_scale_finalize]
+// The labels are read from the int64 targets (low words), no packed copy; point_elem, the finalize kernel
+// and the slot layout are those of the NCHW node; the box kernel's backward also writes the zero gradient
+// of a row's padding channels and adds g * d * x into fp64 slots per level (d scale_l).
 #include <string.h>
 #include "ia_loss.hpp"
 #include "ia_headloss.hpp"
@@ -33,7 +42,9 @@ constexpr float kPtInf = 1e8f;            // the reference's INF sentinel (fcos_
 constexpr int kPtSums = 5;                // sum -log(u) c | sum c | sum BCE_ctr | sum BCE_iou | n
 constexpr int kPtSlotMask = IA_LOSS_SLOTS - 1;
 
-static int point_levels(const ia_point_head_geom *pg, int B, HLLevels &lv)
+// packed: the NCHW node's focal kernel reads the packed labels (the channels-last node does not)
+static int point_levels(const ia_point_head_geom *pg, int B, HLLevels &lv, bool packed = true,
+                        ia_head_geom *out = nullptr)
 {
     if (!pg) return IA_E_ARG;
     ia_head_geom g = ia_head_geom{};
@@ -49,6 +60,8 @@ static int point_levels(const ia_point_head_geom *pg, int B, HLLevels &lv)
     g.cls_activation = IA_CLS_SIGMOID_NOIOU;
     int rc = fill_levels(&g, B, lv);
     if (rc) return rc;
+    if (out) *out = g;
+    if (!packed) return 0;
     // the focal kernel reads the packed labels of a level with HW % 4 == 0 in 16-byte pieces
     for (int l = 0; l < lv.L; ++l)
         if (((lv.H[l] * lv.W[l]) & 3) == 0 && (lv.pack_off[l] & 3)) return IA_E_ARG;
@@ -272,6 +285,177 @@ __global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
     }
 }
 
+
+// ------------------------------------------------------------------ channels-last rows, fp32 / bf16
+struct PtBoxNhwcArgs {
+    HLLevels lv;
+    const void *reg[IA_MAX_LEVELS], *ctr[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
+    int64_t ps_reg[IA_MAX_LEVELS], ps_ctr[IA_MAX_LEVELS], ps_iou[IA_MAX_LEVELS];   // pixel strides (elements)
+    const int64_t *labels[IA_MAX_LEVELS];
+    const float *bt[IA_MAX_LEVELS];
+    void *g_reg[IA_MAX_LEVELS], *g_ctr[IA_MAX_LEVELS], *g_iou[IA_MAX_LEVELS];
+    int64_t pg_reg[IA_MAX_LEVELS], pg_ctr[IA_MAX_LEVELS], pg_iou[IA_MAX_LEVELS];
+    // bwd, packed gradient rows: zero-gradient channels behind d(ctr), and behind d(iou) (d(reg) without it)
+    int32_t pad_cls[IA_MAX_LEVELS], pad_reg[IA_MAX_LEVELS];
+    const float *reg_scale;               // L floats or NULL: reg holds the distances
+    double *sums;                         // fwd: as PtBoxArgs
+    double *scale_sums;                   // bwd with reg_scale: [L][IA_LOSS_SLOTS]
+    const float *res, *gin;
+    float *fgin;
+    int32_t attach;
+};
+
+template <typename T> struct PtStore;
+template <> struct PtStore<float> {
+    static __device__ __forceinline__ void one(float *p, float v) { *p = v; }
+    static __device__ __forceinline__ void four(float *p, const float (&v)[4])
+    {
+        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+};
+template <> struct PtStore<uint16_t> {                     // one round-to-nearest-even each
+    static __device__ __forceinline__ void one(uint16_t *p, float v) { *p = (uint16_t)f32_to_bf16(v); }
+    static __device__ __forceinline__ void four(uint16_t *p, const float (&v)[4])
+    {
+        *reinterpret_cast<uint2 *>(p) = make_uint2(f32_to_bf16(v[0]) | (f32_to_bf16(v[1]) << 16),
+                                                   f32_to_bf16(v[2]) | (f32_to_bf16(v[3]) << 16));
+    }
+};
+template <typename T> __device__ __forceinline__ void load4_f32(const T *p, float (&v)[4]);
+template <> __device__ __forceinline__ void load4_f32<float>(const float *p, float (&v)[4])
+{
+    const float4 q = *reinterpret_cast<const float4 *>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+template <> __device__ __forceinline__ void load4_f32<uint16_t>(const uint16_t *p, float (&v)[4])
+{
+    const uint2 q = *reinterpret_cast<const uint2 *>(p);
+    v[0] = bf16_to_f32((uint16_t)(q.x & 0xffffu)); v[1] = bf16_to_f32((uint16_t)(q.x >> 16));
+    v[2] = bf16_to_f32((uint16_t)(q.y & 0xffffu)); v[3] = bf16_to_f32((uint16_t)(q.y >> 16));
+}
+
+// k_point_box on pixel rows: the blocks, the positive test, point_elem and the fp64 sums are the NCHW
+// kernel's; every point's gradient row is written whole (maps, and the padding the host counted)
+template <typename T, bool BWD, bool IOU>
+__global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
+{
+    __shared__ double red[kPtSums][4];
+    const PtBlock r = locate_point_block(a.lv, blockIdx.x);
+    const int W = a.lv.W[r.l], HW = a.lv.H[r.l] * W;
+    const int p = r.p0 + threadIdx.x;
+    if (BWD && blockIdx.x == 0 && threadIdx.x == 0) a.fgin[3 * a.lv.L] = a.gin[0];
+    const bool raw = a.reg_scale != nullptr;              // uniform
+    double acc[kPtSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double acc_s = 0.0;
+    bool pos = false;
+    if (p < HW) {
+        const int64_t e1 = (int64_t)r.b * HW + p;
+        pos = reinterpret_cast<const int32_t *>(a.labels[r.l])[2 * e1] > 0;      // low word: labels < 2^31
+        float g_box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g_ctr = 0.0f, g_iou = 0.0f;
+        if (pos) {
+            float x[4], d[4];
+            load4_f32<T>(static_cast<const T *>(a.reg[r.l]) + e1 * a.ps_reg[r.l], x);
+            const float sc = raw ? a.reg_scale[r.l] : 1.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = raw ? expf_(sc * x[k]) : x[k];
+            const float4 t = reinterpret_cast<const float4 *>(a.bt[r.l])[e1];
+            const int y = p / W, xx = p - y * W, s = a.lv.stride[r.l];
+            const float px = (float)(xx * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+            const PtElem q = point_elem(px, py, d, t);
+            const float xc = load_f32<T>(static_cast<const T *>(a.ctr[r.l]) + e1 * a.ps_ctr[r.l]);
+            float xi = 0.0f;
+            if constexpr (IOU) xi = load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e1 * a.ps_iou[r.l]);
+            if (!BWD) {
+                acc[0] = (double)(-logf_(q.u) * q.c);
+                acc[1] = (double)q.c;
+                acc[2] = (double)bce_logits_(xc, q.c);
+                if constexpr (IOU) acc[3] = (double)bce_logits_(xi, q.u);
+                acc[4] = 1.0;
+            } else {
+                const float n = a.res[4], sn = a.res[5];
+                const float gs_reg = a.gin[1] / sn, gs_ctr = a.gin[2] / n;
+                g_ctr = (sigmoidf_(xc) - q.c) * gs_ctr;
+                float gu = -(q.c / q.u) * gs_reg;                    // d(-log(u) c) / du
+                if constexpr (IOU) {
+                    const float gs_iou = a.gin[3] / n;
+                    g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
+                    if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
+                }
+                const float inv_un = 1.0f / q.un;
+                const float g_ov = gu * ((q.un + q.ov) * inv_un) * inv_un;
+                const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
+                const float g_w = g_ov * q.h, g_h = g_ov * q.w;
+                const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
+                g_box[0] = g_pw + (q.x1in ? g_w : 0.0f);
+                g_box[1] = g_ph + (q.y1in ? g_h : 0.0f);
+                g_box[2] = g_pw + (q.x2in ? g_w : 0.0f);
+                g_box[3] = g_ph + (q.y2in ? g_h : 0.0f);
+                if (raw) {
+                    // d = exp(scale x): dL/dx = (g d) scale, dL/dscale += (g d) x
+                    float ts = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float gd = g_box[k] * d[k];
+                        ts += gd * x[k];
+                        g_box[k] = gd * sc;
+                    }
+                    acc_s = (double)ts;
+                }
+            }
+        }
+        if (BWD) {
+            T *gr = static_cast<T *>(a.g_reg[r.l]) + e1 * a.pg_reg[r.l];
+            T *gc = static_cast<T *>(a.g_ctr[r.l]) + e1 * a.pg_ctr[r.l];
+            PtStore<T>::four(gr, g_box);
+            PtStore<T>::one(gc, g_ctr);
+            T *tail = gr + 4;                                        // behind d(reg), or behind d(iou)
+            if constexpr (IOU) {
+                T *gi = static_cast<T *>(a.g_iou[r.l]) + e1 * a.pg_iou[r.l];
+                PtStore<T>::one(gi, g_iou);
+                tail = gi + 1;
+            }
+            for (int k = 0; k < a.pad_cls[r.l]; ++k) gc[1 + k] = (T)0;      // +0 in both storage types
+            for (int k = 0; k < a.pad_reg[r.l]; ++k) tail[k] = (T)0;
+        }
+    }
+    if (!BWD) {
+        if (!__syncthreads_or(pos)) return;
+        const int w = threadIdx.x >> 6;
+#pragma unroll
+        for (int k = 0; k < kPtSums; ++k) {
+            if (k == 3 && !IOU) continue;
+            const double s = wave_sum(acc[k]);
+            if ((threadIdx.x & 63) == 0) red[k][w] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < kPtSums && (IOU || threadIdx.x != 3)) {
+            const int k = threadIdx.x;
+            const double s = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+            atomicAdd(a.sums + (size_t)k * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask), s);
+        }
+    } else if (raw) {
+        // a block is one level's: its g d x sum into that level's slots (nothing without a positive)
+        if (!__syncthreads_or(pos)) return;
+        const double s = wave_sum(acc_s);
+        if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            atomicAdd(a.scale_sums + (size_t)r.l * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask),
+                      ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]);
+    }
+}
+
+// slots -> d scale_l (fp32); a level without positives has nothing but the memset's zeros: exactly 0
+__global__ void __launch_bounds__(64) k_point_scale_finalize(const double *scale_sums, int L, float *grad_scale)
+{
+    const int i = threadIdx.x;
+    if (i < L) {
+        double s = 0.0;
+        for (int k = 0; k < IA_LOSS_SLOTS; ++k) s += scale_sums[(size_t)i * IA_LOSS_SLOTS + k];
+        grad_scale[i] = (float)s;
+    }
+}
+
 // ------------------------------------------------------------------ slots -> losses
 struct PtFinArgs {
     const double *sums;                   // [L + kPtSums][IA_LOSS_SLOTS]
@@ -370,6 +554,127 @@ static int point_loss_args(const ia_point_head_geom *g, const ia_point_level_ptr
     ba.sums = nullptr; ba.res = ba.gin = nullptr; ba.fgin = nullptr;
     ba.attach = cfg->attach_iou_target ? 1 : 0;
     return 0;
+}
+
+// ------------------------------------------------------------------ channels-last rows: host
+// workspace: fp64 slots [L + kPtSums] | the focal kernel's two (3L + 4) vectors | fp64 slots [L] of d scale
+struct PtNhwcWorkspace { double *sums; float *fgin, *fres; double *scale_sums; size_t bytes; };
+
+static PtNhwcWorkspace carve_point_nhwc(int L, void *workspace)
+{
+    const size_t slots = ((sizeof(double) * (L + kPtSums) * IA_LOSS_SLOTS + 255) / 256) * 256;
+    const size_t fint = ((sizeof(float) * 2 * (3 * L + 4) + 255) / 256) * 256;
+    const size_t ss = ((sizeof(double) * L * IA_LOSS_SLOTS + 255) / 256) * 256;
+    char *w = static_cast<char *>(workspace);
+    PtNhwcWorkspace r;
+    r.sums = reinterpret_cast<double *>(w);
+    r.fgin = reinterpret_cast<float *>(w + slots);
+    r.fres = r.fgin + (3 * L + 4);
+    r.scale_sums = reinterpret_cast<double *>(w + slots + fint);
+    r.bytes = slots + fint + ss;
+    return r;
+}
+
+static int point_levels_nhwc(const ia_point_head_geom *g, int batch, HLLevels &lv, NhwcLevels &nl)
+{
+    ia_head_geom hg;
+    int rc = point_levels(g, batch, lv, false, &hg);
+    if (rc) return rc;
+    return fill_levels_nhwc(&hg, batch, nl);                // C % 4 == 0: class quads
+}
+
+// one set of maps (head outputs, or gradients): pointers, strides and the alignment of the vector pieces
+static int point_rows_ok(int L, int C, int esize, const ia_point_level_ptrs *p, const ia_point_pix_strides *st,
+                         bool with_iou)
+{
+    const uintptr_t amask = (uintptr_t)(4 * esize - 1);     // 16 bytes fp32, 8 bytes bf16
+    for (int l = 0; l < L; ++l) {
+        if (!p->cls[l] || !p->reg[l] || !p->ctr[l] || ((p->iou[l] != nullptr) != with_iou)) return IA_E_ARG;
+        if (st->cls[l] < C || st->reg[l] < 4 || st->ctr[l] < 1 || (with_iou && st->iou[l] < 1)) return IA_E_ARG;
+        if ((st->cls[l] & 3) || (st->reg[l] & 3)) return IA_E_ARG;
+        if (((uintptr_t)p->cls[l] & amask) || ((uintptr_t)p->reg[l] & amask)) return IA_E_ARG;
+        const uintptr_t emask = (uintptr_t)(esize - 1);
+        if (((uintptr_t)p->ctr[l] & emask) || (with_iou && ((uintptr_t)p->iou[l] & emask))) return IA_E_ARG;
+    }
+    return 0;
+}
+
+// what forward and backward check alike (backward = forward + gradient maps); no launch before it returns 0
+static int point_nhwc_args(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
+                           const ia_point_pix_strides *strides, int dtype, int batch, const ia_point_targets *t,
+                           const ia_point_loss_cfg *cfg, const float *reg_scale, void *workspace,
+                           size_t workspace_bytes, bool bwd, const ia_point_level_ptrs *grads,
+                           const ia_point_pix_strides *grad_strides, int grad_rows_packed,
+                           FocalNhwcArgs &fa, PtBoxNhwcArgs &ba, PtNhwcWorkspace &ws, bool &with_iou)
+{
+    if (!p || !strides || !t || !cfg || !workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
+    if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
+    if (bwd && (!grads || !grad_strides)) return IA_E_ARG;
+    int rc = point_levels_nhwc(g, batch, ba.lv, fa.lv);
+    if (rc) return rc;
+    if (cfg->gamma != 2.0f) return IA_E_ARG;
+    const int L = ba.lv.L, C = ba.lv.C, esize = dtype == IA_BF16 ? 2 : 4;
+    with_iou = p->iou[0] != nullptr;
+    if ((rc = point_rows_ok(L, C, esize, p, strides, with_iou))) return rc;
+    if (bwd && (rc = point_rows_ok(L, C, esize, grads, grad_strides, with_iou))) return rc;
+    ws = carve_point_nhwc(L, workspace);
+    if (workspace_bytes < ws.bytes) return IA_E_WORKSPACE;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < L, gon = on && bwd;
+        if (on && (!t->labels[l] || !t->bbox_targets[l] || ((uintptr_t)t->bbox_targets[l] & 15u))) return IA_E_ARG;
+        fa.cls[l] = on ? p->cls[l] : nullptr;
+        fa.ps_cls[l] = on ? strides->cls[l] : 0;
+        fa.labels[l] = on ? t->labels[l] : nullptr;
+        fa.lw[l] = nullptr;                                  // unit weights: never read
+        fa.grad[l] = gon ? const_cast<void *>(grads->cls[l]) : nullptr;
+        fa.ps_grad[l] = gon ? grad_strides->cls[l] : 0;
+        ba.reg[l] = on ? p->reg[l] : nullptr; ba.ctr[l] = on ? p->ctr[l] : nullptr;
+        ba.iou[l] = (on && with_iou) ? p->iou[l] : nullptr;
+        ba.ps_reg[l] = on ? strides->reg[l] : 0; ba.ps_ctr[l] = on ? strides->ctr[l] : 0;
+        ba.ps_iou[l] = (on && with_iou) ? strides->iou[l] : 0;
+        ba.labels[l] = on ? t->labels[l] : nullptr;
+        ba.bt[l] = on ? t->bbox_targets[l] : nullptr;
+        ba.g_reg[l] = gon ? const_cast<void *>(grads->reg[l]) : nullptr;
+        ba.g_ctr[l] = gon ? const_cast<void *>(grads->ctr[l]) : nullptr;
+        ba.g_iou[l] = (gon && with_iou) ? const_cast<void *>(grads->iou[l]) : nullptr;
+        ba.pg_reg[l] = gon ? grad_strides->reg[l] : 0; ba.pg_ctr[l] = gon ? grad_strides->ctr[l] : 0;
+        ba.pg_iou[l] = (gon && with_iou) ? grad_strides->iou[l] : 0;
+        ba.pad_cls[l] = ba.pad_reg[l] = 0;
+        if (gon && grad_rows_packed) {
+            // the caller states rows [cls C | ctr | pad] and [reg 4 | iou? | pad]: the channels left up to
+            // each row's end get their zero gradient in the box kernel
+            const char *gc = static_cast<const char *>(grads->cls[l]), *gr = static_cast<const char *>(grads->reg[l]);
+            if (static_cast<const char *>(grads->ctr[l]) != gc + (size_t)C * esize ||
+                grad_strides->ctr[l] != grad_strides->cls[l] || grad_strides->cls[l] < C + 1)
+                return IA_E_ARG;
+            const int nreg = with_iou ? 5 : 4;
+            if (with_iou && (static_cast<const char *>(grads->iou[l]) != gr + (size_t)4 * esize ||
+                             grad_strides->iou[l] != grad_strides->reg[l]))
+                return IA_E_ARG;
+            if (grad_strides->reg[l] < nreg || grad_strides->cls[l] - (C + 1) > 1024 ||
+                grad_strides->reg[l] - nreg > 1024)
+                return IA_E_ARG;
+            ba.pad_cls[l] = (int32_t)(grad_strides->cls[l] - (C + 1));
+            ba.pad_reg[l] = (int32_t)(grad_strides->reg[l] - nreg);
+        }
+    }
+    fa.tail = focal_tail(cfg->alpha, 1.0f, false, nullptr, nullptr, nullptr);
+    ba.reg_scale = reg_scale;
+    ba.sums = nullptr; ba.scale_sums = ws.scale_sums;
+    ba.res = ba.gin = nullptr; ba.fgin = nullptr;
+    ba.attach = cfg->attach_iou_target ? 1 : 0;
+    return 0;
+}
+
+static int launch_point_box_nhwc(int dtype, bool bwd, bool with_iou, const PtBoxNhwcArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][2][2])(PtBoxNhwcArgs) = {
+        {{k_point_box_nhwc<float, false, false>, k_point_box_nhwc<float, false, true>},
+         {k_point_box_nhwc<float, true, false>, k_point_box_nhwc<float, true, true>}},
+        {{k_point_box_nhwc<uint16_t, false, false>, k_point_box_nhwc<uint16_t, false, true>},
+         {k_point_box_nhwc<uint16_t, true, false>, k_point_box_nhwc<uint16_t, true, true>}}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd][with_iou], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
 }
 
 }  // namespace ia
@@ -495,6 +800,81 @@ int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptr
     else hipLaunchKernelGGL((k_point_box<true, false>), dim3(grid), dim3(256), 0, s, ba);
     if ((rc = hip_status(hipGetLastError()))) return rc;
     return launch_focal_ml_f32(fa, true, s);
+}
+
+size_t ia_point_head_loss_nhwc_workspace_bytes(const ia_point_head_geom *g, int batch)
+{
+    ia::HLLevels lv;
+    ia::NhwcLevels nl;
+    if (ia::point_levels_nhwc(g, batch, lv, nl)) return 0;
+    return ia::carve_point_nhwc(lv.L, nullptr).bytes;
+}
+
+int ia_point_head_loss_fwd_nhwc(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
+                                const ia_point_pix_strides *strides, int dtype, int batch,
+                                const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                                const float *reg_scale, void *workspace, size_t workspace_bytes,
+                                float *result, void *stream)
+{
+    using namespace ia;
+    if (!result) return IA_E_ARG;
+    FocalNhwcArgs fa;
+    PtBoxNhwcArgs ba;
+    PtNhwcWorkspace ws;
+    bool with_iou;
+    int rc = point_nhwc_args(g, p, strides, dtype, batch, t, cfg, reg_scale, workspace, workspace_bytes, false,
+                             nullptr, nullptr, 0, fa, ba, ws, with_iou);
+    if (rc) return rc;
+    const int L = ba.lv.L;
+    fa.tail.sums = ws.sums;
+    fa.tail.big_logits = cfg->exact_large_logits ? 1 : 0;
+    ba.sums = ws.sums + (size_t)L * IA_LOSS_SLOTS;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s);
+    if (e != hipSuccess) return (int)e;
+    if ((rc = launch_focal_nhwc_unit(fa, dtype, false, s))) return rc;
+    if ((rc = launch_point_box_nhwc(dtype, false, with_iou, ba, s))) return rc;
+    PtFinArgs f;
+    f.sums = ws.sums; f.counts = t->counts; f.L = L; f.B = batch; f.iou = with_iou ? 1 : 0;
+    f.res = result; f.fgin = ws.fgin; f.fres = ws.fres;
+    hipLaunchKernelGGL(k_point_finalize, dim3(1), dim3(64), 0, s, f);
+    return hip_status(hipGetLastError());
+}
+
+int ia_point_head_loss_bwd_nhwc(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
+                                const ia_point_pix_strides *strides, int dtype, int batch,
+                                const ia_point_targets *t, const ia_point_loss_cfg *cfg,
+                                const float *reg_scale, void *workspace, size_t workspace_bytes,
+                                const float *result, const float *grad_result,
+                                const ia_point_level_ptrs *grads, const ia_point_pix_strides *grad_strides,
+                                int grad_rows_packed, float *grad_scale, void *stream)
+{
+    using namespace ia;
+    if (!result || !grad_result) return IA_E_ARG;
+    if ((reg_scale != nullptr) != (grad_scale != nullptr)) return IA_E_ARG;
+    FocalNhwcArgs fa;
+    PtBoxNhwcArgs ba;
+    PtNhwcWorkspace ws;
+    bool with_iou;
+    int rc = point_nhwc_args(g, p, strides, dtype, batch, t, cfg, reg_scale, workspace, workspace_bytes, true,
+                             grads, grad_strides, grad_rows_packed, fa, ba, ws, with_iou);
+    if (rc) return rc;
+    const int L = ba.lv.L;
+    fa.tail.gin = ws.fgin; fa.tail.res = ws.fres;
+    ba.res = result; ba.gin = grad_result; ba.fgin = ws.fgin;
+    hipStream_t s = (hipStream_t)stream;
+    if (reg_scale) {
+        hipError_t e = hipMemsetAsync(ws.scale_sums, 0, sizeof(double) * (size_t)L * IA_LOSS_SLOTS, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    // the box kernel first: it hands the upstream gradient of loss_cls to the focal kernel
+    if ((rc = launch_point_box_nhwc(dtype, true, with_iou, ba, s))) return rc;
+    if ((rc = launch_focal_nhwc_unit(fa, dtype, true, s))) return rc;
+    if (reg_scale) {
+        hipLaunchKernelGGL(k_point_scale_finalize, dim3(1), dim3(64), 0, s, ws.scale_sums, L, grad_scale);
+        return hip_status(hipGetLastError());
+    }
+    return 0;
 }
 
 }  // extern "C"

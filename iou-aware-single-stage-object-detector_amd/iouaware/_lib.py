@@ -72,6 +72,12 @@ class PointLevelPtrs(C.Structure):
                 ('ctr', C.c_void_p * IA_MAX_LEVELS), ('iou', C.c_void_p * IA_MAX_LEVELS)]
 
 
+class PointPixStrides(C.Structure):
+    """ia_point_pix_strides"""
+    _fields_ = [('cls', C.c_int64 * IA_MAX_LEVELS), ('reg', C.c_int64 * IA_MAX_LEVELS),
+                ('ctr', C.c_int64 * IA_MAX_LEVELS), ('iou', C.c_int64 * IA_MAX_LEVELS)]
+
+
 class PointTargets(C.Structure):
     """ia_point_targets"""
     _fields_ = [('labels', C.c_void_p * IA_MAX_LEVELS), ('bbox_targets', C.c_void_p * IA_MAX_LEVELS),
@@ -111,6 +117,7 @@ _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 _G, _P = C.POINTER(HeadGeom), C.POINTER(LevelPtrs)
 _PG, _WG = C.POINTER(PointHeadGeom), C.POINTER(WinoGeom)
 _PP, _PT, _PC = C.POINTER(PointLevelPtrs), C.POINTER(PointTargets), C.POINTER(PointLossCfg)
+_PS = C.POINTER(PointPixStrides)
 
 # name -> (restype, argtypes); mirrors include/iouaware.h one to one
 SIGNATURES = {
@@ -285,6 +292,10 @@ SIGNATURES = {
     'ia_point_head_loss_workspace_bytes': (_sz, [_PG, _i]),
     'ia_point_head_loss_fwd': (_i, [_PG, _PP, _i, _PT, _PC, _vp, _sz, _vp, _vp]),
     'ia_point_head_loss_bwd': (_i, [_PG, _PP, _i, _PT, _PC, _vp, _vp, _vp, _PP, _vp]),
+    'ia_point_head_loss_nhwc_workspace_bytes': (_sz, [_PG, _i]),
+    'ia_point_head_loss_fwd_nhwc': (_i, [_PG, _PP, _PS, _i, _i, _PT, _PC, _vp, _vp, _sz, _vp, _vp]),
+    'ia_point_head_loss_bwd_nhwc': (_i, [_PG, _PP, _PS, _i, _i, _PT, _PC, _vp, _vp, _sz, _vp, _vp, _PP,
+                                         _PS, _i, _vp, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

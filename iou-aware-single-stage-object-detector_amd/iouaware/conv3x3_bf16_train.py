@@ -138,10 +138,17 @@ def _wide(ts, n):
 class _Bf16ConvLevels(torch.autograd.Function):
     """conv3x3 (stride 1, pad 1) + bias (+ ReLU) with ONE fp32 weight (groups * cout, cin, 3, 3) over
     `groups` lists of bf16 level tensors; outputs: groups x levels bf16 tensors, the channel slices
-    [g * P, g * P + cout) of one (B, groups * P, H, W) tensor per level, P = cout rounded up to 32"""
+    [g * P, g * P + cout) of one (B, groups * P, H, W) tensor per level, P = cout rounded up to 32.
+    `padded` (the subclass _Bf16ConvLevelsPadded, one group): the outputs are the (B, P, H, W) tensors
+    themselves (zeros behind cout), and backward takes gradients of that width as they are (the padding's
+    gradient is not read)"""
 
     @staticmethod
     def forward(ctx, weight, bias, relu, groups, *xs):
+        return _Bf16ConvLevels._forward(ctx, False, weight, bias, relu, groups, xs)
+
+    @staticmethod
+    def _forward(ctx, padded, weight, bias, relu, groups, xs):
         L = len(xs) // groups
         xg = [[_cl_bf16(x) for x in xs[g * L:(g + 1) * L]] for g in range(groups)]
         cout, cin = weight.shape[0] // groups, weight.shape[1]
@@ -158,8 +165,11 @@ class _Bf16ConvLevels(torch.autograd.Function):
             ops.conv3x3_bf16_levels(xg[:ge], wp, b, ce, yk, relu=relu, cin=cin)
             ys = [[t[:, g * cout:(g + 1) * cout] for t in bufs] for g in range(groups)] if shared else yk
         ctx.relu, ctx.has_bias, ctx.groups, ctx.L, ctx.shared = bool(relu), bias is not None, groups, L, shared
+        ctx.padded = bool(padded)
         flat_x = [x for g in range(ge) for x in xg[g]]
         ctx.save_for_backward(weight, *flat_x, *(bufs if relu else []))
+        if padded:
+            return tuple(bufs)
         return tuple(y for g in range(groups) for y in ys[g])
 
     @staticmethod
@@ -174,6 +184,8 @@ class _Bf16ConvLevels(torch.autograd.Function):
         ybufs = list(saved[1 + ge * L:1 + ge * L + L]) if ctx.relu else None
         with torch.no_grad():
             dyg = [[_cl_bf16(d) for d in dys[g * L:(g + 1) * L]] for g in range(groups)]
+            if ctx.padded:                # (B, P, H, W) gradients: the real channels, where they lie
+                dyg = [[d[:, :cout] for d in dyg[0]]]
             want_b = ctx.has_bias and ctx.needs_input_grad[1]
             need_x = any(ctx.needs_input_grad[4:])
             # the incoming gradients of two groups as ONE (B, 2 * cout, H, W) tensor per level when they
@@ -225,20 +237,33 @@ class _Bf16ConvLevels(torch.autograd.Function):
         return (dw, db, None, None) + tuple(dxs)
 
 
-def conv_levels(xs_groups, weight, bias=None, relu=False):
+class _Bf16ConvLevelsPadded(_Bf16ConvLevels):
+    """_Bf16ConvLevels (one group) whose outputs are the tensors of the padded width"""
+
+    @staticmethod
+    def forward(ctx, weight, bias, relu, groups, *xs):
+        return _Bf16ConvLevels._forward(ctx, True, weight, bias, relu, groups, xs)
+
+
+def conv_levels(xs_groups, weight, bias=None, relu=False, padded=False):
     """xs_groups: one or two lists (the cls / reg tower) of per-level (B, cin, H, W) bf16 CUDA tensors
     (channels-last or channel slices of channels-last tensors); weight fp32 (groups * cout, cin, 3,
     3), bias fp32 (groups * cout) or None -> per group the list of per-level (B, cout, H, W) bf16
     tensors (channel slices of one channels-last tensor per level).  cin % 32 == 0, cout even.
     Two groups given the SAME input tensors run as one convolution with 2 * cout outputs, and the
-    input's gradient is the sum over both."""
+    input's gradient is the sum over both.
+    padded (one group only): -> [the list of per-level (B, P, H, W) tensors], P = cout rounded up to 32,
+    zeros in the channels behind cout; their gradients are taken at that width."""
     groups = len(xs_groups)
     L = len(xs_groups[0])
     if not 1 <= groups <= 2 or any(len(g) != L for g in xs_groups):
         raise ValueError('conv_levels takes one or two groups of the same levels')
+    if padded and groups != 1:
+        raise ValueError('conv_levels: padded outputs for one group only')
     if any(not x.is_cuda or x.dtype != _BF for g in xs_groups for x in g) or weight.dtype != torch.float32:
         raise TypeError('conv_levels takes bf16 CUDA activations and an fp32 weight')
-    out = _Bf16ConvLevels.apply(weight, bias, bool(relu), groups, *[x for g in xs_groups for x in g])
+    node = _Bf16ConvLevelsPadded if padded else _Bf16ConvLevels
+    out = node.apply(weight, bias, bool(relu), groups, *[x for g in xs_groups for x in g])
     return [list(out[g * L:(g + 1) * L]) for g in range(groups)]
 
 
@@ -353,24 +378,56 @@ def fcos_usable(feats, head):
             and fcos_head_supported(head, [tuple(x.shape[-2:]) for x in feats], feats[0].shape[0]))
 
 
-def _packed_outputs(convs, feat):
-    """several output convolutions of one tower as one bf16 node (columns padded with zero weight and
-    bias to an even count: the forward kernel stores channel pairs) -> per convolution the list of
-    per-level fp32 NCHW-contiguous maps"""
+def _packed_weights(convs):
+    """several output convolutions of one tower as one: weight and bias, columns padded with zeros to an
+    even count (the forward kernel stores channel pairs)"""
     n = [c.out_channels for c in convs]
     pad = sum(n) % 2
     w0, b0 = convs[0].weight, convs[0].bias
     if len(convs) == 1 and not pad:
-        w, b = w0, b0
-    else:
-        w = torch.cat([c.weight for c in convs] + ([w0.new_zeros((pad,) + tuple(w0.shape[1:]))] if pad else []))
-        b = torch.cat([c.bias for c in convs] + ([b0.new_zeros(pad)] if pad else []))
+        return w0, b0
+    w = torch.cat([c.weight for c in convs] + ([w0.new_zeros((pad,) + tuple(w0.shape[1:]))] if pad else []))
+    b = torch.cat([c.bias for c in convs] + ([b0.new_zeros(pad)] if pad else []))
+    return w, b
+
+
+def _packed_outputs(convs, feat):
+    """several output convolutions of one tower as one bf16 node -> per convolution the list of
+    per-level fp32 NCHW-contiguous maps"""
+    w, b = _packed_weights(convs)
     ys = conv_levels([feat], w, b)[0]
     res, off = [], 0
-    for k in n:
+    for k in [c.out_channels for c in convs]:
         res.append([t[:, off:off + k].to(torch.float32, memory_format=torch.contiguous_format) for t in ys])
         off += k
     return res
+
+
+def _fcos_towers(head, feats):
+    """both GN towers in bf16 -> (cls_feat[L], reg_feat[L]): the features cast once to bf16
+    channels-last; per tower layer one convolution node for both towers and ONE GroupNorm + ReLU node
+    on the 2F-channel activation"""
+    from .fcos_ops import groupnorm_relu_bf16_towers
+    xs = [x.to(dtype=_BF, memory_format=_CL) for x in feats]
+    cur = [xs, xs]
+    for mc, mr in zip(head.cls_convs, head.reg_convs):
+        cur = conv_levels(cur, torch.cat([mc.conv.weight, mr.conv.weight]), None, relu=False)
+        gc, gr = mc.norm, mr.norm
+        cur = list(groupnorm_relu_bf16_towers(cur[0], cur[1], torch.cat([gc.weight, gr.weight]),
+                                              torch.cat([gc.bias, gr.bias]), 2 * gc.num_groups, gc.eps))
+    return cur
+
+
+def fcos_head_forward_packed(head, feats):
+    """the towers and the two output convolutions of fcos_head_forward, and nothing behind them:
+    -> (cls_ctr[L], reg_iou[L]), the bf16 channels-last outputs of the padded width (82 -> 96, 6 -> 32),
+    rows [cls | centerness | zeros] and [raw fcos_reg 4 | iou? | zeros], unsliced and unconverted -- what
+    fcos_ops.point_head_loss_packed takes.  The convolution node's backward takes a gradient of the
+    padded width as it is."""
+    cls_feat, reg_feat = _fcos_towers(head, feats)
+    wc, bc = _packed_weights([head.fcos_cls, head.fcos_centerness])
+    wr, br = _packed_weights([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []))
+    return (conv_levels([cls_feat], wc, bc, padded=True)[0], conv_levels([reg_feat], wr, br, padded=True)[0])
 
 
 def fcos_head_forward(head, feats):
@@ -383,15 +440,7 @@ def fcos_head_forward(head, feats):
     head).  The outputs become fp32 NCHW maps and bbox_pred = exp(scale_l * reg) runs in torch in
     fp32: the reference's tuple (cls[L], bbox[L], centerness[L][, iou[L]]), which the fused loss node
     takes."""
-    from .fcos_ops import groupnorm_relu_bf16_towers
-    xs = [x.to(dtype=_BF, memory_format=_CL) for x in feats]
-    cur = [xs, xs]
-    for mc, mr in zip(head.cls_convs, head.reg_convs):
-        cur = conv_levels(cur, torch.cat([mc.conv.weight, mr.conv.weight]), None, relu=False)
-        gc, gr = mc.norm, mr.norm
-        cur = list(groupnorm_relu_bf16_towers(cur[0], cur[1], torch.cat([gc.weight, gr.weight]),
-                                              torch.cat([gc.bias, gr.bias]), 2 * gc.num_groups, gc.eps))
-    cls_feat, reg_feat = cur
+    cls_feat, reg_feat = _fcos_towers(head, feats)
     cls, ctr = _packed_outputs([head.fcos_cls, head.fcos_centerness], cls_feat)
     ri = _packed_outputs([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []), reg_feat)
     bbox = [scale(t).exp() for t, scale in zip(ri[0], head.scales)]

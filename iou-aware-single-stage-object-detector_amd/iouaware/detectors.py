@@ -81,7 +81,12 @@ class SingleStageDetector(BaseDetector):
         return self.neck(x) if self.with_neck else x
 
     def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
-        outs = self.bbox_head(self.extract_feat(img))
+        feats = self.extract_feat(img)
+        if getattr(self.bbox_head, 'fuse_head_loss', False) and hasattr(self.bbox_head, 'forward_loss'):
+            # forward + loss in one call (the FCOS heads: packed tower outputs straight into the loss node)
+            return self.bbox_head.forward_loss(feats, gt_bboxes, gt_labels, img_metas, self.train_cfg,
+                                               gt_bboxes_ignore=gt_bboxes_ignore)
+        outs = self.bbox_head(feats)
         return self.bbox_head.loss(*(outs + (gt_bboxes, gt_labels, img_metas, self.train_cfg)),
                                    gt_bboxes_ignore=gt_bboxes_ignore)
 

@@ -20,6 +20,9 @@ constructor kwargs, parameter names and method signatures.
     fcos_ops.point_head_loss: csrc/pointloss.hip), no host synchronisation; `fuse_loss = False`, or
     inputs the node does not cover (see _fused_loss_ok), take the torch transcription of the
     reference with the class term through the HIP sigmoid focal-loss op.
+  * forward_loss (opt-in, `fuse_head_loss = True`): forward + loss as one call; on the two HIP tower
+    routes the packed channels-last outputs of the output convolutions go straight into the loss
+    node (fcos_ops.point_head_loss_packed), exp(scale * x) inside it.
 There is no CPU fallback for get_bboxes / loss: they need tensors on a gfx950 device.
 
 Both heads are `_FCOSHeadBase` with the class attribute `iou_branch` (fcos_iou present or absent):
@@ -93,8 +96,8 @@ class _FCOSHeadBase(nn.Module):
         if self.iou_branch:
             normal_init(self.fcos_iou, std=0.01)
 
-    # training: all-levels Winograd towers + HIP GroupNorm when set and usable.  Off by default: the
-    # whole-iteration comparison against the module route is not measured yet
+    # training: all-levels Winograd towers + HIP GroupNorm when set and usable.  Off by default (the
+    # whole-iteration comparison against the module route: DESIGN 3.17, "Whole FCOS training iterations")
     train_winograd = False
     # training: bf16 activations on the MFMA convolution kernels and the bf16 GroupNorm node, fp32
     # master weights (conv3x3_bf16_train.fcos_head_forward).  Off by default: it changes the
@@ -202,24 +205,69 @@ class _FCOSHeadBase(nn.Module):
     # targets and loss on the HIP kernels of csrc/pointloss.hip where they apply (_fused_loss_ok)
     fuse_loss = True
 
-    def _fused_loss_ok(self, maps, gt_bboxes, gt_labels, cfg):
-        """what the HIP node covers: fp32 NCHW-contiguous device maps, gamma 2, at most 8 levels,
-        1..512 gts per image, at most 16 images"""
-        L = len(maps[0])
+    def _fused_targets_ok(self, L, B, gt_bboxes, gt_labels, cfg):
+        """what the HIP target and loss kernels cover whatever the maps' layout: gamma 2, at most 8
+        levels, 1..512 gts per image on the device, at most 16 images"""
         if not 1 <= L <= fcos_ops._lib.IA_MAX_LEVELS or L != len(self.strides):
             return False
         if float(cfg.gamma) != 2.0:
             return False
-        B = maps[0][0].size(0)
         if not 1 <= B <= fcos_ops._lib.IA_MAX_TARGET_BATCH or len(gt_bboxes) != B or len(gt_labels) != B:
             return False
-        for t in [t for m in maps for t in m]:
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
-                return False
         for b, l in zip(gt_bboxes, gt_labels):
             if not (b.is_cuda and l.is_cuda) or not 1 <= b.size(0) <= 512 or l.size(0) != b.size(0):
                 return False
         return True
+
+    def _fused_loss_ok(self, maps, gt_bboxes, gt_labels, cfg):
+        """what the HIP node covers: fp32 NCHW-contiguous device maps, gamma 2, at most 8 levels,
+        1..512 gts per image, at most 16 images"""
+        if not maps[0] or not self._fused_targets_ok(len(maps[0]), maps[0][0].size(0), gt_bboxes, gt_labels, cfg):
+            return False
+        for t in [t for m in maps for t in m]:
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+                return False
+        return True
+
+    # training: towers, output convolutions, point targets and the loss node on the packed channels-last
+    # rows with nothing in between (forward_loss).  Off by default: see DESIGN 3.17 for what it buys
+    fuse_head_loss = False
+
+    def _packed_route(self, feats):
+        """the HIP tower route that produces packed rows for these features (its
+        fcos_head_forward_packed), or None"""
+        if not self.training:
+            return None
+        if self.train_bf16:
+            from . import conv3x3_bf16_train
+            if conv3x3_bf16_train.fcos_usable(feats, self):
+                return conv3x3_bf16_train.fcos_head_forward_packed
+        if self.train_winograd:
+            from . import winograd_train
+            if winograd_train.fcos_usable(feats, self):
+                return winograd_train.fcos_head_forward_packed
+        return None
+
+    def forward_loss(self, feats, gt_bboxes, gt_labels, img_metas, cfg, gt_bboxes_ignore=None):
+        """loss(*forward(feats), ...) -- the same dict.  With `fuse_head_loss = True`, in training on one
+        of the two HIP tower routes and where the conditions of _fused_loss_ok hold (the dtype and
+        layout being the route's own: fp32 or bf16 channels-last rows), the towers' packed outputs go
+        straight into fcos_ops.point_head_loss_packed: no slice, no conversion, no Scale / exp node --
+        exp(scale_l * reg) is formed in the loss kernels, which return the scales' gradients."""
+        feats = list(feats)
+        route = self._packed_route(feats) if (self.fuse_head_loss and self.fuse_loss and feats) else None
+        if route is not None and self._fused_targets_ok(len(feats), feats[0].size(0), gt_bboxes,
+                                                        gt_labels, cfg):
+            B = feats[0].size(0)
+            geom = self.geometry([tuple(x.shape[-2:]) for x in feats])
+            if fcos_ops.point_loss_supported(geom, B) and fcos_ops.point_loss_packed_supported(geom, B):
+                cls_ctr, reg_iou = route(self, feats)
+                labels, bbox_targets, counts = fcos_ops.point_targets(geom, gt_bboxes, gt_labels,
+                                                                      self.regress_ranges)
+                return fcos_ops.point_head_loss_packed(
+                    geom, cls_ctr, reg_iou, [s.scale for s in list(self.scales)[:geom.L]], labels,
+                    bbox_targets, counts, cfg.gamma, cfg.alpha, with_iou=self.iou_branch)
+        return self.loss(*self(feats), gt_bboxes, gt_labels, img_metas, cfg)
 
     def _loss(self, cls_scores, bbox_preds, centernesses, ious, gt_bboxes, gt_labels, cfg):
         """focal classification over (num_pos + num_imgs), the centerness-weighted IoU loss, the

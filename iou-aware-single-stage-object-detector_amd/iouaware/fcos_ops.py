@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import LevelPtrs, PointHeadGeom, PointLevelPtrs
+from ._lib import LevelPtrs, PointHeadGeom, PointLevelPtrs, PointPixStrides
 from . import winograd
 from .ops import (_LayoutTwin, _det_outputs, _meta_tensors, _own_workspace, _ptr, _require_gpu,
                   _state_workspace, _stream, _ws_views, _zero1, stream_id, to_nchw)
@@ -616,6 +616,138 @@ def point_head_loss(geom, cls, reg, ctr, iou, labels, bbox_targets, counts, gamm
         _require_gpu(t, 'head output')
     cfg = (float(gamma), float(alpha), int(bool(attach_iou_target)), int(bool(exact_large_logits)))
     res = _PointHeadLossFn.apply(geom, (labels, bbox_targets, counts), cfg, with_iou, *outs)
+    losses = dict(loss_cls=res[0], loss_reg=res[1], loss_centerness=res[2])
+    if with_iou:
+        losses['loss_iou'] = res[3]
+    return losses
+
+
+# ------------------------------------------------------------------ the loss on packed channels-last rows
+def point_loss_packed_supported(geom, batch):
+    """whether the channels-last loss kernels cover this geometry and batch (C % 4 == 0)"""
+    return _lib.lib().ia_point_head_loss_nhwc_workspace_bytes(geom.ref(), int(batch)) != 0
+
+
+def _packed_rows(geom, cls_ctr, reg_iou, with_iou):
+    """the argument contract of point_head_loss_packed, checked before the device is touched
+    -> (batch, dtype)"""
+    L = geom.L
+    if len(cls_ctr) != L or len(reg_iou) != L:
+        raise ValueError('point_head_loss_packed: expected %d levels, got %d / %d'
+                         % (L, len(cls_ctr), len(reg_iou)))
+    dtype = cls_ctr[0].dtype
+    if dtype not in _DTYPES or any(t.dtype != dtype for t in list(cls_ctr) + list(reg_iou)):
+        raise TypeError('point_head_loss_packed takes fp32 or bf16 rows, all of one dtype')
+    B = cls_ctr[0].shape[0] if cls_ctr[0].dim() == 4 else -1
+    for l in range(L):
+        h, w = geom.featmap_sizes[l]
+        for name, t, need in (('cls_ctr', cls_ctr[l], geom.C + 1), ('reg_iou', reg_iou[l], 5 if with_iou else 4)):
+            if t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (h, w):
+                raise ValueError('%s level %d has shape %s, expected (%d, width, %d, %d)'
+                                 % (name, l, tuple(t.shape), B, h, w))
+            if t.shape[1] < need:
+                raise ValueError('%s level %d: a row of %d channels is too narrow for its maps (%d)'
+                                 % (name, l, t.shape[1], need))
+            if t.shape[1] % 4 or not t.is_contiguous(memory_format=_CL) \
+                    or t.data_ptr() % (4 * t.element_size()):
+                raise ValueError('%s level %d: rows must be dense channels-last, a multiple of 4 channels '
+                                 'wide and aligned to 4 elements' % (name, l))
+    for t in list(cls_ctr) + list(reg_iou):
+        _require_gpu(t, 'packed head output')
+    return B, dtype
+
+
+def _packed_ptrs(geom, cls_ctr, reg_iou, with_iou):
+    p, st = PointLevelPtrs(), PointPixStrides()
+    es = cls_ctr[0].element_size()
+    for l in range(geom.L):
+        c, r = cls_ctr[l], reg_iou[l]
+        p.cls[l], p.ctr[l] = c.data_ptr(), c.data_ptr() + geom.C * es
+        p.reg[l], p.iou[l] = r.data_ptr(), (r.data_ptr() + 4 * es) if with_iou else None
+        st.cls[l] = st.ctr[l] = int(c.shape[1])
+        st.reg[l] = st.iou[l] = int(r.shape[1])
+    return p, st
+
+
+class _PointHeadLossPackedFn(torch.autograd.Function):
+    """the FCOS losses of every level on the towers' own output rows (ia_point_head_loss_*_nhwc): 3
+    launches forward, 3 backward.  Inputs: L rows [cls C | ctr | pad], L rows [reg 4 | iou? | pad] (the
+    raw fcos_reg output: exp(scale_l * x) is formed in the kernels), L scales."""
+
+    @staticmethod
+    def forward(ctx, geom, targets, cfg, with_iou, *ins):
+        L = geom.L
+        cls_ctr, reg_iou, scales = list(ins[:L]), list(ins[L:2 * L]), list(ins[2 * L:])
+        B, dtype = _packed_rows(geom, cls_ctr, reg_iou, with_iou)
+        dev = cls_ctr[0].device
+        labels, bbox_targets, counts = targets
+        labels = [t.contiguous().to(torch.int64) for t in labels]
+        bbox_targets = [t.contiguous().to(torch.float32) for t in bbox_targets]
+        for t in labels + bbox_targets:
+            _require_gpu(t, 'targets')
+        pt = _lib.PointTargets()
+        for l in range(L):
+            pt.labels[l], pt.bbox_targets[l] = labels[l].data_ptr(), bbox_targets[l].data_ptr()
+        pt.packed = None
+        pt.counts = counts.data_ptr() if counts is not None else None
+        p, st = _packed_ptrs(geom, cls_ctr, reg_iou, with_iou)
+        pc = _lib.PointLossCfg(*cfg)
+        sc = torch.cat([s.detach().reshape(1).to(torch.float32) for s in scales])
+        nbytes = _lib.lib().ia_point_head_loss_nhwc_workspace_bytes(geom.ref(), B)
+        if nbytes == 0:
+            raise _lib.IouAwareLibraryError('unsupported geometry / batch for ia_point_head_loss_fwd_nhwc')
+        ws = _own_workspace(dev, nbytes)   # carries the normalisers from forward to backward
+        res = torch.empty(6, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().ia_point_head_loss_fwd_nhwc(
+            geom.ref(), C.byref(p), C.byref(st), _DTYPES[dtype], B, C.byref(pt), C.byref(pc), _ptr(sc),
+            _ptr(ws), nbytes, _ptr(res), _stream()), 'ia_point_head_loss_fwd_nhwc')
+        ctx.ws, ctx.res, ctx.geom, ctx.cfg, ctx.B, ctx.with_iou = ws, res, geom, pc, B, with_iou
+        ctx.keep = (cls_ctr, reg_iou, sc, p, st, pt, (labels, bbox_targets, counts))
+        ctx.scale_shapes = [tuple(s.shape) for s in scales]
+        ctx.set_materialize_grads(False)
+        return tuple(res[:4].view(4, 1).unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        cls_ctr, reg_iou, sc, p, st, pt, _ = ctx.keep
+        geom, L, dev = ctx.geom, ctx.geom.L, cls_ctr[0].device
+        z = _zero1(dev)
+        gin = torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
+        # of the inputs' dtype, shape and memory format; the kernels write every channel (rows stated packed)
+        g_cc = [torch.empty_like(t) for t in cls_ctr]
+        g_ri = [torch.empty_like(t) for t in reg_iou]
+        gp, gst = _packed_ptrs(geom, g_cc, g_ri, ctx.with_iou)
+        g_sc = torch.empty(L, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().ia_point_head_loss_bwd_nhwc(
+            geom.ref(), C.byref(p), C.byref(st), _DTYPES[cls_ctr[0].dtype], ctx.B, C.byref(pt),
+            C.byref(ctx.cfg), _ptr(sc), _ptr(ctx.ws), ctx.ws.numel(), _ptr(ctx.res), _ptr(gin),
+            C.byref(gp), C.byref(gst), 1, _ptr(g_sc), _stream()), 'ia_point_head_loss_bwd_nhwc')
+        g_scales = [g_sc[l:l + 1].reshape(shape) for l, shape in enumerate(ctx.scale_shapes)]
+        return (None, None, None, None) + tuple(g_cc) + tuple(g_ri) + tuple(g_scales)
+
+
+def point_head_loss_packed(geom, cls_ctr, reg_iou, scales, labels, bbox_targets, counts, gamma=2.0,
+                           alpha=0.25, attach_iou_target=True, exact_large_logits=False, with_iou=True):
+    """point_head_loss on the packed channels-last outputs of the HIP tower routes, consumed in place:
+    cls_ctr[l] (B, wc, H_l, W_l) rows [cls C | centerness | padding], reg_iou[l] (B, wr, H_l, W_l) rows
+    [raw fcos_reg 4 | iou (with_iou) | padding], fp32 or bf16 (one dtype), dense channels-last, any
+    width that is a multiple of 4; scales: the L Scale parameters -- bbox_pred = exp(scale_l * reg) is
+    formed inside the kernels.  One autograd node: its gradients are one tensor per packed input, of
+    that input's dtype, shape and memory format with every channel written (zeros in the padding), and
+    one fp32 gradient per scale.  -> the reference's loss dict (loss_iou with with_iou only).
+    CPU tensors: IouAwareLibraryError; a mixed dtype: TypeError; a wrong level count, shape, layout or
+    a row too narrow for its maps: ValueError -- all before the device is touched."""
+    cls_ctr, reg_iou, scales = list(cls_ctr), list(reg_iou), list(scales)
+    if len(scales) != geom.L:
+        raise ValueError('point_head_loss_packed: expected %d scales, got %d' % (geom.L, len(scales)))
+    _packed_rows(geom, cls_ctr, reg_iou, bool(with_iou))
+    for s in scales:
+        _require_gpu(s, 'scale')
+        if s.numel() != 1:
+            raise ValueError('point_head_loss_packed: one scalar scale per level')
+    cfg = (float(gamma), float(alpha), int(bool(attach_iou_target)), int(bool(exact_large_logits)))
+    res = _PointHeadLossPackedFn.apply(geom, (labels, bbox_targets, counts), cfg, bool(with_iou),
+                                       *(cls_ctr + reg_iou + scales))
     losses = dict(loss_cls=res[0], loss_reg=res[1], loss_centerness=res[2])
     if with_iou:
         losses['loss_iou'] = res[3]

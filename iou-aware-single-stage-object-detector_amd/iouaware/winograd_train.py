@@ -332,17 +332,25 @@ def fcos_usable(feats, head):
             and fcos_head_supported(head, [tuple(x.shape[-2:]) for x in feats], feats[0].shape[0]))
 
 
-def _packed_outputs(convs, feat):
+def _packed_conv(convs, feat):
     """several output convolutions of one tower as one (columns padded with zero weights and bias
-    to a multiple of 4) -> per convolution the list of per-level channel slices"""
+    to a multiple of 4) -> the per-level channels-last tensors of the padded width"""
     n = [c.out_channels for c in convs]
     pad = (-sum(n)) % 4
     if len(convs) == 1 and not pad:
-        return [wino_conv_levels(feat, convs[0].weight, convs[0].bias)]
+        return wino_conv_levels(feat, convs[0].weight, convs[0].bias)
     w0, b0 = convs[0].weight, convs[0].bias
     w = torch.cat([c.weight for c in convs] + ([w0.new_zeros((pad,) + tuple(w0.shape[1:]))] if pad else []))
     b = torch.cat([c.bias for c in convs] + ([b0.new_zeros(pad)] if pad else []))
-    ys = wino_conv_levels(feat, w, b)
+    return wino_conv_levels(feat, w, b)
+
+
+def _packed_outputs(convs, feat):
+    """_packed_conv -> per convolution the list of per-level channel slices"""
+    ys = _packed_conv(convs, feat)
+    n = [c.out_channels for c in convs]
+    if len(n) == 1 and ys[0].shape[1] == n[0]:
+        return [ys]
     res, off = [], 0
     for k in n:
         res.append([t[:, off:off + k] for t in ys])
@@ -350,14 +358,9 @@ def _packed_outputs(convs, feat):
     return res
 
 
-def fcos_head_forward(head, feats):
-    """_FCOSHeadBase.forward (multi_apply(forward_single), reference fcos_head.py /
-    iou_aware_fcos_head.py) with every tower convolution one Winograd node over all levels, followed
-    by the HIP GroupNorm + ReLU node (fcos_ops.groupnorm_relu); fcos_cls | fcos_centerness are one
-    output convolution on the cls tower (81 -> 84 columns), fcos_reg | fcos_iou one on the reg tower
-    (5 -> 8; fcos_reg alone in the plain head).  bbox_pred = exp(scale_l * reg) in torch on the
-    4-channel slice.  Returns the reference's tuple (cls[L], bbox[L], centerness[L][, iou[L]]) of
-    NCHW-contiguous maps, which the fused loss node takes."""
+def _fcos_towers(head, feats):
+    """both GN towers: every convolution one Winograd node over all levels, followed by the HIP
+    GroupNorm + ReLU node -> (cls_feat[L], reg_feat[L])"""
     from .fcos_ops import groupnorm_relu
     cls_feat = reg_feat = [_cl(x) for x in feats]
     for m in head.cls_convs:
@@ -368,6 +371,29 @@ def fcos_head_forward(head, feats):
         gn = m.norm
         reg_feat = groupnorm_relu(wino_conv_levels(reg_feat, m.conv.weight, None, relu=False),
                                   gn.weight, gn.bias, gn.num_groups, gn.eps)
+    return cls_feat, reg_feat
+
+
+def fcos_head_forward_packed(head, feats):
+    """the towers and the two output convolutions of fcos_head_forward, and nothing behind them:
+    -> (cls_ctr[L], reg_iou[L]), the fp32 channels-last outputs of the padded width, rows
+    [cls | centerness | pad] (81 -> 84) and [raw fcos_reg 4 | iou? | pad] (5 -> 8; 4 in the plain head),
+    unsliced and unconverted -- what fcos_ops.point_head_loss_packed takes.  The convolution node's
+    backward takes a gradient of the padded width as it is."""
+    cls_feat, reg_feat = _fcos_towers(head, feats)
+    return (_packed_conv([head.fcos_cls, head.fcos_centerness], cls_feat),
+            _packed_conv([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []), reg_feat))
+
+
+def fcos_head_forward(head, feats):
+    """_FCOSHeadBase.forward (multi_apply(forward_single), reference fcos_head.py /
+    iou_aware_fcos_head.py) with every tower convolution one Winograd node over all levels, followed
+    by the HIP GroupNorm + ReLU node (fcos_ops.groupnorm_relu); fcos_cls | fcos_centerness are one
+    output convolution on the cls tower (81 -> 84 columns), fcos_reg | fcos_iou one on the reg tower
+    (5 -> 8; fcos_reg alone in the plain head).  bbox_pred = exp(scale_l * reg) in torch on the
+    4-channel slice.  Returns the reference's tuple (cls[L], bbox[L], centerness[L][, iou[L]]) of
+    NCHW-contiguous maps, which the fused loss node takes."""
+    cls_feat, reg_feat = _fcos_towers(head, feats)
     cls, ctr = _packed_outputs([head.fcos_cls, head.fcos_centerness], cls_feat)
     ri = _packed_outputs([head.fcos_reg] + ([head.fcos_iou] if head.iou_branch else []), reg_feat)
     cls = [t.contiguous() for t in cls]

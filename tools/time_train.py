@@ -13,6 +13,9 @@
     TRAIN_STRIDED=1     the stride-2 3x3 convolutions (conv2 of the first block of stages 2-4, P6 / P7) on
                         the im2col / col2im node (backbone.train_strided = neck.train_strided = True;
                         needs FUSE=1); 0: the framework's convolution
+    FUSE_HEAD_LOSS=1    the FCOS heads' forward + loss as one call (bbox_head.fuse_head_loss = True: on the
+                        bf16 / Winograd tower routes the packed channels-last outputs go straight into the loss
+                        node, exp(scale * x) inside it); the route is then named <route>+packed
 The result line names the head route that ran (bf16 / winograd / module) and the TRAIN_STRIDED setting.
     ITERS=n             timed iterations (default 5)"""
 import sys, os, time
@@ -46,6 +49,8 @@ if os.environ.get('TRAIN_WINOGRAD') is not None:
     model.bbox_head.train_winograd = bool(int(os.environ['TRAIN_WINOGRAD']))
 if os.environ.get('TRAIN_BF16') is not None:
     model.bbox_head.train_bf16 = bool(int(os.environ['TRAIN_BF16']))
+if os.environ.get('FUSE_HEAD_LOSS') is not None:
+    model.bbox_head.fuse_head_loss = bool(int(os.environ['FUSE_HEAD_LOSS']))
 STRIDED = bool(int(os.environ.get('TRAIN_STRIDED', '0')))
 if STRIDED:
     model.backbone.train_strided = model.neck.train_strided = True      # the backbone's is read by fuse_inference below
@@ -63,6 +68,8 @@ def _count(mod, name, tag):
 for _name in ('head_forward', 'fcos_head_forward'):
     _count(conv3x3_bf16_train, _name, 'bf16')
     _count(winograd_train, _name, 'winograd')
+_count(conv3x3_bf16_train, 'fcos_head_forward_packed', 'bf16+packed')
+_count(winograd_train, 'fcos_head_forward_packed', 'winograd+packed')
 opt = build_optimizer(model, dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001))
 img = torch.randn(B, 3, 800, 1344, device='cuda')
 if os.environ.get('FUSE'):
