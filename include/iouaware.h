@@ -607,6 +607,17 @@ typedef struct ia_head_loss_cfg {
                                                     iou slices are written, the caller clears the rest.  Nothing is
                                                     inferred from the pointers alone.  Zero-initialise
                                                     this struct: it has grown since round 4.               */
+    /* IoU-balanced losses of the IoU-aware head (IOUbalancedSigmoidFocalLoss / IoUbalancedSmoothL1Loss,
+     * core/loss/losses.py:309-374,416-458); all zero: the plain losses above.  With iou_n the (detached)
+     * IoU of anchor n's decoded prediction with its decoded target -- the IoU branch's regression target:
+     *   balanced_cls: loss_cls[l] = loss_weight_cls * (S0 + norm_l * S2) / avg_factor, S0 the focal sum over
+     *     the elements with target 0, S1 over the positive elements, S2 the same with every term times
+     *     iou_n^eta, norm_l = S1 / (S2 + 1e-6) (detached; 0 on a level without positives); the gradient of
+     *     a positive element is the focal derivative times iou_n^eta * norm_l.  eta > 0.
+     *   balanced_loc: smooth-L1 value and derivative of an anchor times iou_n^delta.  delta > 0.
+     * Either flag with IA_CLS_SIGMOID_NOIOU, or with an exponent <= 0: IA_E_ARG.                        */
+    float eta, delta;
+    int32_t balanced_cls, balanced_loc;
 } ia_head_loss_cfg;
 
 /* workspace (256-byte aligned, ia_head_loss_workspace_bytes): the fp64 partial sums and an
@@ -615,6 +626,12 @@ typedef struct ia_head_loss_cfg {
  * result: (3L + 4) fp32 = loss_cls[L] | loss_bbox[L] | losses_iou[L] | their sums over the
  * levels [3] | avg_factor -- each loss = loss_weight * (sum / avg_factor).              */
 size_t ia_head_loss_workspace_bytes(const ia_head_geom *g, int batch);
+/* The size for a given cfg: with cfg->balanced_cls two more rows of fp64 partial sums per level (S1, S2)
+ * -- for ia_head_loss_fwd; ia_head_loss_fwd_nhwc then takes 8 * 5 L * IA_LOSS_SLOTS bytes instead of
+ * 8 * 3 L * IA_LOSS_SLOTS.  A balanced forward call with less returns IA_E_ARG before anything is
+ * enqueued.  With balanced_cls the result vector is (4L + 4) fp32: the layout above, then norm_l[L],
+ * which the backward calls read from it (grad_result stays 3L + 3).                              */
+size_t ia_head_loss_workspace_bytes_cfg(const ia_head_geom *g, int batch, const ia_head_loss_cfg *cfg);
 int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
                      const ia_head_targets *t, const ia_head_loss_cfg *cfg, void *workspace,
                      size_t workspace_bytes, float *result, void *stream);

@@ -35,6 +35,13 @@
 // instances are smooth-L1 alone -- no anchor, no decode, no IoU map read, no IoU gradient written;
 // the losses_iou entries of the result are 0.  Focal kernels, packed targets and slots are shared.
 //
+// The IoU-balanced losses of the IoU-aware head (IOUbalancedSigmoidFocalLoss / IoUbalancedSmoothL1Loss,
+// core/loss/losses.py:309-374,416-458) are two more compile-time switches on the same kernels and the
+// same launches: BAL_CLS on the focal kernels (the rare positive correction goes to two slot rows of its
+// own, S1 and S2 = S1 weighted by iou^eta, and recomputes the anchor's IoU with the box kernel's code),
+// BAL_LOC on box_elem (smooth-L1 weights times iou^delta); k_headloss_finalize forms
+// norm_l = S1 / (S2 + 1e-6) and leaves it behind the plain result for the backward kernels.
+//
 // The box kernels of the two layouts (k_box_ml: NCHW planes, k_box_nhwc: pixel rows with a stride)
 // keep block location, the `live` test, loads and stores; the per-anchor math is box_elem, the
 // fp64 block reduction box_block_reduce.  Host: ml_loss_args / nhwc_loss_args validate and fill
@@ -117,6 +124,50 @@ __device__ __forceinline__ float pos_der(const Sig &g, float x)
     return -((g.q * g.q) * __builtin_fmaf(2.0f * __builtin_fmaf(kLn2, g.lg, -x), g.p, g.q));
 }
 
+// the anchor of position p of a W-wide level: base anchor + grid shift (regenerated, never stored)
+__device__ __forceinline__ void grid_anchor(const BaseAnchors &ba, int l, int an, int p, int W, int stride,
+                                            float (&anc)[4])
+{
+    const int y = p / W, x = p - y * W;
+    const float sx = (float)(x * stride), sy = (float)(y * stride);
+    const float *b4 = ba.v[l][an];
+    anc[0] = b4[0] + sx; anc[1] = b4[1] + sy; anc[2] = b4[2] + sx; anc[3] = b4[3] + sy;
+}
+
+// ---- IoU-balanced focal loss (BAL_CLS; reference core/loss/losses.py:309-374).  The positive element of
+// a positive anchor goes to two sums of its own, S1 = sum of the focal terms and S2 = the same terms
+// times iou^eta; the class row keeps S0, the negatives.  loss = S0 + norm * S2 with norm = S1 / (S2 + 1e-6)
+// formed by the finalize kernel; backward scales the positive derivative by iou^eta * norm.  iou is the
+// (detached) IoU of the anchor's decoded prediction with its decoded target, recomputed here by the
+// code the box kernel runs: positives are < 1 % of the anchors and one class chunk owns each, so
+// there is no per-anchor map and no ordering between the two kernels.
+// iou^x as k_focal of loss.hip forms it; iou = 0: log2 = -inf, exp2(-inf) = 0 for x > 0 -- no NaN
+__device__ __forceinline__ float iou_pow(float iou, float x)
+{
+    return __builtin_amdgcn_exp2f(x * __builtin_amdgcn_logf(iou));
+}
+__device__ __forceinline__ float bal_weight(const FocalBal &c, int l, int an, int p, int W, int stride,
+                                            const float (&dp)[4], const float4 tq)
+{
+    const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
+    float anc[4];
+    grid_anchor(c.ba, l, an, p, W, stride, anc);
+    return iou_pow(iou_target_elem(anc, dp, dt, c.means, c.stds).t, c.eta);
+}
+
+// S1 / S2 of one wavefront -> the level's slots in the two rows behind the three losses' (wave-uniform
+// branch: positives are rare, most wavefronts have nothing to add)
+__device__ __forceinline__ void bal_wave_sums(double *sums, int L, int l, double s1, double s2)
+{
+    if (__ballot((s1 != 0.0) | (s2 != 0.0))) {
+        const double d1 = wave_sum(s1), d2 = wave_sum(s2);
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(sums + (size_t)(kNumLoss * L + l) * IA_LOSS_SLOTS + (blockIdx.x & kSlotMask), d1);
+            atomicAdd(sums + (size_t)((kNumLoss + 1) * L + l) * IA_LOSS_SLOTS + (blockIdx.x & kSlotMask), d2);
+        }
+    }
+}
+
 template <typename T> struct MLPack;
 template <> struct MLPack<float> {
     typedef float V __attribute__((ext_vector_type(4)));
@@ -130,8 +181,8 @@ template <> struct MLPack<uint16_t> {
     }
 };
 
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
+template <typename T, bool BWD, bool BAL_CLS = false>
+__global__ void __launch_bounds__(64) k_focal_ml(typename FocalSel<BAL_CLS>::ML a)
 {
     const int lane = threadIdx.x;
     const BlockRef r = locate_block<true>(a.lv, blockIdx.x);
@@ -259,7 +310,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
     // Corrections, all rare: (1) the positive element of a positive anchor replaces its
     // negative-form contribution (the same lane wrote the negative-form gradient above, so the
     // overwrite is ordered); (2) logits above kXMax: softplus(x) = x there, the clamp gave kXMax.
-    float total = 0.0f;
+    float total = 0.0f, s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float fix = 0.0f;
@@ -267,8 +318,23 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
             const size_t e = (size_t)(lab[j] - 1) * HW + pos[j];
             const float x = load_f32<T>(cls + e);
             const Sig g = sig_parts(x);
-            if (BWD) grad[e] = pos_der(g, __builtin_fminf(x, kXMax)) * wp[j];
-            else { acc[j] -= neg_val2(g); fix = pos_val(g, __builtin_fminf(x, kXMax)) * wp[j]; }
+            float iw = 1.0f;
+            if constexpr (BAL_CLS) {
+                const T *bp = static_cast<const T *>(a.bal.reg[r.l]) + ((size_t)r.b * A + r.an) * 4 * HW + pos[j];
+                const float dp[4] = {load_f32<T>(bp), load_f32<T>(bp + (size_t)HW),
+                                     load_f32<T>(bp + (size_t)2 * HW), load_f32<T>(bp + (size_t)3 * HW)};
+                iw = bal_weight(a.bal, r.l, r.an, pos[j], a.lv.W[r.l], a.lv.stride[r.l], dp,
+                                reinterpret_cast<const float4 *>(a.bal.bt[r.l])[((size_t)r.b * HW + pos[j]) * A + r.an]);
+            }
+            if (BWD) {
+                const float d = pos_der(g, __builtin_fminf(x, kXMax)) * wp[j];
+                // norm_l = S1 / (S2 + 1e-6) of the forward call, behind the plain result entries
+                grad[e] = BAL_CLS ? d * (iw * a.tail.res[3 * a.lv.L + 4 + r.l]) : d;
+            } else {
+                acc[j] -= neg_val2(g);
+                fix = pos_val(g, __builtin_fminf(x, kXMax)) * wp[j];
+                if constexpr (BAL_CLS) { s1 += fix; s2 += fix * iw; fix = 0.0f; }
+            }
         }
         if (!BWD) total += __builtin_fmaf(acc[j] * kLn2, wn[j], fix);
     }
@@ -287,6 +353,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(FocalMLArgs a)
         const double d = wave_sum((double)total);
         if (lane == 0) atomicAdd(a.tail.sums + (size_t)(0 * a.lv.L + r.l) * IA_LOSS_SLOTS +
                                      (blockIdx.x & kSlotMask), d);
+        if constexpr (BAL_CLS) bal_wave_sums(a.tail.sums, a.lv.L, r.l, (double)s1, (double)s2);
     }
 }
 
@@ -344,6 +411,7 @@ struct BoxTail {
     float means[4], stds[4];
     float beta, lw_bbox, lw_iou;
     int32_t attach;
+    float delta;                          // BAL_LOC: smooth-L1 weights times iou^delta
 };
 
 struct BoxMLArgs {
@@ -356,24 +424,33 @@ struct BoxMLArgs {
 // One live anchor (an, position p of level l) of either layout.  Forward: its two loss terms;
 // backward: d(bbox_pred) = smooth-L1 part + the part through the attached IoU target, and
 // d(iou_pred).  xl is the IoU logit (not looked at without IOU).
-template <bool BWD, bool IOU>
+// BAL_LOC (IoU-balanced smooth-L1, reference core/loss/losses.py:416-458): the anchor's weights times
+// iou^delta, iou the (detached) IoU target this function holds anyway -- powf_pos_ on the weights like
+// k_smooth_l1 of loss.hip, so both routes round alike; IoU BCE and the gradient through the attached
+// target are unchanged.
+template <bool BWD, bool IOU, bool BAL_LOC = false>
 __device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba, int L, int l, int an, int p, int W, int stride,
                                          const float (&wv)[4], const float (&dp)[4],
                                          const float (&dt)[4], float xl, double &acc_l1,
                                          double &acc_iou, float (&g_box)[4], float &g_iou)
 {
+    static_assert(IOU || !BAL_LOC, "the IoU-balanced smooth-L1 needs the IoU branch");
     IouElem q;
     if constexpr (IOU) {
-        const int y = p / W, x = p - y * W;
-        const float sx = (float)(x * stride), sy = (float)(y * stride);
-        const float *b4 = ba.v[l][an];
-        const float anc[4] = {b4[0] + sx, b4[1] + sy, b4[2] + sx, b4[3] + sy};
+        float anc[4];
+        grid_anchor(ba, l, an, p, W, stride, anc);
         q = iou_target_elem(anc, dp, dt, c.means, c.stds);
+    }
+    float wl[4] = {wv[0], wv[1], wv[2], wv[3]};           // the smooth-L1 term's weights
+    if constexpr (BAL_LOC) {
+        const float pw = powf_pos_(q.t, c.delta);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wl[k] = wv[k] * pw;
     }
     if (!BWD) {
         float s = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], c.beta) * wv[k];
+        for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], c.beta) * wl[k];
         acc_l1 = (double)s;
         if constexpr (IOU) acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
     } else {
@@ -386,7 +463,7 @@ __device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float g = (smooth_l1_der(dp[k] - dt[k], c.beta) * wv[k]) * gs1;
+            const float g = (smooth_l1_der(dp[k] - dt[k], c.beta) * wl[k]) * gs1;
             // with the IoU term the add is unconditional (attach off: gv = 0, and x + 0.0f turns
             // -0.0f into +0.0f); the plain RetinaHead kind (smooth-L1 alone) has no add
             g_box[k] = IOU ? g + gv[k] : g;
@@ -416,7 +493,7 @@ __device__ __forceinline__ void box_block_reduce(double *sums, int L, int l, dou
     }
 }
 
-template <typename T, bool BWD, bool IOU>
+template <typename T, bool BWD, bool IOU, bool BAL_LOC = false>
 __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
 {
     const BlockRef r = locate_block<false>(a.lv, blockIdx.x);
@@ -438,8 +515,8 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
             const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[r.l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
             const float xl = IOU ? load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e) : 0.0f;
-            box_elem<BWD, IOU>(a.tail, a.ba, a.lv.L, r.l, r.an, p, W, a.lv.stride[r.l], wv, dp, dt, xl,
-                               acc_l1, acc_iou, g_box, g_iou);
+            box_elem<BWD, IOU, BAL_LOC>(a.tail, a.ba, a.lv.L, r.l, r.an, p, W, a.lv.stride[r.l], wv, dp, dt, xl,
+                                        acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
             float *go = a.tail.g_reg[r.l] + ba * 4 * HW + p;
@@ -464,9 +541,10 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
 // T: storage type of logits and gradient (float, or uint16_t = bf16 widened on load, the fp32 gradient
 // rounded to nearest even once on store); UNITW: every label weight is 1, a.lw is not read (the point
 // heads, A = 1)
-template <bool BWD, typename T, bool UNITW>
-__global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
+template <bool BWD, typename T, bool UNITW, bool BAL_CLS = false>
+__global__ void __launch_bounds__(256) k_focal_nhwc(typename FocalSel<BAL_CLS>::Nhwc a)
 {
+    static_assert(!BAL_CLS || (sizeof(T) == 4 && !UNITW), "IoU-balanced: the anchor heads' fp32 rows");
     __shared__ double red[4];
     int o = 0;
     while ((int)blockIdx.x >= a.lv.fblk_off[o + 1]) ++o;
@@ -518,7 +596,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
         lwv[u] = UNITW ? 1.0f : lwp[anchor];
         goff[u] = pix * pg + 4 * r;
     }
-    double total = 0.0;
+    double total = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int u = 0; u < kFocalU; ++u) {
         const int lab = labv[u];
@@ -547,12 +625,36 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
         }
         const int jp = lab - 1 - 4 * cq[u];                 // the positive class's slot in this quad
         if (jp >= 0 && jp < 4) {
+            float iw = 1.0f;
+            if constexpr (BAL_CLS) {
+                // the chunk's (pixel, anchor) once more (not kept across the loads above), then the
+                // anchor's deltas and target as the box kernel reads them; a clamped chunk weighs 0
+                const int rr = r0 + (int)threadIdx.x + 256 * u;
+                const int dpx = (int)(((float)rr + 0.5f) * inv_ac4);
+                const int an = (int)(((float)(rr - dpx * AC4) + 0.5f) * inv_c4);
+                const int64_t pix = pix0 + dpx;
+                iw = 0.0f;
+                if (on[u]) {
+                    const float4 d4 = *reinterpret_cast<const float4 *>(
+                        static_cast<const float *>(a.bal.reg[l]) + pix * a.bal.ps_reg[l] + 4 * an);
+                    const float dp[4] = {d4.x, d4.y, d4.z, d4.w};
+                    iw = bal_weight(a.bal, l, an, (int)(pix % HW), a.lv.W[l], a.lv.stride[l], dp,
+                                    reinterpret_cast<const float4 *>(a.bal.bt[l])[pix * A + an]);
+                    if (BWD) iw *= a.tail.res[3 * a.lv.L + 4 + l];          // norm_l of the forward call
+                }
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k == jp) {
                     Sig g; g.q = rq[k]; g.lg = lg[k]; g.p = t[k] * rq[k];
-                    if (BWD) o4[k] = pos_der(g, __builtin_fminf(x[k], kXMax)) * wp;
-                    else { acc -= neg_val2(g); fix = pos_val(g, __builtin_fminf(x[k], kXMax)) * wp; }
+                    if (BWD) {
+                        const float d = pos_der(g, __builtin_fminf(x[k], kXMax)) * wp;
+                        o4[k] = BAL_CLS ? d * iw : d;
+                    } else {
+                        acc -= neg_val2(g);
+                        fix = pos_val(g, __builtin_fminf(x[k], kXMax)) * wp;
+                        if constexpr (BAL_CLS) { s1 += (double)fix; s2 += (double)(fix * iw); fix = 0.0f; }
+                    }
                 }
         }
         if (!BWD && a.tail.big_logits) {                         // exact tail, on request (wave-uniform)
@@ -576,6 +678,7 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(FocalNhwcArgs a)
         if (threadIdx.x == 0)
             atomicAdd(a.tail.sums + (size_t)(0 * a.lv.L + l) * IA_LOSS_SLOTS + (blockIdx.x & kSlotMask),
                       (red[0] + red[1]) + (red[2] + red[3]));
+        if constexpr (BAL_CLS) bal_wave_sums(a.tail.sums, a.lv.L, l, s1, s2);
     }
 }
 
@@ -588,7 +691,7 @@ struct BoxNhwcArgs {
     int32_t g_pad[IA_MAX_LEVELS];         // bwd: zero-gradient channels behind d(iou) in the same pixel row
 };
 
-template <bool BWD, bool IOU>
+template <bool BWD, bool IOU, bool BAL_LOC = false>
 __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
 {
     int o = 0;
@@ -612,8 +715,8 @@ __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
             const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
             const float xl = IOU ? a.iou[l][pix * a.ps_iou[l] + an] : 0.0f;
-            box_elem<BWD, IOU>(a.tail, a.ba, a.lv.L, l, an, p, W, a.lv.stride[l], wv, dp, dt, xl,
-                               acc_l1, acc_iou, g_box, g_iou);
+            box_elem<BWD, IOU, BAL_LOC>(a.tail, a.ba, a.lv.L, l, an, p, W, a.lv.stride[l], wv, dp, dt, xl,
+                                        acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
             *reinterpret_cast<float4 *>(a.tail.g_reg[l] + pix * a.pg_reg[l] + 4 * an) =
@@ -642,7 +745,8 @@ struct FinArgs {
     float avg_host;
     float lw[kNumLoss];
     int32_t L, B;
-    float *res;                           // 3L + 4
+    float *res;                           // 3L + 4 (+ L: norm_l, balanced_cls)
+    int32_t bal_cls;                      // loss_cls[l] = lw * (S0 + norm_l * S2) / avg, norm_l = S1 / (S2 + 1e-6)
 };
 
 __global__ void __launch_bounds__(64) k_headloss_finalize(FinArgs a)
@@ -658,8 +762,23 @@ __global__ void __launch_bounds__(64) k_headloss_finalize(FinArgs a)
     if (i < kNumLoss * a.L) {
         double s = 0.0;
         for (int k = 0; k < IA_LOSS_SLOTS; ++k) s += a.sums[(size_t)i * IA_LOSS_SLOTS + k];
+        float sv = (float)s;
+        if (a.bal_cls && i < a.L) {
+            // iou_balanced_sigmoid_focal_loss (losses.py:363-374) in fp32 like the per-level route
+            // (ops._FocalBalancedFn): the class row is S0; a level without positives has S1 = S2 = 0,
+            // norm_l = 0 and loss = lw * S0 / avg
+            double d1 = 0.0, d2 = 0.0;
+            for (int k = 0; k < IA_LOSS_SLOTS; ++k) {
+                d1 += a.sums[(size_t)(kNumLoss * a.L + i) * IA_LOSS_SLOTS + k];
+                d2 += a.sums[(size_t)((kNumLoss + 1) * a.L + i) * IA_LOSS_SLOTS + k];
+            }
+            const float S1 = (float)d1, S2 = (float)d2;
+            const float norm = S1 / (S2 + 1e-6f);
+            sv = sv + norm * S2;
+            a.res[kNumLoss * a.L + kNumLoss + 1 + i] = norm;
+        }
         // weighted_*: sum()[None] / avg_factor, then * loss_weight (losses.py:303,411,480)
-        const float v = a.lw[i / a.L] * ((float)s / avg);
+        const float v = a.lw[i / a.L] * (sv / avg);
         s_loss[i] = v;
         a.res[i] = v;
     }
@@ -784,6 +903,9 @@ static int check_common(const ia_head_geom *g, const ia_level_ptrs *p, const ia_
     if (cfg->gamma != 2.0f || !(cfg->beta > 0.0f)) return IA_E_ARG;      // other gammas: per-level path
     const int L = g->num_levels;
     with_iou = g->cls_activation == IA_CLS_SIGMOID;
+    // the IoU-balanced losses weigh by the IoU target: the IoU-aware kind only, positive exponents
+    if ((cfg->balanced_cls || cfg->balanced_loc) && !with_iou) return IA_E_ARG;
+    if ((cfg->balanced_cls && !(cfg->eta > 0.0f)) || (cfg->balanced_loc && !(cfg->delta > 0.0f))) return IA_E_ARG;
     if (!iou_ptrs_ok(p, L, with_iou) || (bwd && !iou_ptrs_ok(grads, L, with_iou))) return IA_E_ARG;
     for (int l = 0; l < L; ++l) {
         if (!p->cls[l] || !p->reg[l] || !t->labels[l] || !t->label_weights[l] ||
@@ -826,15 +948,33 @@ static void fill_box_tail(BoxTail &b, BaseAnchors &ba, const ia_head_geom *g, co
     for (int k = 0; k < 4; ++k) { b.means[k] = g->means[k]; b.stds[k] = g->stds[k]; }
     b.beta = cfg->beta; b.lw_bbox = cfg->loss_weight_bbox; b.lw_iou = 1.0f;
     b.attach = cfg->attach_iou_target ? 1 : 0;
+    b.delta = cfg->delta;
+}
+// the balanced focal kernels' extra block; st is NULL for the NCHW kernels
+static void fill_focal_bal(FocalBal &f, const ia_head_geom *g, const ia_level_ptrs *p, const ia_head_targets *t,
+                           const ia_head_loss_cfg *cfg, const ia_level_pix_strides *st)
+{
+    memcpy(f.ba.v, g->base_anchors, sizeof(f.ba.v));
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < g->num_levels;
+        f.reg[l] = on ? p->reg[l] : nullptr; f.bt[l] = on ? t->bbox_targets[l] : nullptr;
+        f.ps_reg[l] = (on && st) ? st->reg[l] : 0;
+    }
+    for (int k = 0; k < 4; ++k) { f.means[k] = g->means[k]; f.stds[k] = g->stds[k]; }
+    f.eta = cfg->eta;
 }
 
 // the workspace of the NCHW entries: fp64 slots | packed labels (int32) | packed weights (fp32),
 // 256-byte aligned pieces; the channels-last entries use the slots alone
 struct HLWorkspace { double *sums; int32_t *lab_am; float *w_am; size_t bytes; };
-static size_t slot_bytes(int L) { return sizeof(double) * kNumLoss * (size_t)L * IA_LOSS_SLOTS; }
-static HLWorkspace carve(const HLLevels &lv, const void *workspace)
+// (balanced_cls: two more slot rows per level, S1 and S2, behind the three losses')
+static size_t slot_bytes(int L, bool bal_cls)
 {
-    const size_t slots = ((slot_bytes(lv.L) + 255) / 256) * 256;
+    return sizeof(double) * (kNumLoss + (bal_cls ? 2 : 0)) * (size_t)L * IA_LOSS_SLOTS;
+}
+static HLWorkspace carve(const HLLevels &lv, const void *workspace, bool bal_cls)
+{
+    const size_t slots = ((slot_bytes(lv.L, bal_cls) + 255) / 256) * 256;
     const size_t pk = (((size_t)lv.pack_off[lv.L] * 4 + 255) / 256) * 256;
     char *w = static_cast<char *>(const_cast<void *>(workspace));
     HLWorkspace r;
@@ -850,13 +990,14 @@ static HLWorkspace carve(const HLLevels &lv, const void *workspace)
 static int ml_loss_args(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
                         const ia_head_targets *t, const ia_head_loss_cfg *cfg, const void *workspace,
                         const float *result, bool bwd, const float *grad_result,
-                        const ia_level_ptrs *grads, FocalMLArgs &fa, BoxMLArgs &ba, HLWorkspace &ws,
+                        const ia_level_ptrs *grads, FocalMLBalArgs &fa, BoxMLArgs &ba, HLWorkspace &ws,
                         bool &with_iou)
 {
     if (!workspace || (dtype != IA_F32 && dtype != IA_BF16)) return IA_E_ARG;
     int rc = fill_levels(g, batch, fa.lv);
     if (rc || (rc = check_common(g, p, t, cfg, result, bwd, grad_result, grads, with_iou))) return rc;
-    ws = carve(fa.lv, workspace);
+    ws = carve(fa.lv, workspace, cfg->balanced_cls != 0);
+    if (cfg->balanced_cls) fill_focal_bal(fa.bal, g, p, t, cfg, nullptr);
     ba.lv = fa.lv;
     for (int l = 0; l < IA_MAX_LEVELS; ++l) {
         const bool on = l < fa.lv.L;
@@ -877,7 +1018,7 @@ static int nhwc_loss_args(const ia_head_geom *g, const ia_level_ptrs *p,
                           const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
                           const ia_head_loss_cfg *cfg, double *sums, const float *result, bool bwd,
                           const float *grad_result, const ia_level_ptrs *grads,
-                          const ia_level_pix_strides *grad_strides, FocalNhwcArgs &fa,
+                          const ia_level_pix_strides *grad_strides, FocalNhwcBalArgs &fa,
                           BoxNhwcArgs &ba, bool &with_iou)
 {
     if (!strides || (bwd && !grad_strides)) return IA_E_ARG;
@@ -886,6 +1027,7 @@ static int nhwc_loss_args(const ia_head_geom *g, const ia_level_ptrs *p,
     if ((rc = check_strides(fa.lv, strides, p, with_iou)) ||
         (bwd && (rc = check_strides(fa.lv, grad_strides, grads, with_iou))))
         return rc;
+    if (cfg->balanced_cls) fill_focal_bal(fa.bal, g, p, t, cfg, strides);
     ba.lv = fa.lv;
     fa.tail = focal_tail(cfg->alpha, cfg->loss_weight_cls, !bwd && cfg->exact_large_logits, sums, grad_result,
                          bwd ? result : nullptr);
@@ -920,7 +1062,8 @@ static int nhwc_loss_args(const ia_head_geom *g, const ia_level_ptrs *p,
 }
 
 // ------------------------------------------------------------------ host: launches
-// the instantiation switches: [dtype == IA_BF16][bwd] and [..][bwd][with_iou]
+// the instantiation switches: [dtype == IA_BF16][bwd] and [..][bwd][kind], kind = no IoU term / IoU
+// term / IoU term + balanced smooth-L1 (the balanced losses exist with the IoU term only: check_common)
 static int launch_focal_ml(int dtype, bool bwd, const FocalMLArgs &fa, hipStream_t s)
 {
     static void (*const k[2][2])(FocalMLArgs) = {{k_focal_ml<float, false>, k_focal_ml<float, true>},
@@ -929,21 +1072,44 @@ static int launch_focal_ml(int dtype, bool bwd, const FocalMLArgs &fa, hipStream
     return hip_status(hipGetLastError());
 }
 int launch_focal_ml_f32(const FocalMLArgs &fa, bool bwd, hipStream_t s) { return launch_focal_ml(IA_F32, bwd, fa, s); }
-static int launch_box_ml(int dtype, bool bwd, bool with_iou, const BoxMLArgs &ba, hipStream_t s)
+// bal_cls: the IoU-balanced instances on the whole block; else the plain ones on its plain part
+static int launch_focal_ml(int dtype, bool bwd, bool bal_cls, const FocalMLBalArgs &fa, hipStream_t s)
 {
-    static void (*const k[2][2][2])(BoxMLArgs) = {
-        {{k_box_ml<float, false, false>, k_box_ml<float, false, true>},
-         {k_box_ml<float, true, false>, k_box_ml<float, true, true>}},
-        {{k_box_ml<uint16_t, false, false>, k_box_ml<uint16_t, false, true>},
-         {k_box_ml<uint16_t, true, false>, k_box_ml<uint16_t, true, true>}}};
-    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd][with_iou], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    if (!bal_cls) return launch_focal_ml(dtype, bwd, static_cast<const FocalMLArgs &>(fa), s);
+    static void (*const k[2][2])(FocalMLBalArgs) = {
+        {k_focal_ml<float, false, true>, k_focal_ml<float, true, true>},
+        {k_focal_ml<uint16_t, false, true>, k_focal_ml<uint16_t, true, true>}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd], dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(64), 0, s, fa);
     return hip_status(hipGetLastError());
 }
-static int launch_box_nhwc(bool bwd, bool with_iou, const BoxNhwcArgs &ba, hipStream_t s)
+static int launch_focal_nhwc(bool bwd, bool bal_cls, const FocalNhwcBalArgs &fa, hipStream_t s)
 {
-    static void (*const k[2][2])(BoxNhwcArgs) = {{k_box_nhwc<false, false>, k_box_nhwc<false, true>},
-                                                 {k_box_nhwc<true, false>, k_box_nhwc<true, true>}};
-    hipLaunchKernelGGL(k[bwd][with_iou], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    const dim3 grid((unsigned)fa.lv.fblk_off[fa.lv.L]);
+    if (!bal_cls) {
+        const FocalNhwcArgs &f = fa;
+        if (bwd) hipLaunchKernelGGL((k_focal_nhwc<true, float, false>), grid, dim3(256), 0, s, f);
+        else hipLaunchKernelGGL((k_focal_nhwc<false, float, false>), grid, dim3(256), 0, s, f);
+    } else if (bwd) hipLaunchKernelGGL((k_focal_nhwc<true, float, false, true>), grid, dim3(256), 0, s, fa);
+    else hipLaunchKernelGGL((k_focal_nhwc<false, float, false, true>), grid, dim3(256), 0, s, fa);
+    return hip_status(hipGetLastError());
+}
+static int box_kind(bool with_iou, const ia_head_loss_cfg *cfg) { return with_iou ? (cfg->balanced_loc ? 2 : 1) : 0; }
+static int launch_box_ml(int dtype, bool bwd, int kind, const BoxMLArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][2][3])(BoxMLArgs) = {
+        {{k_box_ml<float, false, false>, k_box_ml<float, false, true>, k_box_ml<float, false, true, true>},
+         {k_box_ml<float, true, false>, k_box_ml<float, true, true>, k_box_ml<float, true, true, true>}},
+        {{k_box_ml<uint16_t, false, false>, k_box_ml<uint16_t, false, true>, k_box_ml<uint16_t, false, true, true>},
+         {k_box_ml<uint16_t, true, false>, k_box_ml<uint16_t, true, true>, k_box_ml<uint16_t, true, true, true>}}};
+    hipLaunchKernelGGL(k[dtype == IA_BF16][bwd][kind], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
+}
+static int launch_box_nhwc(bool bwd, int kind, const BoxNhwcArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][3])(BoxNhwcArgs) = {
+        {k_box_nhwc<false, false>, k_box_nhwc<false, true>, k_box_nhwc<false, true, true>},
+        {k_box_nhwc<true, false>, k_box_nhwc<true, true>, k_box_nhwc<true, true, true>}};
+    hipLaunchKernelGGL(k[bwd][kind], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
     return hip_status(hipGetLastError());
 }
 int launch_focal_nhwc_unit(const FocalNhwcArgs &fa, int dtype, bool bwd, hipStream_t s)
@@ -960,7 +1126,7 @@ static int launch_finalize(const double *sums, const ia_head_targets *t, const i
     FinArgs f;
     f.sums = sums; f.counts = t->counts; f.avg_dev = t->avg_factor_dev; f.avg_host = t->avg_factor;
     f.lw[0] = cfg->loss_weight_cls; f.lw[1] = cfg->loss_weight_bbox; f.lw[2] = 1.0f;
-    f.L = L; f.B = batch; f.res = result;
+    f.L = L; f.B = batch; f.res = result; f.bal_cls = cfg->balanced_cls ? 1 : 0;
     hipLaunchKernelGGL(k_headloss_finalize, dim3(1), dim3(64), 0, s, f);
     return hip_status(hipGetLastError());
 }
@@ -973,7 +1139,14 @@ size_t ia_head_loss_workspace_bytes(const ia_head_geom *g, int batch)
 {
     ia::HLLevels lv;
     if (ia::fill_levels(g, batch, lv)) return 0;
-    return ia::carve(lv, nullptr).bytes;
+    return ia::carve(lv, nullptr, false).bytes;
+}
+
+size_t ia_head_loss_workspace_bytes_cfg(const ia_head_geom *g, int batch, const ia_head_loss_cfg *cfg)
+{
+    ia::HLLevels lv;
+    if (!cfg || ia::fill_levels(g, batch, lv)) return 0;
+    return ia::carve(lv, nullptr, cfg->balanced_cls != 0).bytes;
 }
 
 int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
@@ -982,14 +1155,16 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
 {
     using namespace ia;
     if ((uintptr_t)workspace & 255u) return IA_E_ARG;
-    FocalMLArgs fa;
+    FocalMLBalArgs fa;
     BoxMLArgs ba;
     HLWorkspace ws;
     bool with_iou;
     int rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, false, nullptr, nullptr, fa, ba,
                           ws, with_iou);
     if (rc) return rc;
-    if (workspace_bytes < ws.bytes) return IA_E_WORKSPACE;
+    const bool bal_cls = cfg->balanced_cls != 0;
+    // (a balanced call is sized by ia_head_loss_workspace_bytes_cfg: the plain size is a wrong argument)
+    if (workspace_bytes < ws.bytes) return bal_cls ? IA_E_ARG : IA_E_WORKSPACE;
     if (!normaliser_ok(t)) return IA_E_ARG;              // before the first enqueue
     const int L = fa.lv.L;
     PackArgs pa;
@@ -1003,10 +1178,11 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
         pa.tile_off[l + 1] = pa.tile_off[l] + (on ? batch * ((fa.lv.H[l] * fa.lv.W[l] + 255) / 256) : 0);
     }
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(ws.sums, 0, slot_bytes(L), s);
+    hipError_t e = hipMemsetAsync(ws.sums, 0, slot_bytes(L, bal_cls), s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)pa.tile_off[L]), dim3(256), 0, s, pa);
-    if ((rc = launch_focal_ml(dtype, false, fa, s)) || (rc = launch_box_ml(dtype, false, with_iou, ba, s)))
+    if ((rc = launch_focal_ml(dtype, false, bal_cls, fa, s)) ||
+        (rc = launch_box_ml(dtype, false, box_kind(with_iou, cfg), ba, s)))
         return rc;
     return launch_finalize(ws.sums, t, cfg, L, batch, result, s);
 }
@@ -1017,7 +1193,7 @@ int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
                      void *stream)
 {
     using namespace ia;
-    FocalMLArgs fa;
+    FocalMLBalArgs fa;
     BoxMLArgs ba;
     HLWorkspace ws;
     bool with_iou;
@@ -1025,8 +1201,8 @@ int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
                           ws, with_iou);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_focal_ml(dtype, true, fa, s))) return rc;
-    return launch_box_ml(dtype, true, with_iou, ba, s);
+    if ((rc = launch_focal_ml(dtype, true, cfg->balanced_cls != 0, fa, s))) return rc;
+    return launch_box_ml(dtype, true, box_kind(with_iou, cfg), ba, s);
 }
 
 int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
@@ -1037,20 +1213,21 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     using namespace ia;
     if (!workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
     double *sums = static_cast<double *>(workspace);
-    FocalNhwcArgs fa;
+    FocalNhwcBalArgs fa;
     BoxNhwcArgs ba;
     bool with_iou;
     int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, sums, result, false, nullptr, nullptr, nullptr,
                             fa, ba, with_iou);
     if (rc) return rc;
     const int L = fa.lv.L;
-    if (workspace_bytes < slot_bytes(L)) return IA_E_WORKSPACE;
+    const bool bal_cls = cfg->balanced_cls != 0;
+    if (workspace_bytes < slot_bytes(L, bal_cls)) return bal_cls ? IA_E_ARG : IA_E_WORKSPACE;   // as ia_head_loss_fwd
     if (!normaliser_ok(t)) return IA_E_ARG;              // before the first enqueue
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(sums, 0, slot_bytes(L), s);
+    hipError_t e = hipMemsetAsync(sums, 0, slot_bytes(L, bal_cls), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_focal_nhwc<false, float, false>), dim3((unsigned)fa.lv.fblk_off[L]), dim3(256), 0, s, fa);
-    if ((rc = launch_box_nhwc(false, with_iou, ba, s))) return rc;
+    if ((rc = launch_focal_nhwc(false, bal_cls, fa, s)) || (rc = launch_box_nhwc(false, box_kind(with_iou, cfg), ba, s)))
+        return rc;
     return launch_finalize(sums, t, cfg, L, batch, result, s);
 }
 
@@ -1061,15 +1238,15 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           void *stream)
 {
     using namespace ia;
-    FocalNhwcArgs fa;
+    FocalNhwcBalArgs fa;
     BoxNhwcArgs ba;
     bool with_iou;
     int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, nullptr, result, true, grad_result, grads,
                             grad_strides, fa, ba, with_iou);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((k_focal_nhwc<true, float, false>), dim3((unsigned)fa.lv.fblk_off[fa.lv.L]), dim3(256), 0, s, fa);
-    return launch_box_nhwc(true, with_iou, ba, s);
+    if ((rc = launch_focal_nhwc(true, cfg->balanced_cls != 0, fa, s))) return rc;
+    return launch_box_nhwc(true, box_kind(with_iou, cfg), ba, s);
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@ struct HLLevels {
 
 // the scalar tail of every focal kernel's arguments (k_focal_ml, k_focal_nhwc)
 struct FocalTail {
-    double *sums;                         // fwd: [3][L][IA_LOSS_SLOTS]
+    double *sums;                         // fwd: [3][L][IA_LOSS_SLOTS] (+ [2][L][..]: S1, S2 of BAL_CLS)
     const float *gin, *res;               // bwd
     float alpha_pos, alpha_neg, loss_weight;
     int32_t big_logits;                   // evaluate the exact tail for logits > kXMax (fwd)
@@ -56,6 +56,23 @@ struct FocalNhwcArgs {
     void *grad[IA_MAX_LEVELS];
     FocalTail tail;
 };
+
+// IoU-balanced focal loss (BAL_CLS instances only): what the rare positive correction needs to
+// recompute its anchor's IoU with the code the box kernel runs -- four deltas, one float4 target,
+// the regenerated anchor.  It rides BEHIND the plain argument block, so the plain instances (and
+// the point heads' launches) keep their kernel arguments as they are.
+struct FocalBal {
+    BaseAnchors ba;
+    const void *reg[IA_MAX_LEVELS];           // NCHW: the kernel's storage type; channels-last: fp32 rows
+    const float *bt[IA_MAX_LEVELS];           // (B, N_l, 4)
+    int64_t ps_reg[IA_MAX_LEVELS];            // channels-last: pixel stride of reg (elements)
+    float means[4], stds[4];
+    float eta;
+};
+struct FocalMLBalArgs : FocalMLArgs { FocalBal bal; };
+struct FocalNhwcBalArgs : FocalNhwcArgs { FocalBal bal; };
+template <bool BAL_CLS> struct FocalSel { typedef FocalMLArgs ML; typedef FocalNhwcArgs Nhwc; };
+template <> struct FocalSel<true> { typedef FocalMLBalArgs ML; typedef FocalNhwcBalArgs Nhwc; };
 
 // forward: sums and the exact_large_logits switch, gin = res = NULL; backward: sums = NULL;
 // headloss.hip

@@ -63,7 +63,10 @@ class HeadLossCfg(C.Structure):
     _fields_ = [('gamma', C.c_float), ('alpha', C.c_float), ('loss_weight_cls', C.c_float),
                 ('beta', C.c_float), ('loss_weight_bbox', C.c_float),
                 ('attach_iou_target', C.c_int32), ('exact_large_logits', C.c_int32),
-                ('grad_rows_start_at_reg', C.c_int32)]
+                ('grad_rows_start_at_reg', C.c_int32),
+                # IoU-balanced losses (zero: the plain FocalLoss / SmoothL1Loss)
+                ('eta', C.c_float), ('delta', C.c_float),
+                ('balanced_cls', C.c_int32), ('balanced_loc', C.c_int32)]
 
 
 class PointLevelPtrs(C.Structure):
@@ -204,6 +207,7 @@ SIGNATURES = {
                                     C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _f, _f, _f, _f,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'ia_head_loss_workspace_bytes': (_sz, [_G, _i]),
+    'ia_head_loss_workspace_bytes_cfg': (_sz, [_G, _i, C.POINTER(HeadLossCfg)]),
     'ia_head_loss_fwd': (_i, [_G, _P, _i, _i, C.POINTER(HeadTargets), C.POINTER(HeadLossCfg), _vp,
                               _sz, _vp, _vp]),
     'ia_head_loss_bwd': (_i, [_G, _P, _i, _i, C.POINTER(HeadTargets), C.POINTER(HeadLossCfg), _vp,

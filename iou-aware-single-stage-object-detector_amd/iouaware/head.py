@@ -208,11 +208,16 @@ class _RetinaHeadBase(AnchorHead):
 
     # ------------------------------------------------------------------ training
     fuse_levels = True                    # all-levels loss kernels when the configuration allows
+    fuse_balanced = False                 # opt-in: the IoU-balanced losses on the all-levels node too
 
     def _fused_loss_ok(self, cls_scores):
-        from .losses import FocalLoss, SmoothL1Loss
-        return (self.fuse_levels and type(self.loss_cls) is FocalLoss
-                and type(self.loss_bbox) is SmoothL1Loss and float(self.loss_cls.gamma) == 2.0
+        from .losses import FocalLoss, SmoothL1Loss, IOUbalancedSigmoidFocalLoss, IoUbalancedSmoothL1Loss
+        cls_t, box_t = type(self.loss_cls), type(self.loss_bbox)
+        balanced = cls_t is IOUbalancedSigmoidFocalLoss or box_t is IoUbalancedSmoothL1Loss
+        if balanced and not (self.fuse_balanced and self.iou_branch):
+            return False                  # they weigh by the IoU target: `_loss_levels`
+        return (self.fuse_levels and cls_t in (FocalLoss, IOUbalancedSigmoidFocalLoss)
+                and box_t in (SmoothL1Loss, IoUbalancedSmoothL1Loss) and float(self.loss_cls.gamma) == 2.0
                 and self.use_sigmoid_cls and not self.sampling and cls_scores[0].is_cuda
                 and cls_scores[0].dtype in (torch.float32, torch.bfloat16))
 
@@ -262,7 +267,9 @@ class _RetinaHeadBase(AnchorHead):
         """loss() of both heads (iou_preds None without the IoU branch): targets, then all levels
         and all losses in one autograd node (csrc/headloss.hip: 3 + 2 kernel launches) when
         `_fused_loss_ok`, else the subclass's per-level losses (`_loss_levels`: the other loss
-        types).  None when an image has no valid anchor."""
+        types).  The IoU-balanced losses of the IoU-aware head take the node too when `fuse_balanced`
+        is set (opt-in; eta / delta travel from the loss modules), else `_loss_levels`.
+        None when an image has no valid anchor."""
         featmap_sizes = [tuple(f.shape[-2:]) for f in cls_scores]
         if len(featmap_sizes) != len(self.anchor_generators):
             raise AssertionError('level count mismatch')
@@ -281,13 +288,16 @@ class _RetinaHeadBase(AnchorHead):
                                      bbox_t, bbox_w, level_anchors, num_total_samples, gt_bboxes,
                                      cfg)
         on_dev = level_anchors[0] is None          # targets came from the HIP assigner
+        # (the balanced focal module, like the reference's, does not apply its loss_weight: losses.py)
+        eta, delta = getattr(self.loss_cls, 'eta', None), getattr(self.loss_bbox, 'delta', None)
         return ops.head_loss(
             geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
             counts=counts if on_dev else None,
             avg_factor=None if on_dev else num_total_samples,
             gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
-            loss_weight_cls=self.loss_cls.loss_weight, beta=self.loss_bbox.beta,
-            loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=self.attach_iou_target)
+            loss_weight_cls=self.loss_cls.loss_weight if eta is None else 1.0, beta=self.loss_bbox.beta,
+            loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=self.attach_iou_target,
+            eta=eta, delta=delta)
 
 
 @HEADS.register_module

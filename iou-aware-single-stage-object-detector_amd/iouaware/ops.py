@@ -1675,8 +1675,10 @@ def anchor_targets(geom, gt_bboxes, gt_labels, pad_shapes, pos_iou_thr, neg_iou_
 class LevelLosses(list):
     """per-level (1,)-shaped loss tensors, like the reference's lists, plus `.total` = their sum
     computed by the finalize kernel (differentiable): train.parse_losses adds three tensors
-    instead of reducing fifteen."""
+    instead of reducing fifteen.  `.norm`: on loss_cls of the IoU-balanced focal loss the (L,) detached
+    normalisers S1 / (S2 + 1e-6) of the levels, else None."""
     total = None
+    norm = None
 
 
 _ZERO1 = {}
@@ -1720,6 +1722,17 @@ def _head_loss_gin(gs, dev):
     return torch.cat([z if g is None else g.detach().reshape(1).to(torch.float32) for g in gs])
 
 
+def _head_loss_outputs(ctx, res, L):
+    """the 3L + 3 loss tensors of a head-loss node, views of its result vector; with the IoU-balanced
+    focal loss also norm_l (L,), the detached normalisers the finalize kernel left behind them"""
+    outs = tuple(res[:3 * L + 3].view(3 * L + 3, 1).unbind(0))
+    if res.numel() > 3 * L + 4:
+        norm = res[3 * L + 4:]
+        ctx.mark_non_differentiable(norm)
+        outs += (norm,)
+    return outs
+
+
 class _HeadLossFn(torch.autograd.Function):
     """the three losses of every level: 3 launches forward, 2 backward (csrc/headloss.hip).
     Outputs: 3L per-level (1,) tensors and 3 totals, views of one result vector.  A geometry without
@@ -1744,9 +1757,10 @@ class _HeadLossFn(torch.autograd.Function):
             p.iou[l] = iou[l].data_ptr() if iou else None
         ht, kept = _pack_head_targets(targets, L)
         hc = _lib.HeadLossCfg(*cfg)
-        res = torch.empty(3 * L + 4, dtype=torch.float32, device=dev)
+        # IoU-balanced focal loss: norm_l[L] behind the plain result, two more slot rows per level
+        res = torch.empty((4 if hc.balanced_cls else 3) * L + 4, dtype=torch.float32, device=dev)
         g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
-        nbytes = _lib.lib().ia_head_loss_workspace_bytes(g.ref(), B)
+        nbytes = _lib.lib().ia_head_loss_workspace_bytes_cfg(g.ref(), B, C.byref(hc))
         if nbytes == 0:
             raise _lib.IouAwareLibraryError('unsupported geometry / batch for ia_head_loss')
         # own buffer (not the shared inference workspace): it carries the packed targets from
@@ -1760,13 +1774,13 @@ class _HeadLossFn(torch.autograd.Function):
         ctx.keep = (cls, reg, iou, p, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
-        return tuple(res[:3 * L + 3].view(3 * L + 3, 1).unbind(0))
+        return _head_loss_outputs(ctx, res, L)
 
     @staticmethod
     def backward(ctx, *gs):
         cls, reg, iou, p, ht, _ = ctx.keep
         L, dev = ctx.geom.L, cls[0].device
-        gin = _head_loss_gin(gs, dev)
+        gin = _head_loss_gin(gs[:3 * L + 3], dev)
         gp = LevelPtrs()
         grads = [[torch.empty(t.shape, dtype=torch.float32, device=dev) for t in x]
                  for x in (cls, reg, iou)]
@@ -1854,8 +1868,9 @@ class _HeadLossNhwcFn(torch.autograd.Function):
                 p.iou[l], st.iou[l] = iou[l].data_ptr(), _pix_stride(iou[l])
         ht, kept = _pack_head_targets(targets, L)
         hc = _lib.HeadLossCfg(*cfg)
-        res = torch.empty(3 * L + 4, dtype=torch.float32, device=dev)
-        nbytes = 8 * 3 * L * _lib.IA_LOSS_SLOTS
+        # IoU-balanced focal loss: norm_l[L] behind the plain result, two more slot rows per level
+        res = torch.empty((4 if hc.balanced_cls else 3) * L + 4, dtype=torch.float32, device=dev)
+        nbytes = 8 * (5 if hc.balanced_cls else 3) * L * _lib.IA_LOSS_SLOTS
         ws = _workspace(dev, nbytes)
         _lib.check(_lib.lib().ia_head_loss_fwd_nhwc(geom.ref(), C.byref(p), C.byref(st), B,
                                                     C.byref(ht), C.byref(hc), _ptr(ws), nbytes,
@@ -1864,13 +1879,13 @@ class _HeadLossNhwcFn(torch.autograd.Function):
         ctx.keep = (cls, reg, iou, bases, p, st, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
-        return tuple(res[:3 * L + 3].view(3 * L + 3, 1).unbind(0))
+        return _head_loss_outputs(ctx, res, L)
 
     @staticmethod
     def backward(ctx, *gs):
         cls, reg, iou, bases, p, st, ht, _ = ctx.keep
         L, dev = ctx.geom.L, cls[0].device
-        gin = _head_loss_gin(gs, dev)
+        gin = _head_loss_gin(gs[:3 * L + 3], dev)
         gp, gst = LevelPtrs(), _lib.LevelPixStrides()
         cl = torch.channels_last
         g_cls = [torch.empty(t.shape, dtype=torch.float32, device=dev, memory_format=cl) for t in cls]
@@ -1932,8 +1947,11 @@ def _nhwc_route(geom, cls, reg, iou):
 def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_weights, counts=None,
               avg_factor=None, gamma=2.0, alpha=0.25, loss_weight_cls=1.0, beta=0.11,
               loss_weight_bbox=1.0, attach_iou_target=True, exact_large_logits=False,
-              channels_last=None):
+              channels_last=None, eta=None, delta=None):
     """FocalLoss(gamma=2) + SmoothL1Loss + IoU BCE of every pyramid level in one autograd node.
+    eta / delta (None: the plain loss): IOUbalancedSigmoidFocalLoss with exponent eta in place of FocalLoss,
+    IoUbalancedSmoothL1Loss with exponent delta in place of SmoothL1Loss -- both weigh by the (detached)
+    IoU target of the IoU branch, so they need a geometry with it; same node, same launches.
     iou=None with a geometry built with iou_branch=False (the plain RetinaHead): FocalLoss +
     SmoothL1Loss alone, -> dict(loss_cls, loss_bbox) (the reference's keys, anchor_head.py:299).
     channels_last: None = the channels-last kernels when every head output is channels-last(-like)
@@ -1947,9 +1965,14 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
         raise ValueError('head_loss needs counts or avg_factor')
     if float(gamma) != 2.0:
         raise ValueError('the all-levels kernel is specialised for gamma = 2')
+    if (eta is not None or delta is not None) and not geom.iou_branch:
+        raise ValueError('the IoU-balanced losses need a head with the IoU branch')
+    if (eta is not None and not float(eta) > 0.0) or (delta is not None and not float(delta) > 0.0):
+        raise ValueError('eta / delta must be positive')
     L = geom.L
     cfg = (float(gamma), float(alpha), float(loss_weight_cls), float(beta), float(loss_weight_bbox),
-           int(bool(attach_iou_target)), int(bool(exact_large_logits)))
+           int(bool(attach_iou_target)), int(bool(exact_large_logits)), 0,
+           float(eta or 0.0), float(delta or 0.0), int(eta is not None), int(delta is not None))
     targets = (list(labels), list(label_weights), list(bbox_targets), list(bbox_weights), counts,
                avg_factor)
     route = _nhwc_route(geom, cls, reg, iou) if channels_last is not False else None
@@ -1965,6 +1988,8 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
         lst = LevelLosses(flat[k * L:(k + 1) * L])
         lst.total = flat[3 * L + k]
         out[name] = lst
+    if eta is not None:
+        out['loss_cls'].norm = flat[3 * L + 3]
     return out
 
 

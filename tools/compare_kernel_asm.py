@@ -23,9 +23,12 @@ def kernels(path):
 
 
 def demangle(names):
+    """mangled -> demangled name; the parameter list is reduced to '()': kernel name and template
+    arguments identify an instance, and a parameter type that came to depend on a new template
+    parameter (k_focal_ml's argument block) must not hide the old instance's partner"""
     out = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True,
                          text=True).stdout.split('\n')
-    return dict(zip(names, out))
+    return dict(zip(names, (re.sub(r'>\(.*\)$', '>()', o) for o in out)))
 
 
 def stream(body, name):

@@ -3,12 +3,17 @@ outputs): device target assignment + the three losses of all levels forward + pa
 backward.  Prints wall per iteration (HIP events); under rocprofv3 the kernel trace is reduced by
 tools/summarize_trace.py with the marker `k_box_ml<float, true` (last kernel of an iteration).
 
-    python tools/time_headloss.py [B] [per_level | nhwc] [plain | --head {iou_aware,plain}] [--iters N]
+    python tools/time_headloss.py [B] [per_level | nhwc] [plain | balanced | --head {iou_aware,plain}] [--iters N]
 
 `plain` (or `--head plain`): the plain RetinaHead built from the same settings, the IoU maps
 dropped -- FocalLoss + SmoothL1Loss alone, on the same three routes (the all-levels node without
 the IoU term, the per-level kernels, the channels-last kernels with reg as its own tensor, as its
 training head produces it).  The focal part, and with it the algorithmic-bytes line, is shared.
+
+`balanced`: the IoU-aware head with IOUbalancedSigmoidFocalLoss(eta = 1.5) + IoUbalancedSmoothL1Loss
+(delta = 1.5), `fuse_balanced` set: the all-levels node with its IoU-balanced instances (markers
+`k_box_ml<float, true, true, true>` / `k_box_nhwc<true, true, true>`), or with `per_level` the route such
+a head takes without the switch.
 """
 import os
 import sys
@@ -36,7 +41,10 @@ if '--iters' in args:
     k = args.index('--iters')
     n = int(args[k + 1])
     del args[k:k + 2]
-args = [a for a in args if a != 'plain']
+balanced = 'balanced' in args
+if balanced and plain:
+    sys.exit('the IoU-balanced losses need the IoU-aware head')
+args = [a for a in args if a not in ('plain', 'balanced')]
 B = int(args[0]) if args else 4
 per_level = len(args) > 1 and args[1] == 'per_level'
 nhwc = len(args) > 1 and args[1] == 'nhwc'              # channels-last outputs, reg | iou as slices of one
@@ -49,8 +57,14 @@ kw.pop('type')
 if plain:
     for k in ('loss_iou', 'attach_iou_target'):
         kw.pop(k, None)
+if balanced:
+    kw['loss_cls'] = dict(type='IOUbalancedSigmoidFocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25,
+                          eta=1.5, loss_weight=1.0)
+    kw['loss_bbox'] = dict(type='IoUbalancedSmoothL1Loss', beta=kw['loss_bbox'].get('beta', 0.11), delta=1.5,
+                           loss_weight=kw['loss_bbox'].get('loss_weight', 1.0))
 head = (RetinaHead if plain else IoUawareRetinaHead)(**kw).cuda()
 head.fuse_levels = not per_level
+head.fuse_balanced = balanced
 cls, reg, iou = synth.head_outputs(3, B, 800, 1344, 'A')
 outs = [[torch.from_numpy(t).cuda().requires_grad_(True) for t in x]
         for x in ((cls, reg) if plain else (cls, reg, iou))]
@@ -99,7 +113,7 @@ e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / n
 print('B=%d %s%s: targets + losses fwd + bwd  %.3f ms per iteration' %
-      (B, 'plain RetinaHead, ' if plain else '',
+      (B, 'plain RetinaHead, ' if plain else ('IoU-balanced losses, ' if balanced else ''),
        'per-level kernels' if per_level else 'all-levels kernels', ms))
 print('focal algorithmic bytes: fwd %.1f MB, bwd %.1f MB per iteration' %
       (66931200 * B / 1e6, 131443200 * B / 1e6))
