@@ -56,7 +56,10 @@ __device__ __forceinline__ float focal_elem(float x, bool t, float at, float gam
     else {
         const float lg = __builtin_amdgcn_logf(pt);      // log2
         mod = __builtin_amdgcn_exp2f(gamma * lg);
-        dmod = gamma * __builtin_amdgcn_exp2f((gamma - 1.0f) * lg);
+        // pt is exactly 0 once exp(-|x|) flushes (|x| > 87.3): lg = -inf, and (gamma - 1) * lg is
+        // NaN for gamma = 1, +inf (times dpt = 0 below) for gamma < 1.  The term's limit is 0:
+        // pt^(gamma - 1) * dpt = -+ pt^gamma * (1 - pt).
+        dmod = (pt > 0.0f) ? gamma * __builtin_amdgcn_exp2f((gamma - 1.0f) * lg) : 0.0f;
     }
     if (!BWD) return bce * (at * mod);
     const float dbce = t ? -qr : pr;                     // p - t
