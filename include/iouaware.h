@@ -681,6 +681,34 @@ int ia_grouped_conv3x3_nhwc(const float *x, const float *wpack, const float *bia
                             int batch, int H, int W, int channels, int groups, int stride, int relu,
                             void *stream);
 
+/* Training (csrc/gconv_bwd.hip): the same layout and shapes -- channels-last fp32, x / dz / dx
+ * 16-byte aligned, 4 / 8 / 16 / 32 channels per group, channels % 16 == 0 (% 32 for 32 per group),
+ * pad 1, stride 1 or 2, H / W the INPUT size, Ho = (H - 1) / stride + 1; anything else is IA_E_ARG
+ * before the first enqueue, nothing written.  All pointers are DEVICE pointers.
+ * ia_grouped_conv3x3_pack_dev: one launch; weight (C, C/groups, 3, 3) contiguous (+ optional
+ *   per-output-channel scale) -> wpack in the layout of ia_grouped_conv3x3_pack.  adjoint = 0: the
+ *   bits of the host pack; adjoint = 1: the weight of the input-gradient convolution (taps flipped
+ *   in both directions, input and output channel swapped inside each group, scale ignored);
+ *   adjoint = 2: both in one launch, wpack twice the size -- the adjoint = 0 pack, then the
+ *   adjoint = 1 pack (the scale applies to the first only).
+ * ia_grouped_conv3x3_bwd_data_nhwc: dz (B, Ho, Wo, C) and the ADJOINT pack -> dx (B, H, W, C),
+ *   every element written; stride 1 is the forward kernel on the adjoint pack, stride 2 a gather
+ *   kernel (terms whose output row / column does not exist are masked).  No atomics.
+ * ia_grouped_conv3x3_bwd_weight_nhwc: x (B, H, W, C), dz (B, Ho, Wo, C) -> dw (C, C/groups, 3, 3)
+ *   contiguous; the reduction over the pixels is cut into slices of output rows whose partial
+ *   results go to `workspace` (ia_grouped_conv3x3_bwd_weight_workspace_bytes, 0 for a shape that
+ *   is not covered; a smaller workspace is IA_E_ARG; need not be initialised) and are added in a
+ *   fixed order: the same bits in every run.                                                  */
+int ia_grouped_conv3x3_pack_dev(const float *weight, const float *scale, int channels, int groups,
+                                int adjoint, float *wpack, void *stream);
+int ia_grouped_conv3x3_bwd_data_nhwc(const float *dz, const float *wpack_adjoint, float *dx, int batch,
+                                     int H, int W, int channels, int groups, int stride, void *stream);
+size_t ia_grouped_conv3x3_bwd_weight_workspace_bytes(int batch, int H, int W, int channels, int groups,
+                                                     int stride);
+int ia_grouped_conv3x3_bwd_weight_nhwc(const float *x, const float *dz, float *dw, void *workspace,
+                                       size_t workspace_bytes, int batch, int H, int W, int channels,
+                                       int groups, int stride, void *stream);
+
 /* The bf16 twin (csrc/gconv_bf16.hip): channels-last bf16 in and out, fp32 accumulation on
  * v_mfma_f32_16x16x32_bf16, fp32 bias (+ ReLU) in fp32, one round-to-nearest-even to bf16 at the
  * store.  A wavefront owns 32 consecutive channels: channels % 32 == 0, 4 / 8 / 16 / 32 channels

@@ -220,6 +220,10 @@ SIGNATURES = {
     'ia_grouped_conv3x3_pack': (_i, [_vp, _vp, _i, _i, _vp]),
     'ia_grouped_conv3x3_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_grouped_conv3x3_packed_bytes_bf16': (C.c_size_t, [_i, _i]),
+    'ia_grouped_conv3x3_pack_dev': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'ia_grouped_conv3x3_bwd_data_nhwc': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'ia_grouped_conv3x3_bwd_weight_workspace_bytes': (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    'ia_grouped_conv3x3_bwd_weight_nhwc': (_i, [_vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_grouped_conv3x3_pack_bf16': (_i, [_vp, _vp, _i, _i, _vp]),
     'ia_grouped_conv3x3_bf16_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_sigmoid_focal_loss_fwd': (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),

@@ -138,6 +138,10 @@ class ResNet(nn.Module):
     # on the im2col / col2im node instead of the framework's convolution -- the same bits in every
     # run.  Read by fuse_inference, like gconv_bf16.
     train_strided = False
+    # training, opt-in: the grouped 3x3 conv2 of a fused ResNeXt training block on the MFMA kernels
+    # of csrc/gconv.hip / csrc/gconv_bwd.hip (train_fuse.grouped_conv3x3_train) instead of the module
+    # route (framework convolutions + BatchNorm modules).  Read by fuse_inference, like train_strided.
+    train_gconv = False
 
     def __init__(self, depth, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
                  out_indices=(0, 1, 2, 3), style='pytorch', frozen_stages=-1, conv_cfg=None,

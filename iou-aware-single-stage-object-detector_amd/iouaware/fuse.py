@@ -656,12 +656,14 @@ def fuse_inference(model, winograd=False, train=False):
                 fpn_convs.update(id(c) for c in m.fpn_convs)
     # the backbone's `gconv_bf16` switch (bf16 ResNeXt: grouped conv2 on csrc/gconv_bf16.hip) is read
     # here for its bottlenecks; a bottleneck fused on its own takes the class default
-    # (`train_strided`, the training route's stride-2 conv2 on the im2col / col2im node, likewise)
-    gconv_bf16, train_strided = {}, {}
+    # (`train_strided`, the training route's stride-2 conv2 on the im2col / col2im node, and
+    # `train_gconv`, the ResNeXt training route on csrc/gconv_bwd.hip, likewise)
+    gconv_bf16, train_strided, train_gconv = {}, {}, {}
     for m in model.modules():
         if isinstance(m, ResNet):
             gconv_bf16.update((id(b), bool(m.gconv_bf16)) for b in m.modules() if isinstance(b, Bottleneck))
             train_strided.update((id(b), bool(m.train_strided)) for b in m.modules() if isinstance(b, Bottleneck))
+            train_gconv.update((id(b), bool(m.train_gconv)) for b in m.modules() if isinstance(b, Bottleneck))
     for m in model.modules():
         fwd = _forward_for(m, winograd)
         if fwd is None:
@@ -670,6 +672,7 @@ def fuse_inference(model, winograd=False, train=False):
         if isinstance(m, Bottleneck):
             m._ia_gconv_bf16 = gconv_bf16.get(id(m), bool(ResNet.gconv_bf16))
             m._ia_train_strided = train_strided.get(id(m), bool(ResNet.train_strided))
+            m._ia_train_gconv = train_gconv.get(id(m), bool(ResNet.train_gconv))
         if not _fold(m):
             del m._ia_opts
             continue
@@ -704,7 +707,7 @@ def unfuse_inference(model):
             del m._ia_layer
             m.__dict__.pop('forward', None)
         for attr in ('_ia_fused', '_ia_wino', '_ia_c3', '_ia_opts', '_ia_stamp', '_ia_dirty', '_ia_stamp_slots',
-                     '_ia_gconv_bf16', '_ia_train_strided'):
+                     '_ia_gconv_bf16', '_ia_train_strided', '_ia_train_gconv'):
             if hasattr(m, attr):
                 delattr(m, attr)
                 for name in ('forward', '_stem', '_stages'):

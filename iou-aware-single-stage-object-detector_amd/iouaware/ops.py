@@ -1335,6 +1335,101 @@ def grouped_conv3x3(x, wpack, bias, groups, stride=1, relu=False):
     return y
 
 
+def _grouped_shape(Cn, groups, what):
+    cg = Cn // groups if groups > 0 and Cn % groups == 0 else 0
+    if cg not in (4, 8, 16, 32) or Cn % (32 if cg == 32 else 16):
+        raise ValueError('%s covers 4 / 8 / 16 / 32 channels per group and a channel count that '
+                         'is a multiple of 16 (32 for 32 per group)' % what)
+    return cg
+
+
+def pack_grouped_weight_dev(weight, scale=None, adjoint=False):
+    """pack_grouped_weight on the device, one launch, no host round trip (training: the weight
+    changes every iteration).  weight (C, C/groups, 3, 3) fp32 contiguous on the GPU.
+    adjoint=False: the bits of pack_grouped_weight(weight, scale); adjoint=True: the operand of the
+    input-gradient convolution (taps flipped, input / output channel swapped inside each group; no
+    scale) for grouped_conv3x3_bwd_data (csrc/gconv_bwd.hip); adjoint='both': (plain, adjoint) from
+    ONE launch, two views of one buffer (the scale applies to the plain pack only)"""
+    _require_gpu(weight, 'weight')
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) \
+            or not weight.is_contiguous():
+        raise ValueError('pack_grouped_weight_dev needs a contiguous fp32 (C, C/groups, 3, 3) weight')
+    Cn, cg = int(weight.shape[0]), int(weight.shape[1])
+    if cg < 1 or Cn % cg:
+        raise ValueError('pack_grouped_weight_dev: C is not a multiple of C/groups')
+    groups = Cn // cg
+    _grouped_shape(Cn, groups, 'pack_grouped_weight_dev')
+    if adjoint is True and scale is not None:
+        raise ValueError('pack_grouped_weight_dev: the adjoint pack takes no scale')
+    if scale is not None and (not scale.is_cuda or scale.dtype != torch.float32 or scale.numel() != Cn
+                              or not scale.is_contiguous()):
+        raise ValueError('pack_grouped_weight_dev needs a contiguous fp32 scale of C values on the GPU')
+    nb = 2 if cg == 32 else 1
+    n = Cn // (16 * nb) * 9 * nb * 4 * nb * 64
+    both = isinstance(adjoint, str) and adjoint == 'both'
+    out = torch.empty(2 * n if both else n, dtype=torch.float32, device=weight.device)
+    _lib.check(_lib.lib().ia_grouped_conv3x3_pack_dev(_ptr(weight), _ptr(scale), Cn, groups,
+                                                      2 if both else int(bool(adjoint)), _ptr(out), _stream()),
+               'ia_grouped_conv3x3_pack_dev')
+    return (out[:n], out[n:]) if both else out
+
+
+def grouped_conv3x3_bwd_data(dz, wpack_adjoint, groups, stride, in_hw):
+    """input gradient of grouped_conv3x3: channels-last fp32 dz (B, C, Ho, Wo), the adjoint pack of
+    the weight (pack_grouped_weight_dev(w, adjoint=True)) -> channels-last dx (B, C, H, W),
+    in_hw = (H, W) the input size.  Every element is written; no atomics."""
+    _require_gpu(dz, 'dz')
+    if dz.dtype != torch.float32 or dz.dim() != 4 or not dz.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('grouped_conv3x3_bwd_data needs a channels-last fp32 tensor')
+    B, Cn, Ho, Wo = dz.shape
+    H, W = int(in_hw[0]), int(in_hw[1])
+    stride = int(stride)
+    cg = _grouped_shape(Cn, int(groups), 'grouped_conv3x3_bwd_data')
+    if stride not in (1, 2) or H < 1 or W < 1 or ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo):
+        raise ValueError('grouped_conv3x3_bwd_data: dz is not the output of a stride-%d convolution '
+                         'of a %d x %d map' % (stride, H, W))
+    nb = 2 if cg == 32 else 1
+    if not wpack_adjoint.is_cuda or wpack_adjoint.dtype != torch.float32 or not wpack_adjoint.is_contiguous() \
+            or wpack_adjoint.numel() != Cn // (16 * nb) * 9 * nb * 4 * nb * 64:
+        raise ValueError('grouped_conv3x3_bwd_data: wpack_adjoint is not a pack of a %d-channel, '
+                         '%d-group weight' % (Cn, groups))
+    dx = torch.empty((B, Cn, H, W), dtype=torch.float32, device=dz.device,
+                     memory_format=torch.channels_last)
+    _lib.check(_lib.lib().ia_grouped_conv3x3_bwd_data_nhwc(_ptr(dz), _ptr(wpack_adjoint), _ptr(dx), B, H, W,
+                                                           Cn, int(groups), stride, _stream()),
+               'ia_grouped_conv3x3_bwd_data_nhwc')
+    return dx
+
+
+def grouped_conv3x3_bwd_weight(x, dz, groups, stride, workspace=None):
+    """weight gradient of grouped_conv3x3: channels-last fp32 x (B, C, H, W) and dz (B, C, Ho, Wo)
+    -> (C, C/groups, 3, 3) contiguous.  The pixel reduction is cut into slices of output rows added
+    in a fixed order (the same bits in every run); `workspace`: a uint8 tensor for the partial
+    results (default: this stream's workspace), its contents do not matter."""
+    _require_gpu(x, 'x')
+    _require_gpu(dz, 'dz')
+    cl = torch.channels_last
+    if x.dtype != torch.float32 or dz.dtype != torch.float32 or x.dim() != 4 or dz.dim() != 4 \
+            or not x.is_contiguous(memory_format=cl) or not dz.is_contiguous(memory_format=cl):
+        raise ValueError('grouped_conv3x3_bwd_weight needs channels-last fp32 tensors')
+    B, Cn, H, W = x.shape
+    stride = int(stride)
+    cg = _grouped_shape(Cn, int(groups), 'grouped_conv3x3_bwd_weight')
+    if stride not in (1, 2) or tuple(dz.shape) != (B, Cn, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError('grouped_conv3x3_bwd_weight: dz is not the output gradient of a stride-%d '
+                         'convolution of x' % stride)
+    nbytes = int(_lib.lib().ia_grouped_conv3x3_bwd_weight_workspace_bytes(B, H, W, Cn, int(groups), stride))
+    ws = _workspace(x.device, nbytes) if workspace is None else workspace
+    if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise ValueError('grouped_conv3x3_bwd_weight: the workspace is a contiguous uint8 tensor on the GPU')
+    dw = torch.empty((Cn, cg, 3, 3), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().ia_grouped_conv3x3_bwd_weight_nhwc(_ptr(x), _ptr(dz), _ptr(dw), _ptr(ws),
+                                                             int(ws.numel()), B, H, W, Cn, int(groups),
+                                                             stride, _stream()),
+               'ia_grouped_conv3x3_bwd_weight_nhwc')
+    return dw
+
+
 def pack_grouped_weight_bf16(weight, scale=None):
     """(C, C/groups, 3, 3) grouped conv weight (+ per-output-channel scale, folded in fp32 and rounded
     to bf16 once) -> the per-lane MFMA operand layout of csrc/gconv_bf16.hip as a flat bf16 tensor on

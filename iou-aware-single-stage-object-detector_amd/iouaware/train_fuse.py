@@ -26,6 +26,11 @@ channels-last activation:
                    `Conv3x3Strided`: im2col + GEMM forward (ops.conv3x3_im2col, the inference
                    kernels), dx = col2im(g . w_kn^T), dw = g^T . col with col recomputed --
                    fixed reduction orders, the same bits in every run
+    3x3, grouped   (ResNeXt) the block runs its module forward; with `ResNet.train_gconv` set
+                   (opt-in) `GroupedConv3x3`: the MFMA kernel of csrc/gconv.hip forward on a
+                   weight packed on the device, csrc/gconv_bwd.hip for the input gradient
+                   (stride 1: the forward kernel on the adjoint pack; stride 2: a gather kernel)
+                   and the weight gradient (row slices added in a fixed order)
 
 The fold `w * s`, `beta - mean * s` is one more autograd node on the parameters (`FoldBN`, one
 kernel forward, one backward), which carries d(w*s), db back to w, gamma and beta; nothing of
@@ -227,6 +232,63 @@ def conv3x3_strided(x, weight, bias=None, stride=2, relu=False):
     return Conv3x3Strided.apply(x, weight, bias, stride, relu)
 
 
+# ------------------------------------------------------------------ grouped 3x3 convolution (ResNeXt)
+class GroupedConv3x3(torch.autograd.Function):
+    """relu?( grouped conv3x3(x, weight, stride, pad 1) + bias ) on a channels-last fp32 activation:
+    the MFMA kernel of csrc/gconv.hip forward, csrc/gconv_bwd.hip backward.  The weight is packed on
+    the device in every call (one launch; it changes every iteration), the adjoint pack for the
+    input gradient by the same launch where the input wants a gradient (kept for backward instead
+    of the weight).  No atomics anywhere: the same bits in every run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, stride, relu):
+        x = _cl(x)
+        w = weight.detach().contiguous()
+        wadj = None
+        if ctx.needs_input_grad[0]:
+            wp, wadj = ops.pack_grouped_weight_dev(w, adjoint='both')
+        else:            # the first trainable block behind a frozen stage
+            wp = ops.pack_grouped_weight_dev(w)
+        y = ops.grouped_conv3x3(x, wp, None if bias is None else bias.detach().contiguous(), groups,
+                                stride, relu)
+        ctx.groups, ctx.stride, ctx.relu, ctx.hw = int(groups), int(stride), bool(relu), tuple(x.shape[-2:])
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None,
+                              wadj, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wadj, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g, db = WT.relu_bwd_bias_grad(dy, y if ctx.relu else None, bias_grad=need_b)
+        dx = dw = None
+        if need_x:       # not for the first trainable block behind a frozen stage
+            dx = ops.grouped_conv3x3_bwd_data(g, wadj, ctx.groups, ctx.stride, ctx.hw)
+        if need_w:
+            dw = ops.grouped_conv3x3_bwd_weight(x, g, ctx.groups, ctx.stride)
+        return dx, dw, db, None, None, None
+
+
+def grouped_conv_ok(conv):
+    """the module side of grouped_conv3x3_train: a grouped 3x3 / pad 1 / dilation 1 nn.Conv2d
+    without bias, stride 1 or 2, as many outputs as inputs, 4 / 8 / 16 / 32 channels per group and a
+    channel count the supergroups divide"""
+    if not (type(conv) is torch.nn.Conv2d and conv.groups > 1 and tuple(conv.kernel_size) == (3, 3)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.bias is None
+            and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2)
+            and conv.in_channels == conv.out_channels and conv.padding_mode == 'zeros'
+            and conv.weight.dtype == torch.float32):
+        return False
+    cg = conv.in_channels // conv.groups
+    return cg in (4, 8, 16, 32) and conv.in_channels % (32 if cg == 32 else 16) == 0
+
+
+def grouped_conv3x3_train(x, w, shift, groups, stride=1, relu=False):
+    """x (B, C, H, W) fp32 CUDA; w (C, C/groups, 3, 3) and shift (C) a parameter pair or FoldBN's
+    output -> channels-last (B, C, Ho, Wo)"""
+    return GroupedConv3x3.apply(x, w, shift, groups, stride, relu)
+
+
 # ------------------------------------------------------------------ eval-mode BatchNorm fold
 def _inv_std(bn):
     key = (bn.running_var.data_ptr(), bn.running_var._version)
@@ -344,7 +406,8 @@ def bottleneck_usable(m, x):
             and _eval_bn(m.norm1) and _eval_bn(m.norm2) and _eval_bn(m.norm3)
             and _gemm_ok(m.conv1) and _gemm_ok(m.conv3)
             and tuple(c2.kernel_size) == (3, 3) and tuple(c2.padding) == (1, 1)
-            and tuple(c2.dilation) == (1, 1) and c2.groups == 1 and c2.bias is None
+            and tuple(c2.dilation) == (1, 1) and c2.bias is None
+            and (c2.groups == 1 or (getattr(m, '_ia_train_gconv', False) and grouped_conv_ok(c2)))
             and c2.stride[0] == c2.stride[1] and c2.stride[0] in (1, 2)
             and c2.in_channels % 4 == 0 and c2.out_channels % 4 == 0
             and (m.downsample is None or (_gemm_ok(m.downsample[0], (1, 2))
@@ -361,7 +424,9 @@ def bottleneck_forward(m, x):
         out, x = conv1x1_fork(x, _nk(w1), b1, True)     # x: the identity branch from here on
     else:
         out = conv1x1(x, _nk(w1), b1, None, True)
-    if m.conv2.stride[0] == 1:
+    if m.conv2.groups > 1:       # ResNeXt with `train_gconv` (bottleneck_usable has checked the shape)
+        out = grouped_conv3x3_train(out, w2, b2, m.conv2.groups, m.conv2.stride[0], True)
+    elif m.conv2.stride[0] == 1:
         out = WT.wino_conv_levels([out], w2, b2, relu=True)[0]
     elif getattr(m, '_ia_train_strided', False) and strided_conv_ok(m.conv2):
         out = conv3x3_strided(out, w2, b2, m.conv2.stride[0], True)

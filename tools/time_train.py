@@ -16,7 +16,12 @@
     FUSE_HEAD_LOSS=1    the FCOS heads' forward + loss as one call (bbox_head.fuse_head_loss = True: on the
                         bf16 / Winograd tower routes the packed channels-last outputs go straight into the loss
                         node, exp(scale * x) inside it); the route is then named <route>+packed
-The result line names the head route that ran (bf16 / winograd / module) and the TRAIN_STRIDED setting.
+    BACKBONE=x101-32x4d|x101-64x4d   (MODEL=retina) the ResNeXt-101 backbones of the reference's
+                        iou_aware_retinanet_x101_*_fpn_1x configs instead of R-50
+    TRAIN_GCONV=1       the grouped 3x3 conv2 of the ResNeXt blocks on csrc/gconv.hip / csrc/gconv_bwd.hip
+                        (backbone.train_gconv = True; needs FUSE=1); 0: the blocks' module route
+The result line names the head route that ran (bf16 / winograd / module), the TRAIN_STRIDED setting and
+the TRAIN_GCONV setting with the calls of the grouped node per iteration (the route that ran).
     ITERS=n             timed iterations (default 5)"""
 import sys, os, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -31,8 +36,16 @@ TRAIN_CFG = ConfigDict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg
                                      ignore_iof_thr=-1), allowed_border=-1, pos_weight=-1, debug=False)
 torch.manual_seed(0)
 MODEL = os.environ.get('MODEL', 'retina')
+BACKBONE = os.environ.get('BACKBONE', '')
 if MODEL == 'retina':
-    model = iouaware.build_detector(ConfigDict(bench.MODEL), train_cfg=TRAIN_CFG, test_cfg=ConfigDict(bench.TEST_CFG)).cuda().train()
+    MODEL_CFG = dict(bench.MODEL)
+    if BACKBONE:
+        if BACKBONE not in ('x101-32x4d', 'x101-64x4d'):
+            sys.exit('BACKBONE=%s: x101-32x4d or x101-64x4d (unset: R-50)' % BACKBONE)
+        groups, base_width = dict([('x101-32x4d', (32, 4)), ('x101-64x4d', (64, 4))])[BACKBONE]
+        MODEL_CFG['backbone'] = dict(type='ResNeXt', depth=101, groups=groups, base_width=base_width, num_stages=4,
+                                     out_indices=(0, 1, 2, 3), frozen_stages=1, style='pytorch')
+    model = iouaware.build_detector(ConfigDict(MODEL_CFG), train_cfg=TRAIN_CFG, test_cfg=ConfigDict(bench.TEST_CFG)).cuda().train()
 else:
     TRAIN_CFG = ConfigDict(gamma=2.0, alpha=0.25)
     if os.environ.get('CONFIG'):
@@ -54,6 +67,11 @@ if os.environ.get('FUSE_HEAD_LOSS') is not None:
 STRIDED = bool(int(os.environ.get('TRAIN_STRIDED', '0')))
 if STRIDED:
     model.backbone.train_strided = model.neck.train_strided = True      # the backbone's is read by fuse_inference below
+GCONV = bool(int(os.environ.get('TRAIN_GCONV', '0')))
+if GCONV:
+    if not os.environ.get('FUSE'):
+        sys.exit('TRAIN_GCONV=1 needs FUSE=1: the switch is read by fuse_inference')
+    model.backbone.train_gconv = True                                   # read by fuse_inference below
 print('model %s  head %s  train_winograd %s  train_bf16 %s' % (MODEL, type(model.bbox_head).__name__, model.bbox_head.train_winograd,
                                                                getattr(model.bbox_head, 'train_bf16', False)))
 # which head route runs: count the calls of the route functions
@@ -70,6 +88,13 @@ for _name in ('head_forward', 'fcos_head_forward'):
     _count(winograd_train, _name, 'winograd')
 _count(conv3x3_bf16_train, 'fcos_head_forward_packed', 'bf16+packed')
 _count(winograd_train, 'fcos_head_forward_packed', 'winograd+packed')
+from iouaware import train_fuse
+GCONV_CALLS = []
+_real_gconv = train_fuse.grouped_conv3x3_train
+def _gconv_spy(*a, **k):
+    GCONV_CALLS.append(1)
+    return _real_gconv(*a, **k)
+train_fuse.grouped_conv3x3_train = _gconv_spy
 opt = build_optimizer(model, dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001))
 img = torch.randn(B, 3, 800, 1344, device='cuda')
 if os.environ.get('FUSE'):
@@ -83,11 +108,11 @@ gtb = [torch.from_numpy(x).cuda() for x in gts]; gtl = [torch.from_numpy(x).cuda
 metas = [synth.img_meta(800, 1333, 800, 1344) for _ in range(B)]
 for _ in range(3): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats(); t = time.time(); n = int(os.environ.get('ITERS', 5))
-del ROUTE[:]
+del ROUTE[:]; del GCONV_CALLS[:]
 for _ in range(n): lv = train_step(model, opt, img, metas, gtb, gtl, grad_clip=dict(max_norm=35, norm_type=2))
 torch.cuda.synchronize(); dt = (time.time() - t) / n
 route = '+'.join(sorted(set(ROUTE))) if ROUTE else 'module'
-print('B=%d  head route %s  train_strided %d  %.1f ms/iter  %.1f img/s  loss %s  mem %.2f GB' % (B, route, STRIDED, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
+print('B=%d  backbone %s  head route %s  train_strided %d  train_gconv %d (%d node calls per iteration)  %.1f ms/iter  %.1f img/s  loss %s  mem %.2f GB' % (B, BACKBONE or 'r50', route, STRIDED, GCONV, len(GCONV_CALLS) // n, dt * 1e3, B / dt, {k: round(v, 4) for k, v in lv.items()}, torch.cuda.max_memory_allocated() / 1e9))
 if os.environ.get('TRAIN_ONLY'):
     sys.exit(0)
 # loss part alone (targets + 3 losses fwd + bwd) on fixed head outputs
