@@ -502,6 +502,19 @@ int ia_smooth_l1_bwd(const void *pred, int dtype, const float *target, const flo
                      int B, int A, int HW, float beta, float gscale, const float *gscale_dev,
                      float *grad_pred, void *stream);
 
+/* BalancedL1Loss -> weighted_balanced_l1_loss (losses.py:482-520), same tensors, slots and gscale as the
+ * smooth-L1 pair.  With d = |pred - target| and b = e^(gamma / alpha) - 1 (formed in double, rounded once):
+ * d < beta: alpha / b * (b d + 1) * log(b d / beta + 1) - alpha d, else gamma d + gamma / b - alpha beta;
+ * the gradient is that of this expression (0 at pred == target, the linear branch at d == beta, a jump
+ * at the knee for beta != 1).  A gradient is written for every element, exactly 0 where the weight is 0.
+ * alpha, gamma or beta not > 0: IA_E_ARG.                                                             */
+int ia_balanced_l1_fwd(const void *pred, int dtype, const float *target, const float *weight,
+                       int B, int A, int HW, float beta, float alpha, float gamma, double *loss_sum,
+                       void *stream);
+int ia_balanced_l1_bwd(const void *pred, int dtype, const float *target, const float *weight,
+                       int B, int A, int HW, float beta, float alpha, float gamma, float gscale,
+                       const float *gscale_dev, float *grad_pred, void *stream);
+
 /* The IoU-balanced variants (loss_cls.type='IOUbalancedSigmoidFocalLoss', losses.py:309-374;
  * loss_bbox.type='IoUbalancedSmoothL1Loss', losses.py:416-458; anchor_head.py:83-84).
  * anchor_iou (B*N_l): the IoU regression target of the level (ia_iou_bce_fwd's iou_target),
@@ -667,6 +680,43 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           const ia_head_loss_cfg *cfg, const float *result, const float *grad_result,
                           const ia_level_ptrs *grads, const ia_level_pix_strides *grad_strides,
                           void *stream);
+
+/* The localisation loss of the four entries above as a choice: ia_head_loss_cfg keeps its layout, the choice
+ * travels in a struct of its own.  kind IA_BOX_SMOOTH_L1: SmoothL1Loss (cfg->beta), alpha / gamma not looked at;
+ * IA_BOX_BALANCED_L1: BalancedL1Loss (losses.py:482-520; ia_balanced_l1_fwd) with knee cfg->beta, weight
+ * cfg->loss_weight_bbox and the alpha / gamma given here -- on every layout and dtype of the entries above, with
+ * or without the IoU term (with it d(bbox_pred) = the BalancedL1 gradient + the gradient through the attached
+ * IoU target, as for smooth-L1).  Focal kernels, slots, result layout and workspace size are those of the
+ * entries above, which call these with box = NULL.  Contract:
+ *   box == NULL or kind IA_BOX_SMOOTH_L1: the bits of the entry above;
+ *   IA_E_ARG before anything is enqueued for: struct_size != sizeof(ia_box_loss_cfg); an unknown kind;
+ *   IA_BOX_BALANCED_L1 together with cfg->balanced_loc (the IoU-balanced weighting belongs to smooth-L1);
+ *   IA_BOX_BALANCED_L1 with alpha, gamma or cfg->beta not > 0.
+ *   IA_BOX_BALANCED_L1 with cfg->balanced_cls is allowed (the focal kernels do not depend on the choice).
+ * The backward call takes the struct the forward call took.                                             */
+#define IA_BOX_SMOOTH_L1 0
+#define IA_BOX_BALANCED_L1 1
+typedef struct ia_box_loss_cfg {
+    int32_t struct_size;                         /* sizeof(ia_box_loss_cfg)                           */
+    int32_t kind;                                /* IA_BOX_*                                          */
+    float alpha, gamma;                          /* BalancedL1Loss(alpha, gamma)                      */
+} ia_box_loss_cfg;
+int ia_head_loss_fwd_box(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                         const ia_head_targets *t, const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box,
+                         void *workspace, size_t workspace_bytes, float *result, void *stream);
+int ia_head_loss_bwd_box(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                         const ia_head_targets *t, const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box,
+                         const void *workspace, const float *result, const float *grad_result,
+                         const ia_level_ptrs *grads, void *stream);
+int ia_head_loss_fwd_nhwc_box(const ia_head_geom *g, const ia_level_ptrs *p,
+                              const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
+                              const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box, void *workspace,
+                              size_t workspace_bytes, float *result, void *stream);
+int ia_head_loss_bwd_nhwc_box(const ia_head_geom *g, const ia_level_ptrs *p,
+                              const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
+                              const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box, const float *result,
+                              const float *grad_result, const ia_level_ptrs *grads,
+                              const ia_level_pix_strides *grad_strides, void *stream);
 
 /* ------------------------------------------------------------------ ResNeXt grouped 3x3 convolution
  * conv2 of the ResNeXt bottleneck (mmdet/models/backbones/resnext.py:12-91: groups = 32 / 64,

@@ -42,11 +42,17 @@
 // BAL_LOC on box_elem (smooth-L1 weights times iou^delta); k_headloss_finalize forms
 // norm_l = S1 / (S2 + 1e-6) and leaves it behind the plain result for the backward kernels.
 //
+// BalancedL1Loss (core/loss/losses.py:482-520) in place of smooth-L1 is the box kernels' last template
+// parameter, LOC (0 smooth-L1, 1 balanced L1: balanced_l1_val / _der of ia_loss.hpp), with or without the IoU
+// term; its constants ride behind the smooth-L1 argument blocks (BoxSel), so every LOC = 0 instance keeps
+// its kernel arguments and its code.  Focal kernels, packed targets, slots, finalize and workspace are shared.
+//
 // The box kernels of the two layouts (k_box_ml: NCHW planes, k_box_nhwc: pixel rows with a stride)
 // keep block location, the `live` test, loads and stores; the per-anchor math is box_elem, the
 // fp64 block reduction box_block_reduce.  Host: ml_loss_args / nhwc_loss_args validate and fill
 // for forward and backward alike (backward = forward + gradient pointers); carve() alone knows
 // the workspace layout; a forward call is refused before its first enqueue.
+#include <stddef.h>
 #include <string.h>
 #include "ia_loss.hpp"
 #include "ia_headloss.hpp"
@@ -420,6 +426,19 @@ struct BoxMLArgs {
     const void *reg[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
     BoxTail tail;
 };
+// LOC = 1: the balanced-L1 constants BEHIND the block of either layout (as FocalBal rides behind the focal
+// blocks); loc_consts hands them to box_elem, nothing for LOC = 0
+struct BoxMLBl1Args : BoxMLArgs { BalL1 bl; };
+struct BoxNhwcArgs;
+struct BoxNhwcBl1Args;
+template <int LOC> struct BoxSel { typedef BoxMLArgs ML; typedef BoxNhwcArgs Nhwc; };
+template <> struct BoxSel<1> { typedef BoxMLBl1Args ML; typedef BoxNhwcBl1Args Nhwc; };
+template <int LOC, class Args>
+__device__ __forceinline__ BalL1 loc_consts(const Args &a)
+{
+    if constexpr (LOC == 1) return a.bl;
+    else return BalL1();
+}
 
 // One live anchor (an, position p of level l) of either layout.  Forward: its two loss terms;
 // backward: d(bbox_pred) = smooth-L1 part + the part through the attached IoU target, and
@@ -428,13 +447,17 @@ struct BoxMLArgs {
 // iou^delta, iou the (detached) IoU target this function holds anyway -- powf_pos_ on the weights like
 // k_smooth_l1 of loss.hip, so both routes round alike; IoU BCE and the gradient through the attached
 // target are unchanged.
-template <bool BWD, bool IOU, bool BAL_LOC = false>
-__device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba, int L, int l, int an, int p, int W, int stride,
+// LOC: the localisation loss of a coordinate -- 0 smooth-L1, 1 balanced L1 (constants bl, c.beta its knee).
+template <bool BWD, bool IOU, bool BAL_LOC = false, int LOC = 0>
+__device__ __forceinline__ void box_elem(const BoxTail &c, const BalL1 &bl, const BaseAnchors &ba, int L, int l, int an, int p, int W, int stride,
                                          const float (&wv)[4], const float (&dp)[4],
                                          const float (&dt)[4], float xl, double &acc_l1,
                                          double &acc_iou, float (&g_box)[4], float &g_iou)
 {
     static_assert(IOU || !BAL_LOC, "the IoU-balanced smooth-L1 needs the IoU branch");
+    static_assert(LOC == 0 || (LOC == 1 && !BAL_LOC), "balanced L1 has no IoU-balanced variant");
+    auto loc_val = [&](float df) { if constexpr (LOC == 1) return balanced_l1_val(df, c.beta, bl); else return smooth_l1_val(df, c.beta); };
+    auto loc_der = [&](float df) { if constexpr (LOC == 1) return balanced_l1_der(df, c.beta, bl); else return smooth_l1_der(df, c.beta); };
     IouElem q;
     if constexpr (IOU) {
         float anc[4];
@@ -450,7 +473,7 @@ __device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba
     if (!BWD) {
         float s = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) s += smooth_l1_val(dp[k] - dt[k], c.beta) * wl[k];
+        for (int k = 0; k < 4; ++k) s += loc_val(dp[k] - dt[k]) * wl[k];
         acc_l1 = (double)s;
         if constexpr (IOU) acc_iou = (double)(bce_logits_(xl, q.t) * wv[0]);
     } else {
@@ -463,7 +486,7 @@ __device__ __forceinline__ void box_elem(const BoxTail &c, const BaseAnchors &ba
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float g = (smooth_l1_der(dp[k] - dt[k], c.beta) * wl[k]) * gs1;
+            const float g = (loc_der(dp[k] - dt[k]) * wl[k]) * gs1;
             // with the IoU term the add is unconditional (attach off: gv = 0, and x + 0.0f turns
             // -0.0f into +0.0f); the plain RetinaHead kind (smooth-L1 alone) has no add
             g_box[k] = IOU ? g + gv[k] : g;
@@ -493,8 +516,8 @@ __device__ __forceinline__ void box_block_reduce(double *sums, int L, int l, dou
     }
 }
 
-template <typename T, bool BWD, bool IOU, bool BAL_LOC = false>
-__global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
+template <typename T, bool BWD, bool IOU, bool BAL_LOC = false, int LOC = 0>
+__global__ void __launch_bounds__(256) k_box_ml(typename BoxSel<LOC>::ML a)
 {
     const BlockRef r = locate_block<false>(a.lv, blockIdx.x);
     const int A = a.lv.A, W = a.lv.W[r.l], HW = a.lv.H[r.l] * W;
@@ -515,8 +538,8 @@ __global__ void __launch_bounds__(256) k_box_ml(BoxMLArgs a)
             const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[r.l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
             const float xl = IOU ? load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e) : 0.0f;
-            box_elem<BWD, IOU, BAL_LOC>(a.tail, a.ba, a.lv.L, r.l, r.an, p, W, a.lv.stride[r.l], wv, dp, dt, xl,
-                                        acc_l1, acc_iou, g_box, g_iou);
+            box_elem<BWD, IOU, BAL_LOC, LOC>(a.tail, loc_consts<LOC>(a), a.ba, a.lv.L, r.l, r.an, p, W, a.lv.stride[r.l],
+                                             wv, dp, dt, xl, acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
             float *go = a.tail.g_reg[r.l] + ba * 4 * HW + p;
@@ -691,8 +714,17 @@ struct BoxNhwcArgs {
     int32_t g_pad[IA_MAX_LEVELS];         // bwd: zero-gradient channels behind d(iou) in the same pixel row
 };
 
-template <bool BWD, bool IOU, bool BAL_LOC = false>
-__global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
+struct BoxNhwcBl1Args : BoxNhwcArgs { BalL1 bl; };
+// the LOC = 0 launches pass the base part of one such block (launch_box_ml / launch_box_nhwc): the base must
+// sit at the block's front with the constants behind it
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"   // single inheritance: a base at offset 0, asserted here
+static_assert(offsetof(BoxMLBl1Args, bl) >= sizeof(BoxMLArgs), "the constants ride behind the smooth-L1 block");
+static_assert(offsetof(BoxNhwcBl1Args, bl) >= sizeof(BoxNhwcArgs), "the constants ride behind the smooth-L1 block");
+#pragma clang diagnostic pop
+
+template <bool BWD, bool IOU, bool BAL_LOC = false, int LOC = 0>
+__global__ void __launch_bounds__(256) k_box_nhwc(typename BoxSel<LOC>::Nhwc a)
 {
     int o = 0;
     while ((int)blockIdx.x >= a.lv.bblk_off[o + 1]) ++o;
@@ -715,8 +747,8 @@ __global__ void __launch_bounds__(256) k_box_nhwc(BoxNhwcArgs a)
             const float4 tq = reinterpret_cast<const float4 *>(a.tail.bt[l])[n];
             const float dt[4] = {tq.x, tq.y, tq.z, tq.w};
             const float xl = IOU ? a.iou[l][pix * a.ps_iou[l] + an] : 0.0f;
-            box_elem<BWD, IOU, BAL_LOC>(a.tail, a.ba, a.lv.L, l, an, p, W, a.lv.stride[l], wv, dp, dt, xl,
-                                        acc_l1, acc_iou, g_box, g_iou);
+            box_elem<BWD, IOU, BAL_LOC, LOC>(a.tail, loc_consts<LOC>(a), a.ba, a.lv.L, l, an, p, W, a.lv.stride[l], wv, dp, dt,
+                                             xl, acc_l1, acc_iou, g_box, g_iou);
         }
         if (BWD) {
             *reinterpret_cast<float4 *>(a.tail.g_reg[l] + pix * a.pg_reg[l] + 4 * an) =
@@ -1112,6 +1144,43 @@ static int launch_box_nhwc(bool bwd, int kind, const BoxNhwcArgs &ba, hipStream_
     hipLaunchKernelGGL(k[bwd][kind], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
     return hip_status(hipGetLastError());
 }
+// bl1: the balanced-L1 instances (kind 0 / 1) on the whole block; else the smooth-L1 ones on its front part
+static int launch_box_ml(int dtype, bool bwd, int kind, bool bl1, const BoxMLBl1Args &ba, hipStream_t s)
+{
+    if (bl1) {
+        static void (*const k[2][2][2])(BoxMLBl1Args) = {
+            {{k_box_ml<float, false, false, false, 1>, k_box_ml<float, false, true, false, 1>},
+             {k_box_ml<float, true, false, false, 1>, k_box_ml<float, true, true, false, 1>}},
+            {{k_box_ml<uint16_t, false, false, false, 1>, k_box_ml<uint16_t, false, true, false, 1>},
+             {k_box_ml<uint16_t, true, false, false, 1>, k_box_ml<uint16_t, true, true, false, 1>}}};
+        hipLaunchKernelGGL(k[dtype == IA_BF16][bwd][kind], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+        return hip_status(hipGetLastError());
+    }
+    return launch_box_ml(dtype, bwd, kind, static_cast<const BoxMLArgs &>(ba), s);
+}
+static int launch_box_nhwc(bool bwd, int kind, bool bl1, const BoxNhwcBl1Args &ba, hipStream_t s)
+{
+    if (bl1) {
+        static void (*const k[2][2])(BoxNhwcBl1Args) = {
+            {k_box_nhwc<false, false, false, 1>, k_box_nhwc<false, true, false, 1>},
+            {k_box_nhwc<true, false, false, 1>, k_box_nhwc<true, true, false, 1>}};
+        hipLaunchKernelGGL(k[bwd][kind], dim3((unsigned)ba.lv.bblk_off[ba.lv.L]), dim3(256), 0, s, ba);
+        return hip_status(hipGetLastError());
+    }
+    return launch_box_nhwc(bwd, kind, static_cast<const BoxNhwcArgs &>(ba), s);
+}
+// ia_box_loss_cfg -> bl1 and the kernels' constants.  NULL / IA_BOX_SMOOTH_L1: the smooth-L1 of cfg alone.
+static int box_loss_consts(const ia_box_loss_cfg *box, const ia_head_loss_cfg *cfg, bool &bl1, BalL1 &bl)
+{
+    bl1 = false;
+    if (!box) return 0;
+    if (box->struct_size != (int32_t)sizeof(ia_box_loss_cfg)) return IA_E_ARG;
+    if (box->kind == IA_BOX_SMOOTH_L1) return 0;
+    if (box->kind != IA_BOX_BALANCED_L1 || !cfg || cfg->balanced_loc) return IA_E_ARG;
+    if (!balanced_l1_consts(box->alpha, box->gamma, cfg->beta, bl)) return IA_E_ARG;
+    bl1 = true;
+    return 0;
+}
 int launch_focal_nhwc_unit(const FocalNhwcArgs &fa, int dtype, bool bwd, hipStream_t s)
 {
     static void (*const k[2][2])(FocalNhwcArgs) = {
@@ -1153,13 +1222,22 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
                      const ia_head_targets *t, const ia_head_loss_cfg *cfg, void *workspace,
                      size_t workspace_bytes, float *result, void *stream)
 {
+    return ia_head_loss_fwd_box(g, p, dtype, batch, t, cfg, nullptr, workspace, workspace_bytes, result, stream);
+}
+
+int ia_head_loss_fwd_box(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                         const ia_head_targets *t, const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box,
+                         void *workspace, size_t workspace_bytes, float *result, void *stream)
+{
     using namespace ia;
     if ((uintptr_t)workspace & 255u) return IA_E_ARG;
     FocalMLBalArgs fa;
-    BoxMLArgs ba;
+    BoxMLBl1Args ba;
     HLWorkspace ws;
-    bool with_iou;
-    int rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, false, nullptr, nullptr, fa, ba,
+    bool with_iou, bl1;
+    int rc = box_loss_consts(box, cfg, bl1, ba.bl);
+    if (rc) return rc;
+    rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, false, nullptr, nullptr, fa, ba,
                           ws, with_iou);
     if (rc) return rc;
     const bool bal_cls = cfg->balanced_cls != 0;
@@ -1182,7 +1260,7 @@ int ia_head_loss_fwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)pa.tile_off[L]), dim3(256), 0, s, pa);
     if ((rc = launch_focal_ml(dtype, false, bal_cls, fa, s)) ||
-        (rc = launch_box_ml(dtype, false, box_kind(with_iou, cfg), ba, s)))
+        (rc = launch_box_ml(dtype, false, box_kind(with_iou, cfg), bl1, ba, s)))
         return rc;
     return launch_finalize(ws.sums, t, cfg, L, batch, result, s);
 }
@@ -1192,17 +1270,27 @@ int ia_head_loss_bwd(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, i
                      const float *result, const float *grad_result, const ia_level_ptrs *grads,
                      void *stream)
 {
+    return ia_head_loss_bwd_box(g, p, dtype, batch, t, cfg, nullptr, workspace, result, grad_result, grads, stream);
+}
+
+int ia_head_loss_bwd_box(const ia_head_geom *g, const ia_level_ptrs *p, int dtype, int batch,
+                         const ia_head_targets *t, const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box,
+                         const void *workspace, const float *result, const float *grad_result,
+                         const ia_level_ptrs *grads, void *stream)
+{
     using namespace ia;
     FocalMLBalArgs fa;
-    BoxMLArgs ba;
+    BoxMLBl1Args ba;
     HLWorkspace ws;
-    bool with_iou;
-    int rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, true, grad_result, grads, fa, ba,
+    bool with_iou, bl1;
+    int rc = box_loss_consts(box, cfg, bl1, ba.bl);
+    if (rc) return rc;
+    rc = ml_loss_args(g, p, dtype, batch, t, cfg, workspace, result, true, grad_result, grads, fa, ba,
                           ws, with_iou);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = launch_focal_ml(dtype, true, cfg->balanced_cls != 0, fa, s))) return rc;
-    return launch_box_ml(dtype, true, box_kind(with_iou, cfg), ba, s);
+    return launch_box_ml(dtype, true, box_kind(with_iou, cfg), bl1, ba, s);
 }
 
 int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
@@ -1210,13 +1298,23 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           const ia_head_loss_cfg *cfg, void *workspace, size_t workspace_bytes,
                           float *result, void *stream)
 {
+    return ia_head_loss_fwd_nhwc_box(g, p, strides, batch, t, cfg, nullptr, workspace, workspace_bytes, result, stream);
+}
+
+int ia_head_loss_fwd_nhwc_box(const ia_head_geom *g, const ia_level_ptrs *p,
+                              const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
+                              const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box, void *workspace,
+                              size_t workspace_bytes, float *result, void *stream)
+{
     using namespace ia;
     if (!workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
     double *sums = static_cast<double *>(workspace);
     FocalNhwcBalArgs fa;
-    BoxNhwcArgs ba;
-    bool with_iou;
-    int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, sums, result, false, nullptr, nullptr, nullptr,
+    BoxNhwcBl1Args ba;
+    bool with_iou, bl1;
+    int rc = box_loss_consts(box, cfg, bl1, ba.bl);
+    if (rc) return rc;
+    rc = nhwc_loss_args(g, p, strides, batch, t, cfg, sums, result, false, nullptr, nullptr, nullptr,
                             fa, ba, with_iou);
     if (rc) return rc;
     const int L = fa.lv.L;
@@ -1226,7 +1324,7 @@ int ia_head_loss_fwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(sums, 0, slot_bytes(L, bal_cls), s);
     if (e != hipSuccess) return (int)e;
-    if ((rc = launch_focal_nhwc(false, bal_cls, fa, s)) || (rc = launch_box_nhwc(false, box_kind(with_iou, cfg), ba, s)))
+    if ((rc = launch_focal_nhwc(false, bal_cls, fa, s)) || (rc = launch_box_nhwc(false, box_kind(with_iou, cfg), bl1, ba, s)))
         return rc;
     return launch_finalize(sums, t, cfg, L, batch, result, s);
 }
@@ -1237,16 +1335,28 @@ int ia_head_loss_bwd_nhwc(const ia_head_geom *g, const ia_level_ptrs *p,
                           const ia_level_ptrs *grads, const ia_level_pix_strides *grad_strides,
                           void *stream)
 {
+    return ia_head_loss_bwd_nhwc_box(g, p, strides, batch, t, cfg, nullptr, result, grad_result, grads, grad_strides,
+                                     stream);
+}
+
+int ia_head_loss_bwd_nhwc_box(const ia_head_geom *g, const ia_level_ptrs *p,
+                              const ia_level_pix_strides *strides, int batch, const ia_head_targets *t,
+                              const ia_head_loss_cfg *cfg, const ia_box_loss_cfg *box, const float *result,
+                              const float *grad_result, const ia_level_ptrs *grads,
+                              const ia_level_pix_strides *grad_strides, void *stream)
+{
     using namespace ia;
     FocalNhwcBalArgs fa;
-    BoxNhwcArgs ba;
-    bool with_iou;
-    int rc = nhwc_loss_args(g, p, strides, batch, t, cfg, nullptr, result, true, grad_result, grads,
+    BoxNhwcBl1Args ba;
+    bool with_iou, bl1;
+    int rc = box_loss_consts(box, cfg, bl1, ba.bl);
+    if (rc) return rc;
+    rc = nhwc_loss_args(g, p, strides, batch, t, cfg, nullptr, result, true, grad_result, grads,
                             grad_strides, fa, ba, with_iou);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = launch_focal_nhwc(true, cfg->balanced_cls != 0, fa, s))) return rc;
-    return launch_box_nhwc(true, box_kind(with_iou, cfg), ba, s);
+    return launch_box_nhwc(true, box_kind(with_iou, cfg), bl1, ba, s);
 }
 
 }  // extern "C"

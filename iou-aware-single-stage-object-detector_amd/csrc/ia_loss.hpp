@@ -5,6 +5,7 @@
 // (reference iou_aware_retina_head.py:256-259,276-281; core/bbox/transforms.py:44-78;
 // core/bbox/geometry.py:34-47; core/loss/losses.py:385-411,460-480).
 #pragma once
+#include <math.h>
 #include "ia_internal.hpp"
 #include "ia_math.hpp"
 #include "ia_block.hpp"
@@ -152,6 +153,41 @@ __device__ __forceinline__ float smooth_l1_der(float df, float beta)
     const float d = __builtin_fabsf(df);
     const float sgn = (df > 0.0f) ? 1.0f : ((df < 0.0f) ? -1.0f : 0.0f);
     return (d < beta) ? df / beta : sgn;
+}
+
+// BalancedL1Loss of one coordinate (losses.py:482-507) and its derivative.  With d = |df| and
+// b = e^(gamma / alpha) - 1:  d < beta: alpha / b * (b d + 1) * log(b d / beta + 1) - alpha d,  else
+// gamma d + gamma / b - alpha beta.  The constants are the fp32 values the reference's python scalars
+// round to (b in double first); the derivative is that of this expression, jump at the knee for
+// beta != 1 included: alpha log(b d / beta + 1) + alpha (1 - beta) / (b d + beta) inside, gamma outside.
+struct BalL1 { float alpha, gamma, b, a_b, g_b, ab, a1mb; };   // ., ., b, alpha/b, gamma/b, alpha*beta, alpha*(1-beta)
+
+// host: false for alpha, gamma or beta not > 0 (or a b beyond fp32)
+inline bool balanced_l1_consts(float alpha, float gamma, float beta, BalL1 &k)
+{
+    if (!(alpha > 0.0f) || !(gamma > 0.0f) || !(beta > 0.0f)) return false;
+    const double b = pow(2.718281828459045, (double)gamma / (double)alpha) - 1.0;   // np.e ** (gamma / alpha) - 1
+    if (!(b > 0.0) || !(b < 3.0e38)) return false;
+    k.alpha = alpha; k.gamma = gamma; k.b = (float)b;
+    k.a_b = (float)((double)alpha / b); k.g_b = (float)((double)gamma / b);
+    k.ab = (float)((double)alpha * (double)beta);
+    k.a1mb = (float)((double)alpha * (1.0 - (double)beta));
+    return true;
+}
+__device__ __forceinline__ float balanced_l1_val(float df, float beta, const BalL1 &k)
+{
+    const float d = __builtin_fabsf(df);
+    const float bd = k.b * d;
+    return (d < beta) ? (k.a_b * (bd + 1.0f)) * fastm::log_(bd / beta + 1.0f) - k.alpha * d
+                      : (k.gamma * d + k.g_b) - k.ab;
+}
+__device__ __forceinline__ float balanced_l1_der(float df, float beta, const BalL1 &k)
+{
+    const float d = __builtin_fabsf(df);
+    const float sgn = (df > 0.0f) ? 1.0f : ((df < 0.0f) ? -1.0f : 0.0f);
+    const float bd = k.b * d;
+    const float in = k.alpha * fastm::log_(bd / beta + 1.0f) + k.a1mb / (bd + beta);
+    return sgn * ((d < beta) ? in : k.gamma);
 }
 
 }  // namespace ia

@@ -14,6 +14,7 @@
 // so every class-plane access is a contiguous 1 KiB segment, and the label /
 // weight of an anchor are read once for all C classes.  Sums are reduced in
 // fp64 (wave shuffle -> LDS -> one fp64 atomic per workgroup).
+#include <stddef.h>
 #include "ia_loss.hpp"
 
 namespace ia {
@@ -246,11 +247,22 @@ struct SmoothArgs {
     const float *anchor_iou;      // IoU-balanced variant (losses.py:416-458): weight * iou^delta
     float delta;
 };
+// BalancedL1Loss (LOC = 1; losses.py:482-520): its constants ride behind the smooth-L1 block, whose
+// instances keep their kernel arguments
+struct BalancedL1Args : SmoothArgs { BalL1 k; };
+// the smooth-L1 launches pass the base part of one such block: it must be the block's front
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"   // single inheritance: a base at offset 0, asserted here
+static_assert(offsetof(BalancedL1Args, k) >= sizeof(SmoothArgs), "the constants ride behind the smooth-L1 block");
+#pragma clang diagnostic pop
+template <int LOC> struct SmoothSel { typedef SmoothArgs Args; };
+template <> struct SmoothSel<1> { typedef BalancedL1Args Args; };
 
 // thread = (image, anchor, position); the 4 delta planes of an anchor are read coalesced along
 // the position, target / weight rows (16 B) from the (B, N_l, 4) arrays.  32-bit index math.
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(256) k_smooth_l1(SmoothArgs a)
+// LOC: the element function -- 0 smooth-L1, 1 balanced L1 (no IoU weights)
+template <typename T, bool BWD, int LOC = 0>
+__global__ void __launch_bounds__(256) k_smooth_l1(typename SmoothSel<LOC>::Args a)
 {
     __shared__ double red[16];
     const int A = a.A, HW = a.HW;
@@ -279,7 +291,10 @@ __global__ void __launch_bounds__(256) k_smooth_l1(SmoothArgs a)
             const size_t e = e0 + (size_t)k * HW;
             float df = load_f32<T>(static_cast<const T *>(a.pred) + e) - tv[k];
             float d = __builtin_fabsf(df);
-            if (BWD) {
+            if constexpr (LOC == 1) {
+                if (BWD) a.grad[e] = (balanced_l1_der(df, a.beta, a.k) * wv[k]) * gs;
+                else acc += balanced_l1_val(df, a.beta, a.k) * wv[k];
+            } else if (BWD) {
                 float sgn = (df > 0.0f) ? 1.0f : ((df < 0.0f) ? -1.0f : 0.0f);
                 float g = (d < a.beta) ? df / a.beta : sgn;
                 a.grad[e] = (g * wv[k]) * gs;
@@ -295,24 +310,32 @@ __global__ void __launch_bounds__(256) k_smooth_l1(SmoothArgs a)
 static int launch_smooth(bool bwd, const void *pred, int dtype, const float *target,
                          const float *weight, int B, int A, int HW, float beta, float gscale,
                          const float *gscale_dev, double *loss_sum, float *grad, hipStream_t s,
-                         const float *anchor_iou = nullptr, float delta = 0.0f)
+                         const float *anchor_iou = nullptr, float delta = 0.0f,
+                         const float *alpha_gamma = nullptr)      // balanced L1: {alpha, gamma}
 {
     if (!pred || !target || !weight || B < 1 || A < 1 || HW < 1 || !(beta > 0.0f)) return IA_E_ARG;
     if (bwd ? !grad : !loss_sum) return IA_E_ARG;
-    SmoothArgs a;
+    BalancedL1Args a;
+    if (alpha_gamma && (anchor_iou || !balanced_l1_consts(alpha_gamma[0], alpha_gamma[1], beta, a.k)))
+        return IA_E_ARG;
     a.pred = pred; a.target = target; a.weight = weight; a.loss_sum = loss_sum; a.grad = grad;
     a.B = B; a.A = A; a.HW = HW; a.beta = beta; a.gscale = gscale; a.gscale_dev = gscale_dev;
     a.anchor_iou = anchor_iou; a.delta = delta;
     const int64_t blocks = (int64_t)B * A * ((HW + 255) / 256);
     if (blocks > 2147483647LL) return IA_E_ARG;
     unsigned grid = (unsigned)blocks;
-    if (dtype == IA_F32) {
-        if (bwd) hipLaunchKernelGGL((k_smooth_l1<float, true>), dim3(grid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_smooth_l1<float, false>), dim3(grid), dim3(256), 0, s, a);
-    } else if (dtype == IA_BF16) {
-        if (bwd) hipLaunchKernelGGL((k_smooth_l1<uint16_t, true>), dim3(grid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_smooth_l1<uint16_t, false>), dim3(grid), dim3(256), 0, s, a);
-    } else return IA_E_ARG;
+    if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
+    const dim3 g3(grid), b3(256);
+    const int bf = dtype == IA_BF16;
+    if (alpha_gamma) {                                            // [bf16][bwd], the balanced-L1 instances
+        static void (*const k[2][2])(BalancedL1Args) = {{k_smooth_l1<float, false, 1>, k_smooth_l1<float, true, 1>},
+                                                        {k_smooth_l1<uint16_t, false, 1>, k_smooth_l1<uint16_t, true, 1>}};
+        hipLaunchKernelGGL(k[bf][bwd], g3, b3, 0, s, a);
+    } else {                                                      // smooth-L1: the block without the constants
+        static void (*const k[2][2])(SmoothArgs) = {{k_smooth_l1<float, false>, k_smooth_l1<float, true>},
+                                                    {k_smooth_l1<uint16_t, false>, k_smooth_l1<uint16_t, true>}};
+        hipLaunchKernelGGL(k[bf][bwd], g3, b3, 0, s, static_cast<const SmoothArgs &>(a));
+    }
     return hip_status(hipGetLastError());
 }
 
@@ -571,6 +594,21 @@ int ia_smooth_l1_balanced_bwd(const void *pred, int dtype, const float *target,
     if (!anchor_iou) return IA_E_ARG;
     return ia::launch_smooth(true, pred, dtype, target, weight, B, A, HW, beta, gscale, gscale_dev,
                              nullptr, grad, (hipStream_t)stream, anchor_iou, delta);
+}
+int ia_balanced_l1_fwd(const void *pred, int dtype, const float *target, const float *weight, int B,
+                       int A, int HW, float beta, float alpha, float gamma, double *loss_sum, void *stream)
+{
+    const float ag[2] = {alpha, gamma};
+    return ia::launch_smooth(false, pred, dtype, target, weight, B, A, HW, beta, 1.0f, nullptr,
+                             loss_sum, nullptr, (hipStream_t)stream, nullptr, 0.0f, ag);
+}
+int ia_balanced_l1_bwd(const void *pred, int dtype, const float *target, const float *weight, int B,
+                       int A, int HW, float beta, float alpha, float gamma, float gscale,
+                       const float *gscale_dev, float *grad, void *stream)
+{
+    const float ag[2] = {alpha, gamma};
+    return ia::launch_smooth(true, pred, dtype, target, weight, B, A, HW, beta, gscale, gscale_dev,
+                             nullptr, grad, (hipStream_t)stream, nullptr, 0.0f, ag);
 }
 int ia_iou_bce_fwd(const ia_head_geom *g, int level, const void *bbox_pred, const void *iou_pred,
                    int dtype, const float *bt, const float *bw, int B, float *iou_target,

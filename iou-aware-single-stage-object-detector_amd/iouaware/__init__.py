@@ -1,7 +1,8 @@
 """MI355X-native IoU-aware RetinaNet hot path (host side).
 
 Importing this package registers the reference's type names (`RetinaNet`,
-`ResNet`, `ResNeXt`, `FPN`, `IoUawareRetinaHead`, `FocalLoss`, `SmoothL1Loss`)
+`ResNet`, `ResNeXt`, `FPN`, `IoUawareRetinaHead`, `FocalLoss`, `SmoothL1Loss`,
+`BalancedL1Loss`)
 so `configs/iou_aware_single_stage_detector/*.py` of the reference build
 unchanged through `build_detector`.  The post-conv compute lives in
 libiouaware_hip.so (hand-written gfx950 kernels, C-ABI in include/iouaware.h).

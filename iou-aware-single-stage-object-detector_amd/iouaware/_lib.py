@@ -69,6 +69,14 @@ class HeadLossCfg(C.Structure):
                 ('balanced_cls', C.c_int32), ('balanced_loc', C.c_int32)]
 
 
+IA_BOX_SMOOTH_L1, IA_BOX_BALANCED_L1 = 0, 1
+
+
+class BoxLossCfg(C.Structure):
+    """ia_box_loss_cfg: the localisation loss of the ia_head_loss_*_box entries"""
+    _fields_ = [('struct_size', C.c_int32), ('kind', C.c_int32), ('alpha', C.c_float), ('gamma', C.c_float)]
+
+
 class PointLevelPtrs(C.Structure):
     """ia_point_level_ptrs"""
     _fields_ = [('cls', C.c_void_p * IA_MAX_LEVELS), ('reg', C.c_void_p * IA_MAX_LEVELS),
@@ -193,6 +201,8 @@ SIGNATURES = {
     'ia_focal_loss_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     'ia_smooth_l1_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     'ia_smooth_l1_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    'ia_balanced_l1_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    'ia_balanced_l1_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp]),
     'ia_focal_loss_balanced_fwd': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     'ia_focal_loss_balanced_bwd': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _f,
                                         _vp, _vp, _vp]),
@@ -217,6 +227,15 @@ SIGNATURES = {
     'ia_head_loss_bwd_nhwc': (_i, [_G, _P, C.POINTER(LevelPixStrides), _i, C.POINTER(HeadTargets),
                                    C.POINTER(HeadLossCfg), _vp, _vp, _P, C.POINTER(LevelPixStrides),
                                    _vp]),
+    'ia_head_loss_fwd_box': (_i, [_G, _P, _i, _i, C.POINTER(HeadTargets), C.POINTER(HeadLossCfg),
+                                  C.POINTER(BoxLossCfg), _vp, _sz, _vp, _vp]),
+    'ia_head_loss_bwd_box': (_i, [_G, _P, _i, _i, C.POINTER(HeadTargets), C.POINTER(HeadLossCfg),
+                                  C.POINTER(BoxLossCfg), _vp, _vp, _vp, _P, _vp]),
+    'ia_head_loss_fwd_nhwc_box': (_i, [_G, _P, C.POINTER(LevelPixStrides), _i, C.POINTER(HeadTargets),
+                                       C.POINTER(HeadLossCfg), C.POINTER(BoxLossCfg), _vp, _sz, _vp, _vp]),
+    'ia_head_loss_bwd_nhwc_box': (_i, [_G, _P, C.POINTER(LevelPixStrides), _i, C.POINTER(HeadTargets),
+                                       C.POINTER(HeadLossCfg), C.POINTER(BoxLossCfg), _vp, _vp, _P,
+                                       C.POINTER(LevelPixStrides), _vp]),
     'ia_grouped_conv3x3_pack': (_i, [_vp, _vp, _i, _i, _vp]),
     'ia_grouped_conv3x3_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_grouped_conv3x3_packed_bytes_bf16': (C.c_size_t, [_i, _i]),

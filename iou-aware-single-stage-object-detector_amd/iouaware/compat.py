@@ -54,6 +54,7 @@ def install(force=False):
                             RetinaNet=detectors.RetinaNet, FCOS=detectors.FCOS)
     models.losses = _mod('mmdet.models.losses', FocalLoss=losses.FocalLoss,
                          SmoothL1Loss=losses.SmoothL1Loss,
+                         BalancedL1Loss=losses.BalancedL1Loss,
                          IOUbalancedSigmoidFocalLoss=losses.IOUbalancedSigmoidFocalLoss,
                          IoUbalancedSmoothL1Loss=losses.IoUbalancedSmoothL1Loss)
     models.utils = _mod('mmdet.models.utils', **{k: getattr(layers, k) for k in (

@@ -211,13 +211,14 @@ class _RetinaHeadBase(AnchorHead):
     fuse_balanced = False                 # opt-in: the IoU-balanced losses on the all-levels node too
 
     def _fused_loss_ok(self, cls_scores):
-        from .losses import FocalLoss, SmoothL1Loss, IOUbalancedSigmoidFocalLoss, IoUbalancedSmoothL1Loss
+        from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, IOUbalancedSigmoidFocalLoss,
+                             IoUbalancedSmoothL1Loss)
         cls_t, box_t = type(self.loss_cls), type(self.loss_bbox)
         balanced = cls_t is IOUbalancedSigmoidFocalLoss or box_t is IoUbalancedSmoothL1Loss
         if balanced and not (self.fuse_balanced and self.iou_branch):
             return False                  # they weigh by the IoU target: `_loss_levels`
         return (self.fuse_levels and cls_t in (FocalLoss, IOUbalancedSigmoidFocalLoss)
-                and box_t in (SmoothL1Loss, IoUbalancedSmoothL1Loss) and float(self.loss_cls.gamma) == 2.0
+                and box_t in (SmoothL1Loss, IoUbalancedSmoothL1Loss, BalancedL1Loss) and float(self.loss_cls.gamma) == 2.0
                 and self.use_sigmoid_cls and not self.sampling and cls_scores[0].is_cuda
                 and cls_scores[0].dtype in (torch.float32, torch.bfloat16))
 
@@ -290,6 +291,9 @@ class _RetinaHeadBase(AnchorHead):
         on_dev = level_anchors[0] is None          # targets came from the HIP assigner
         # (the balanced focal module, like the reference's, does not apply its loss_weight: losses.py)
         eta, delta = getattr(self.loss_cls, 'eta', None), getattr(self.loss_bbox, 'delta', None)
+        from .losses import BalancedL1Loss
+        lb = self.loss_bbox
+        box_loss = ('balanced_l1', lb.alpha, lb.gamma) if type(lb) is BalancedL1Loss else None
         return ops.head_loss(
             geom, cls_scores, bbox_preds, iou_preds, labels, label_w, bbox_t, bbox_w,
             counts=counts if on_dev else None,
@@ -297,7 +301,7 @@ class _RetinaHeadBase(AnchorHead):
             gamma=self.loss_cls.gamma, alpha=self.loss_cls.alpha,
             loss_weight_cls=self.loss_cls.loss_weight if eta is None else 1.0, beta=self.loss_bbox.beta,
             loss_weight_bbox=self.loss_bbox.loss_weight, attach_iou_target=self.attach_iou_target,
-            eta=eta, delta=delta)
+            eta=eta, delta=delta, box_loss=box_loss)
 
 
 @HEADS.register_module

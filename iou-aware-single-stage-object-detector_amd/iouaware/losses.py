@@ -1,4 +1,4 @@
-"""Loss modules the IoU-aware configs name (`FocalLoss`, `SmoothL1Loss`),
+"""Loss modules the IoU-aware configs name (`FocalLoss`, `SmoothL1Loss`, `BalancedL1Loss`),
 backed by the HIP loss kernels (csrc/loss.hip).
 
 Two call forms:
@@ -117,6 +117,33 @@ class SmoothL1Loss(nn.Module):
         n = pred.shape[0]
         total = ops.smooth_l1_sum(pred.reshape(n, 4, 1, 1), target.reshape(n, 1, 4),
                                   weight.reshape(n, 1, 4), 1, self.beta)
+        return total * (self.loss_weight / avg_factor)      # avg_factor: python number or device scalar
+
+
+@LOSSES.register_module
+class BalancedL1Loss(nn.Module):
+    """reference mmdet/models/losses/balanced_l1_loss.py:7-31 with core/loss/losses.py:482-520
+    (Libra R-CNN's balanced L1): a drop-in for SmoothL1Loss in both anchor heads, same call, same weights."""
+
+    def __init__(self, alpha=0.5, gamma=1.5, beta=1.0, loss_weight=1.0):
+        super(BalancedL1Loss, self).__init__()
+        self.alpha, self.gamma, self.beta, self.loss_weight = alpha, gamma, beta, loss_weight
+
+    def forward_level(self, bbox_pred, bbox_targets, bbox_weights, num_anchors, avg_factor):
+        """bbox_pred (B, A*4, H, W); targets / weights (B, N_l, 4)."""
+        total = ops.balanced_l1_sum(bbox_pred, bbox_targets, bbox_weights, num_anchors, self.beta,
+                                    self.alpha, self.gamma)
+        return total * (self.loss_weight / avg_factor)      # avg_factor: python number or device scalar
+
+    def forward(self, pred, target, weight, avg_factor=None, **kwargs):
+        """pred / target / weight (N, 4)."""
+        if pred.size() != target.size() or target.numel() == 0:
+            raise AssertionError('pred / target shape mismatch or empty')
+        if avg_factor is None:
+            avg_factor = float((weight > 0).sum().item()) / 4 + 1e-6
+        n = pred.shape[0]
+        total = ops.balanced_l1_sum(pred.reshape(n, 4, 1, 1), target.reshape(n, 1, 4),
+                                    weight.reshape(n, 1, 4), 1, self.beta, self.alpha, self.gamma)
         return total * (self.loss_weight / avg_factor)      # avg_factor: python number or device scalar
 
 

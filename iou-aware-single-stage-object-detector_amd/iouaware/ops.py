@@ -1557,6 +1557,40 @@ def smooth_l1_sum(pred, target, weight, num_anchors, beta):
     return _SmoothL1Fn.apply(pred, target, weight, num_anchors, beta)
 
 
+class _BalancedL1Fn(torch.autograd.Function):
+    """sum over the level of balanced_l1_loss * weight (reference losses.py:482-520) on NCHW deltas."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, A, beta, alpha, gamma):
+        _require_gpu(pred, 'bbox_pred')
+        pred = pred.contiguous()
+        B, ch, H, W = pred.shape
+        target = target.contiguous().to(torch.float32)
+        weight = weight.contiguous().to(torch.float32)
+        acc = torch.zeros(_lib.IA_LOSS_SLOTS, dtype=torch.float64, device=pred.device)
+        _lib.check(_lib.lib().ia_balanced_l1_fwd(_ptr(pred), _dtype_code(pred), _ptr(target),
+                                                 _ptr(weight), B, A, H * W, float(beta), float(alpha),
+                                                 float(gamma), _ptr(acc), _stream()), 'ia_balanced_l1_fwd')
+        ctx.save_for_backward(pred, target, weight)
+        ctx.cfg = (A, float(beta), float(alpha), float(gamma))
+        return acc.sum().reshape(1).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, weight = ctx.saved_tensors
+        A, beta, alpha, gamma = ctx.cfg
+        B, ch, H, W = pred.shape
+        grad = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+        _lib.check(_lib.lib().ia_balanced_l1_bwd(_ptr(pred), _dtype_code(pred), _ptr(target),
+                                                 _ptr(weight), B, A, H * W, beta, alpha, gamma, 1.0,
+                                                 _ptr(_gdev(g)), _ptr(grad), _stream()), 'ia_balanced_l1_bwd')
+        return grad.to(pred.dtype), None, None, None, None, None, None
+
+
+def balanced_l1_sum(pred, target, weight, num_anchors, beta, alpha=0.5, gamma=1.5):
+    return _BalancedL1Fn.apply(pred, target, weight, num_anchors, beta, alpha, gamma)
+
+
 class _IouBceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, bbox_pred, iou_pred, bbox_targets, bbox_weights, geom, level, attach_target,
@@ -1828,6 +1862,17 @@ def _head_loss_outputs(ctx, res, L):
     return outs
 
 
+def _box_loss_cfg(box):
+    """box: None (SmoothL1Loss, the NULL of the *_box entries) or ('balanced_l1', alpha, gamma)
+    -> ia_box_loss_cfg or None"""
+    if box is None:
+        return None
+    kind, alpha, gamma = box
+    if kind != 'balanced_l1':
+        raise ValueError('unknown localisation loss %r' % (kind,))
+    return _lib.BoxLossCfg(C.sizeof(_lib.BoxLossCfg), _lib.IA_BOX_BALANCED_L1, float(alpha), float(gamma))
+
+
 class _HeadLossFn(torch.autograd.Function):
     """the three losses of every level: 3 launches forward, 2 backward (csrc/headloss.hip).
     Outputs: 3L per-level (1,) tensors and 3 totals, views of one result vector.  A geometry without
@@ -1835,7 +1880,7 @@ class _HeadLossFn(torch.autograd.Function):
     entries of the result are 0 and gradients come back for cls and reg only."""
 
     @staticmethod
-    def forward(ctx, geom, targets, cfg, *outs):
+    def forward(ctx, geom, targets, cfg, box, *outs):
         L = geom.L
         if len(outs) != (3 if geom.iou_branch else 2) * L:
             raise AssertionError('expected %d head outputs' % ((3 if geom.iou_branch else 2) * L))
@@ -1851,7 +1896,7 @@ class _HeadLossFn(torch.autograd.Function):
             p.cls[l], p.reg[l] = cls[l].data_ptr(), reg[l].data_ptr()
             p.iou[l] = iou[l].data_ptr() if iou else None
         ht, kept = _pack_head_targets(targets, L)
-        hc = _lib.HeadLossCfg(*cfg)
+        hc, bc = _lib.HeadLossCfg(*cfg), _box_loss_cfg(box)
         # IoU-balanced focal loss: norm_l[L] behind the plain result, two more slot rows per level
         res = torch.empty((4 if hc.balanced_cls else 3) * L + 4, dtype=torch.float32, device=dev)
         g = geom.with_layout(_lib.IA_LAYOUT_NCHW)
@@ -1861,11 +1906,11 @@ class _HeadLossFn(torch.autograd.Function):
         # own buffer (not the shared inference workspace): it carries the packed targets from
         # the forward to the backward call
         ws = _own_workspace(dev, nbytes)
-        _lib.check(_lib.lib().ia_head_loss_fwd(g.ref(), C.byref(p), dt, B, C.byref(ht),
-                                               C.byref(hc), _ptr(ws), nbytes, _ptr(res),
-                                               _stream()), 'ia_head_loss_fwd')
+        _lib.check(_lib.lib().ia_head_loss_fwd_box(g.ref(), C.byref(p), dt, B, C.byref(ht),
+                                                   C.byref(hc), bc, _ptr(ws), nbytes, _ptr(res),
+                                                   _stream()), 'ia_head_loss_fwd_box')
         ctx.ws = ws
-        ctx.geom, ctx.cfg, ctx.B, ctx.dt = g, hc, B, dt
+        ctx.geom, ctx.cfg, ctx.box, ctx.B, ctx.dt = g, hc, bc, B, dt
         ctx.keep = (cls, reg, iou, p, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
@@ -1882,13 +1927,13 @@ class _HeadLossFn(torch.autograd.Function):
         for l in range(L):
             gp.cls[l], gp.reg[l] = grads[0][l].data_ptr(), grads[1][l].data_ptr()
             gp.iou[l] = grads[2][l].data_ptr() if iou else None
-        _lib.check(_lib.lib().ia_head_loss_bwd(ctx.geom.ref(), C.byref(p), ctx.dt, ctx.B,
-                                               C.byref(ht), C.byref(ctx.cfg), _ptr(ctx.ws),
-                                               _ptr(ctx.res), _ptr(gin), C.byref(gp), _stream()),
-                   'ia_head_loss_bwd')
+        _lib.check(_lib.lib().ia_head_loss_bwd_box(ctx.geom.ref(), C.byref(p), ctx.dt, ctx.B,
+                                                   C.byref(ht), C.byref(ctx.cfg), ctx.box, _ptr(ctx.ws),
+                                                   _ptr(ctx.res), _ptr(gin), C.byref(gp), _stream()),
+                   'ia_head_loss_bwd_box')
         out = [g if g.dtype == t.dtype else g.to(t.dtype)
                for x, gx in zip((cls, reg, iou), grads) for t, g in zip(x, gx)]
-        return (None, None, None) + tuple(out)
+        return (None, None, None, None) + tuple(out)
 
 
 def _pix_stride(t):
@@ -1943,7 +1988,7 @@ class _HeadLossNhwcFn(torch.autograd.Function):
     cls[L] + reg[L], or (fused) cls[L] + the wider tensors whose channels [0, 4A) are reg."""
 
     @staticmethod
-    def forward(ctx, geom, targets, cfg, views, *outs):
+    def forward(ctx, geom, targets, cfg, box, views, *outs):
         L = geom.L
         cls = list(outs[:L])
         fused = views is not None
@@ -1962,15 +2007,15 @@ class _HeadLossNhwcFn(torch.autograd.Function):
             if iou is not None:
                 p.iou[l], st.iou[l] = iou[l].data_ptr(), _pix_stride(iou[l])
         ht, kept = _pack_head_targets(targets, L)
-        hc = _lib.HeadLossCfg(*cfg)
+        hc, bc = _lib.HeadLossCfg(*cfg), _box_loss_cfg(box)
         # IoU-balanced focal loss: norm_l[L] behind the plain result, two more slot rows per level
         res = torch.empty((4 if hc.balanced_cls else 3) * L + 4, dtype=torch.float32, device=dev)
         nbytes = 8 * (5 if hc.balanced_cls else 3) * L * _lib.IA_LOSS_SLOTS
         ws = _workspace(dev, nbytes)
-        _lib.check(_lib.lib().ia_head_loss_fwd_nhwc(geom.ref(), C.byref(p), C.byref(st), B,
-                                                    C.byref(ht), C.byref(hc), _ptr(ws), nbytes,
-                                                    _ptr(res), _stream()), 'ia_head_loss_fwd_nhwc')
-        ctx.geom, ctx.cfg, ctx.B, ctx.fused = geom, hc, B, fused
+        _lib.check(_lib.lib().ia_head_loss_fwd_nhwc_box(geom.ref(), C.byref(p), C.byref(st), B,
+                                                        C.byref(ht), C.byref(hc), bc, _ptr(ws), nbytes,
+                                                        _ptr(res), _stream()), 'ia_head_loss_fwd_nhwc_box')
+        ctx.geom, ctx.cfg, ctx.box, ctx.B, ctx.fused = geom, hc, bc, B, fused
         ctx.keep = (cls, reg, iou, bases, p, st, ht, kept)
         ctx.res = res
         ctx.set_materialize_grads(False)
@@ -2017,11 +2062,11 @@ class _HeadLossNhwcFn(torch.autograd.Function):
             ctx.cfg.grad_rows_start_at_reg = 0
         for l in range(L):
             gp.cls[l], gst.cls[l] = g_cls[l].data_ptr(), cls[l].shape[1]
-        _lib.check(_lib.lib().ia_head_loss_bwd_nhwc(ctx.geom.ref(), C.byref(p), C.byref(st), ctx.B,
-                                                    C.byref(ht), C.byref(ctx.cfg), _ptr(ctx.res),
-                                                    _ptr(gin), C.byref(gp), C.byref(gst), _stream()),
-                   'ia_head_loss_bwd_nhwc')
-        return (None, None, None, None) + tuple(g_cls) + tuple(tail)
+        _lib.check(_lib.lib().ia_head_loss_bwd_nhwc_box(ctx.geom.ref(), C.byref(p), C.byref(st), ctx.B,
+                                                        C.byref(ht), C.byref(ctx.cfg), ctx.box, _ptr(ctx.res),
+                                                        _ptr(gin), C.byref(gp), C.byref(gst), _stream()),
+                   'ia_head_loss_bwd_nhwc_box')
+        return (None, None, None, None, None) + tuple(g_cls) + tuple(tail)
 
 
 def _nhwc_route(geom, cls, reg, iou):
@@ -2042,11 +2087,13 @@ def _nhwc_route(geom, cls, reg, iou):
 def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_weights, counts=None,
               avg_factor=None, gamma=2.0, alpha=0.25, loss_weight_cls=1.0, beta=0.11,
               loss_weight_bbox=1.0, attach_iou_target=True, exact_large_logits=False,
-              channels_last=None, eta=None, delta=None):
+              channels_last=None, eta=None, delta=None, box_loss=None):
     """FocalLoss(gamma=2) + SmoothL1Loss + IoU BCE of every pyramid level in one autograd node.
     eta / delta (None: the plain loss): IOUbalancedSigmoidFocalLoss with exponent eta in place of FocalLoss,
     IoUbalancedSmoothL1Loss with exponent delta in place of SmoothL1Loss -- both weigh by the (detached)
     IoU target of the IoU branch, so they need a geometry with it; same node, same launches.
+    box_loss=('balanced_l1', alpha, gamma): BalancedL1Loss(alpha, gamma, beta) in place of SmoothL1Loss, with
+    or without the IoU branch (not together with delta); None: SmoothL1Loss.
     iou=None with a geometry built with iou_branch=False (the plain RetinaHead): FocalLoss +
     SmoothL1Loss alone, -> dict(loss_cls, loss_bbox) (the reference's keys, anchor_head.py:299).
     channels_last: None = the channels-last kernels when every head output is channels-last(-like)
@@ -2064,6 +2111,10 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
         raise ValueError('the IoU-balanced losses need a head with the IoU branch')
     if (eta is not None and not float(eta) > 0.0) or (delta is not None and not float(delta) > 0.0):
         raise ValueError('eta / delta must be positive')
+    if box_loss is not None and delta is not None:
+        raise ValueError('the IoU-balanced weighting (delta) belongs to SmoothL1Loss, not to %r' % (box_loss[0],))
+    if box_loss is not None:
+        box_loss = (box_loss[0], float(box_loss[1]), float(box_loss[2]))
     L = geom.L
     cfg = (float(gamma), float(alpha), float(loss_weight_cls), float(beta), float(loss_weight_bbox),
            int(bool(attach_iou_target)), int(bool(exact_large_logits)), 0,
@@ -2072,11 +2123,11 @@ def head_loss(geom, cls, reg, iou, labels, label_weights, bbox_targets, bbox_wei
                avg_factor)
     route = _nhwc_route(geom, cls, reg, iou) if channels_last is not False else None
     if route is not None:
-        flat = _HeadLossNhwcFn.apply(geom, targets, cfg, route[0], *route[1])
+        flat = _HeadLossNhwcFn.apply(geom, targets, cfg, box_loss, route[0], *route[1])
     elif channels_last is True:
         raise ValueError('channels_last=True needs channels-last fp32 head outputs, C % 4 == 0')
     else:
-        flat = _HeadLossFn.apply(geom, targets, cfg,
+        flat = _HeadLossFn.apply(geom, targets, cfg, box_loss,
                                  *(list(cls) + list(reg) + (list(iou) if iou is not None else [])))
     out = {}
     for k, name in enumerate(('loss_cls', 'loss_bbox', 'losses_iou')[:3 if geom.iou_branch else 2]):

@@ -3,7 +3,8 @@ outputs): device target assignment + the three losses of all levels forward + pa
 backward.  Prints wall per iteration (HIP events); under rocprofv3 the kernel trace is reduced by
 tools/summarize_trace.py with the marker `k_box_ml<float, true` (last kernel of an iteration).
 
-    python tools/time_headloss.py [B] [per_level | nhwc] [plain | balanced | --head {iou_aware,plain}] [--iters N]
+    python tools/time_headloss.py [B] [per_level | nhwc] [plain | balanced | --head {iou_aware,plain}]
+                                  [balanced_l1] [--iters N]
 
 `plain` (or `--head plain`): the plain RetinaHead built from the same settings, the IoU maps
 dropped -- FocalLoss + SmoothL1Loss alone, on the same three routes (the all-levels node without
@@ -14,6 +15,11 @@ training head produces it).  The focal part, and with it the algorithmic-bytes l
 (delta = 1.5), `fuse_balanced` set: the all-levels node with its IoU-balanced instances (markers
 `k_box_ml<float, true, true, true>` / `k_box_nhwc<true, true, true>`), or with `per_level` the route such
 a head takes without the switch.
+
+`balanced_l1`: loss_bbox = BalancedL1Loss(alpha = 0.5, gamma = 1.5) with the configuration's beta and
+loss_weight, on either head (combine with `plain`) and on all three routes: the node's LOC = 1 instances
+(markers `k_box_ml<float, true, true, false, 1>` / `k_box_nhwc<true, true, false, 1>`, `.., false, false, 1>`
+without the IoU term), or with `per_level` the per-level kernels `k_smooth_l1<.., 1>`.
 """
 import os
 import sys
@@ -44,7 +50,10 @@ if '--iters' in args:
 balanced = 'balanced' in args
 if balanced and plain:
     sys.exit('the IoU-balanced losses need the IoU-aware head')
-args = [a for a in args if a not in ('plain', 'balanced')]
+balanced_l1 = 'balanced_l1' in args
+if balanced and balanced_l1:
+    sys.exit('balanced (the IoU-balanced smooth-L1) and balanced_l1 both replace loss_bbox')
+args = [a for a in args if a not in ('plain', 'balanced', 'balanced_l1')]
 B = int(args[0]) if args else 4
 per_level = len(args) > 1 and args[1] == 'per_level'
 nhwc = len(args) > 1 and args[1] == 'nhwc'              # channels-last outputs, reg | iou as slices of one
@@ -61,6 +70,9 @@ if balanced:
     kw['loss_cls'] = dict(type='IOUbalancedSigmoidFocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25,
                           eta=1.5, loss_weight=1.0)
     kw['loss_bbox'] = dict(type='IoUbalancedSmoothL1Loss', beta=kw['loss_bbox'].get('beta', 0.11), delta=1.5,
+                           loss_weight=kw['loss_bbox'].get('loss_weight', 1.0))
+if balanced_l1:
+    kw['loss_bbox'] = dict(type='BalancedL1Loss', alpha=0.5, gamma=1.5, beta=kw['loss_bbox'].get('beta', 0.11),
                            loss_weight=kw['loss_bbox'].get('loss_weight', 1.0))
 head = (RetinaHead if plain else IoUawareRetinaHead)(**kw).cuda()
 head.fuse_levels = not per_level
@@ -114,6 +126,7 @@ torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / n
 print('B=%d %s%s: targets + losses fwd + bwd  %.3f ms per iteration' %
       (B, 'plain RetinaHead, ' if plain else ('IoU-balanced losses, ' if balanced else ''),
-       'per-level kernels' if per_level else 'all-levels kernels', ms))
+       ('BalancedL1Loss, ' if balanced_l1 else '') +
+       ('per-level kernels' if per_level else 'all-levels kernels'), ms))
 print('focal algorithmic bytes: fwd %.1f MB, bwd %.1f MB per iteration' %
       (66931200 * B / 1e6, 131443200 * B / 1e6))
