@@ -325,6 +325,15 @@ int ia_wino_output_transform(const ia_wino_geom *g, const float *M, int channels
  * not overlap M.                                                                              */
 int ia_wino_mid_transform(const ia_wino_geom *g, const float *M, int channels, int groups_m,
                           const float *bias, int relu, float *V, int groups_v, void *stream);
+/* Input transform and the 36 products behind it in one launch: M[k] (T, channels) = V[k] . U[k]
+ * with V never written to memory -- the bits that ia_wino_input_transform(groups = 1) followed
+ * by ia_batched_gemm_stream(36, T, channels, channels) gives.  channels == 64 (Cin == Cout).
+ * u_packed: U (36, Cin, Cout) in MFMA fragment order, (36, Cout/16, Cin/16, 64, 4):
+ *   u_packed[k][nb][j][16 q + p][c] = U[k][16 j + 4 q + c][16 nb + p]
+ * (iouaware/winograd.py pack_u_fragments).  pre_scale / pre_shift / pre_relu as for
+ * ia_wino_input_transform; x, u_packed, M, pre_* 16-byte aligned.                            */
+int ia_wino_in_gemm(const ia_wino_geom *g, const float *const *x, int channels, const float *pre_scale,
+                    const float *pre_shift, int pre_relu, const float *u_packed, float *M, void *stream);
 
 /* Training: gradient of the output transform, dM = A dY A^T per tile (dY (B,H,W,channels)
  * channels-last per level, zero outside the map), written as 36 matrices (36, tiles, channels)

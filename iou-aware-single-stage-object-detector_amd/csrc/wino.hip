@@ -17,7 +17,9 @@
 //                             into the channels-last activation / head-output tensors;
 //   k_wino_mid  (this file)   k_wino_out of a layer and k_wino_in of the next layer of the same
 //                             geometry in one launch (the head's tower transitions): the
-//                             activation in between stays in LDS.
+//                             activation in between stays in LDS;
+//   k_wino_in_gemm (this file) k_wino_in and the 36 products of a 64 -> 64 convolution in one
+//                             launch (ResNet stage 1): V stays in LDS.
 // Activations are channels-last fp32: a wavefront handles one tile x 256 channels, 16 bytes per
 // lane, so every load / store instruction moves one contiguous 1 KiB pixel row.  Both kernels
 // are HBM-bound streams (36 x 16 B in, 36 x 16 B out per lane; 36 in, 16 out).
@@ -185,6 +187,188 @@ __global__ void __launch_bounds__(64) k_wino_in(WinoInArgs a)
 #pragma unroll
         for (int j = 0; j < 6; ++j)
             *reinterpret_cast<float4 *>(v + (size_t)(i * 6 + j) * kstride) = o[j];
+    }
+}
+
+// ---- Input transform and the 36 Winograd-domain products in ONE launch (ResNet stage 1, the
+// bottlenecks' 3x3 / 64 -> 64 convolutions): M[k] = V[k] . U[k] without V's trip through HBM (309 MB
+// written by k_wino_in and read straight back by k_conv1x1_stream<64, 64> at batch 8 of 200 x 336).
+// A workgroup of C / 16 wavefronts owns 16 consecutive tiles.
+//   transform: the body of k_wino_in<true>, expression by expression (lane = (tile, channel quad),
+//     all 36 clamped loads first, pre-activation, padding select, bt6 on columns, then bt6 row by
+//     row); the 6 planes of a row go to LDS as [plane][tile 0..15][C] instead of to V;
+//   products: the loop of k_conv1x1_stream<C, C> in its MFMA order: wavefront nb owns output
+//     channels 16 nb .. + 15, lane (p, q) feeds its tile's channels 16 j + 4 q + c (j outer, c
+//     inner) into v_mfma_f32_16x16x4_f32 against the weight fragment U[16 j + 4 q + c][16 nb + p],
+//     the accumulator starts at +0 and is stored as one float4 into M[tile p][16 nb + 4 q .. + 3].
+// So every element of M has the bits of the two launches.  What stays resident is the
+// column-transformed tile (tmp, dying row by row) and two LDS buffers of 6 planes: row i + 1 is
+// written while row i is multiplied, one barrier per row.
+// U comes from global memory (L1 / L2: all workgroups read the same 36 x C x C floats) in
+// FRAGMENT ORDER, packed once on the host side: [plane][nb][j][lane 16 q + p][c], so that a lane
+// reads the four weights of a j step as one float4 and a wavefront 1 KiB contiguous.
+// LDS image: the 16-byte slot s of tile p's row sits at slot s ^ p.  The product phase reads slot
+// 4 j + q of row p; unswizzled, the 16 lanes that ds_read_b128 serves in one cycle (two lane
+// quads of one q and eight lanes of another) would all hit the four banks of slot 4 j + q: 8-way.
+// With the XOR every such group covers 16 different slots, and the transform's 8-lane write
+// groups (one tile, 8 consecutive quads) stay on 8 different slots modulo 8.
+struct WinoInGemmArgs {
+    WinoLevels lv;
+    const float *x[IA_MAX_LEVELS];        // per level (B, H, W, C) channels-last
+    const float *U;                       // (36, C / 16, C / 16, 64, 4): fragment order
+    float *M;                             // (36, T, C)
+    const float *pre_scale, *pre_shift;   // as WinoInArgs
+    int32_t T, pre_relu, ngroups;
+};
+
+template <int C>
+__global__ void __launch_bounds__(4 * C) k_wino_in_gemm(WinoInGemmArgs a)
+{
+    static_assert(C == 64, "lane maps and the LDS swizzle are worked out for 16 quads per tile");
+    constexpr int Q = C / 4, TPW = 64 / Q, NB = C / 16, J = C / 16;
+    constexpr int kPlane = 16 * C;                     // floats of one plane of the 16 tiles
+    __shared__ __attribute__((aligned(16))) float s_v[2 * 6 * kPlane];
+    const int grp = xcd_tile(blockIdx.x, a.ngroups);
+    if (grp >= a.ngroups) return;                      // the grid is rounded up to the 8 XCDs
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    // ---- transform phase: this lane's tile and channel quad
+    const int sub = lane / Q, quad = lane - sub * Q, tg = wave * TPW + sub, c = 4 * quad;
+    const int t0 = grp * 16 + tg;
+    const int t = t0 < a.T ? t0 : a.T - 1;             // past the end: a valid tile, its products are not stored
+    int H, W;
+    const TileRef r = locate_tile(a.lv, t, &H, &W);
+    const float *x = level_ptr<false>(a.x, r.l) + (size_t)r.b * H * W * C + c;
+    const bool pre = a.pre_shift != nullptr;
+    float4 ps = f4(1.0f), pb = f4(0.0f);
+    if (pre) {
+        if (a.pre_scale) ps = *reinterpret_cast<const float4 *>(a.pre_scale + c);
+        pb = *reinterpret_cast<const float4 *>(a.pre_shift + c);
+    }
+    float4 d[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int y = r.y0 - 1 + i;
+        const int yc = (y >= 0 && y < H) ? y : 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int xx = r.x0 - 1 + j;
+            const int xc = (xx >= 0 && xx < W) ? xx : 0;
+            d[i][j] = *reinterpret_cast<const float4 *>(x + ((size_t)yc * W + xc) * C);
+        }
+    }
+    if (pre) {
+        const bool relu = a.pre_relu != 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                float4 v = d[i][j];
+                v = make_float4(v.x * ps.x + pb.x, v.y * ps.y + pb.y, v.z * ps.z + pb.z, v.w * ps.w + pb.w);
+                const float4 z = make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f,
+                                             v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
+                d[i][j] = relu ? z : v;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int y = r.y0 - 1 + i;
+        const bool yin = (y >= 0) && (y < H);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int xx = r.x0 - 1 + j;
+            const bool in = yin && (xx >= 0) && (xx < W);
+            d[i][j] = in ? d[i][j] : f4(0.0f);
+        }
+    }
+    float4 tmp[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {                       // columns: tmp = B^T d
+        float4 col[6], o[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) col[i] = d[i][j];
+        bt6(col, o);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) tmp[i][j] = o[i];
+    }
+    float *const sw = s_v + tg * C + 4 * (quad ^ tg);   // this lane's slot of a plane
+
+    // ---- product phase: this lane's tile (B operand / output row) and k group
+    const int p = lane & 15, q = lane >> 4;
+    const int tp = grp * 16 + p;
+    const bool live = tp < a.T;
+    const float *const sr = s_v + p * C;
+    int xo[J];                                         // float offset of slot 4 j + q in row p
+#pragma unroll
+    for (int j = 0; j < J; ++j) xo[j] = 4 * ((4 * j + q) ^ p);
+    const float *const up = a.U + ((size_t)wave * J * 64 + lane) * 4;
+    float *const mp = a.M + ((size_t)(live ? tp : 0) * C + 16 * wave + 4 * q);
+    const size_t kstride = (size_t)a.T * C;
+
+    // Planes go through the MFMA pipe in pairs, their two accumulator chains interleaved (40 cycles
+    // of dependent latency against 32 of issue); the weights of the next pair are requested before
+    // this pair's MFMAs, also across the barrier.
+    constexpr int PG = 2;
+    f32x4_t wn[PG][J];
+#pragma unroll
+    for (int g = 0; g < PG; ++g)
+#pragma unroll
+        for (int j = 0; j < J; ++j) wn[g][j] = *reinterpret_cast<const f32x4_t *>(up + g * (C * C) + j * 256);
+
+    {                                                   // row 0 of V = tmp B -> buffer 0
+        float4 o[6];
+        bt6(tmp[0], o);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) *reinterpret_cast<float4 *>(sw + j * kPlane) = o[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        if (i + 1 < 6) {                                // row i + 1 -> the other buffer
+            float4 o[6];
+            bt6(tmp[i + 1], o);
+            float *const s = sw + ((i + 1) & 1) * 6 * kPlane;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) *reinterpret_cast<float4 *>(s + j * kPlane) = o[j];
+        }
+#pragma unroll
+        for (int j6 = 0; j6 < 6; j6 += PG) {
+            const int k = i * 6 + j6;
+            const float *const s = sr + ((i & 1) * 6 + j6) * kPlane;
+            f32x4_t xv[PG][J], wv[PG][J], acc[PG];
+#pragma unroll
+            for (int g = 0; g < PG; ++g) {
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    xv[g][j] = *reinterpret_cast<const f32x4_t *>(s + g * kPlane + xo[j]);
+                    wv[g][j] = wn[g][j];
+                }
+                acc[g] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+            }
+            if (k + PG < 36) {
+                const float *const un = up + (size_t)(k + PG) * (C * C);
+#pragma unroll
+                for (int g = 0; g < PG; ++g)
+#pragma unroll
+                    for (int j = 0; j < J; ++j) wn[g][j] = *reinterpret_cast<const f32x4_t *>(un + g * (C * C) + j * 256);
+            }
+            // (without it the scheduler sinks these loads to the end of the pair's MFMAs, right in
+            // front of the wait of the next pair: one L2 round trip exposed per pair)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+                    for (int g = 0; g < PG; ++g)
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[g][j][cc], xv[g][j][cc], acc[g], 0, 0, 0);
+            if (live) {
+#pragma unroll
+                for (int g = 0; g < PG; ++g) *reinterpret_cast<f32x4_t *>(mp + (size_t)(k + g) * kstride) = acc[g];
+            }
+        }
+        if (i + 1 < 6) __syncthreads();
     }
 }
 
@@ -518,6 +702,30 @@ int ia_wino_input_transform(const ia_wino_geom *g, const float *const *x, int ch
     dim3 grid((unsigned)((waves + 7) / 8 * 8), (unsigned)((channels / 4 + 63) / 64));
     if (a.tpw > 1) hipLaunchKernelGGL(ia::k_wino_in<true>, grid, dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ia::k_wino_in<false>, grid, dim3(64), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+int ia_wino_in_gemm(const ia_wino_geom *g, const float *const *x, int channels, const float *pre_scale,
+                    const float *pre_shift, int pre_relu, const float *u_packed, float *M, void *stream)
+{
+    ia::WinoInGemmArgs a;
+    int rc = ia::make_wino_levels(g, a.lv);
+    if (rc) return rc;
+    if (!x || !u_packed || !M || channels != 64) return IA_E_ARG;
+    if (((uintptr_t)u_packed & 15u) || ((uintptr_t)M & 15u) || ((uintptr_t)pre_scale & 15u) ||
+        ((uintptr_t)pre_shift & 15u))
+        return IA_E_ARG;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        a.x[l] = (l < a.lv.L) ? x[l] : nullptr;
+        if (l < a.lv.L && (!x[l] || ((uintptr_t)x[l] & 15u))) return IA_E_ARG;
+    }
+    if (pre_scale && !pre_shift) return IA_E_ARG;
+    a.U = u_packed; a.M = M;
+    a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.pre_relu = pre_relu ? 1 : 0;
+    a.T = a.lv.tile_off[a.lv.L];
+    a.ngroups = (int32_t)(((int64_t)a.T + 15) / 16);
+    dim3 grid((unsigned)((a.ngroups + 7) / 8 * 8));
+    hipLaunchKernelGGL(ia::k_wino_in_gemm<64>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return ia::hip_status(hipGetLastError());
 }
 

@@ -6,6 +6,7 @@ retina_reg, retina_iou) and of the FPN output convolutions (fpn.py:124-127).
     V . U   (36 [x2 towers] plain fp32 GEMMs: hipBLASLt, strided batched, csrc/gemm.hip)    -->  M
     M  --k_wino_out (+bias, +ReLU)-->  next activations / the head outputs, channels-last
     M  --k_wino_mid (+bias, +ReLU)-->  V of the next tower layer (bias + ReLU towers: no activation tensor)
+    activations  --k_wino_in_gemm-->  M  (64 -> 64, ResNet stage 1: transform and products in one launch, no V)
 
 The head's weights are shared by the pyramid levels, so every layer is ONE batched GEMM over the
 tiles of all levels; the two towers run side by side (first layer: one GEMM with 512 output
@@ -213,6 +214,31 @@ def batched_gemm(v, u, out):
     return out
 
 
+FUSE_IN_GEMM = True    # False: input_transform + batched_gemm (tests compare the two bit for bit)
+_IN_GEMM_CHANNELS = (64,)      # ia_wino_in_gemm: Cin == Cout in this list
+
+
+def pack_u_fragments(u):
+    """U (36, Cin, Cout) -> the MFMA fragment order ia_wino_in_gemm reads, (36, Cout/16, Cin/16, 64, 4):
+    packed[k][nb][j][16 q + p][c] = u[k][16 j + 4 q + c][16 nb + p]"""
+    b, k, n = u.shape
+    if k % 16 or n % 16:
+        raise ValueError('fragment order needs multiples of 16 channels')
+    return u.reshape(b, k // 16, 4, 4, n // 16, 16).permute(0, 4, 1, 2, 5, 3).contiguous() \
+            .view(b, n // 16, k // 16, 64, 4)
+
+
+def input_transform_gemm(plan, xs, u_packed, out, pre=None):
+    """out (36, T, C) = input_transform(xs) @ U in one launch (V stays on chip): the bits of
+    input_transform followed by ia_batched_gemm_stream.  Not a pure transform, so not `_timed`."""
+    ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+    ps, pb, pr = pre if pre is not None else (None, None, False)
+    _lib.check(_lib.lib().ia_wino_in_gemm(C.byref(plan.geom), ptrs, int(xs[0].shape[1]), _ptr(ps), _ptr(pb),
+                                          int(bool(pr)), _ptr(u_packed), _ptr(out), _stream()),
+               'ia_wino_in_gemm')
+    return out
+
+
 class WinogradConv3x3(object):
     """one 3x3 / stride-1 / pad-1 convolution (+bias, +ReLU) over a list of channels-last level
     tensors that do NOT share the weight with other layers' inputs (FPN output convs: one
@@ -220,6 +246,9 @@ class WinogradConv3x3(object):
 
     def __init__(self, weight, bias, relu=False):
         self.u = transform_weight(weight)
+        self.u_packed = None
+        if self.u.shape[1] == self.u.shape[2] and self.u.shape[1] in _IN_GEMM_CHANNELS:
+            self.u_packed = pack_u_fragments(self.u)
         self.bias = None if bias is None else bias.detach().to(torch.float32).contiguous()
         self.relu = relu
         self.cin, self.cout = self.u.shape[1], self.u.shape[2]
@@ -240,8 +269,14 @@ class WinogradConv3x3(object):
         # do not share them
         key = (x.shape[0], tuple(x.shape[-2:]), x.device, stream_id())
         plan = _plan_for(self._plans, key, lambda: _Plan([tuple(x.shape[-2:])], x.shape[0], x.device))
-        v = input_transform(plan, [x], 1, plan.buf('v', (36, plan.T, self.cin)), pre)
-        m = batched_gemm(v, self.u, plan.buf('m', (36, plan.T, self.cout)))
+        if (FUSE_IN_GEMM and self.u_packed is not None and STREAM_BMM
+                and (self.cin, self.cout) in _STREAM_BMM_SHAPES and plan.T >= 4096
+                and x.dtype == torch.float32):
+            # exactly where batched_gemm takes the streaming kernel: the same bits, V not written
+            m = input_transform_gemm(plan, [x], self.u_packed, plan.buf('m', (36, plan.T, self.cout)), pre)
+        else:
+            v = input_transform(plan, [x], 1, plan.buf('v', (36, plan.T, self.cin)), pre)
+            m = batched_gemm(v, self.u, plan.buf('m', (36, plan.T, self.cout)))
         y = torch.empty((x.shape[0], self.cout) + tuple(x.shape[-2:]), dtype=torch.float32,
                         device=x.device, memory_format=torch.channels_last)
         output_transform(plan, m, self.cout, 1, self.bias, self.relu, [(0, self.cout, [y], 0)])
