@@ -178,7 +178,11 @@ struct PtBoxArgs {
     int32_t attach;
 };
 
-struct PtElem { float c, u, ov, un, w, h, pw, ph; bool x1in, y1in, x2in, y2in; };
+// sx1 .. sy2: the share of d ov / d (intersection edge) that the predicted edge takes -- 1 inside the
+// target's, 0 outside, 0.5 on it (what torch.max / torch.min and the anchor kernels of ia_loss.hpp do)
+struct PtElem { float c, u, ov, un, w, h, pw, ph, sx1, sy1, sx2, sy2; };
+
+__device__ __forceinline__ float tie_share(bool in, bool on) { return in ? 1.0f : (on ? 0.5f : 0.0f); }
 
 // centerness target, the two boxes and their aligned IoU (+1 widths) of one positive point
 __device__ __forceinline__ PtElem point_elem(float px, float py, const float (&d)[4], const float4 &t)
@@ -189,9 +193,11 @@ __device__ __forceinline__ PtElem point_elem(float px, float py, const float (&d
     e.c = __builtin_sqrtf((lrmin / lrmax) * (tbmin / tbmax));
     const float px1 = px - d[0], py1 = py - d[1], px2 = px + d[2], py2 = py + d[3];
     const float tx1 = px - t.x, ty1 = py - t.y, tx2 = px + t.z, ty2 = py + t.w;
-    e.x1in = px1 > tx1; e.y1in = py1 > ty1; e.x2in = px2 < tx2; e.y2in = py2 < ty2;
-    const float ltx = e.x1in ? px1 : tx1, lty = e.y1in ? py1 : ty1;
-    const float rbx = e.x2in ? px2 : tx2, rby = e.y2in ? py2 : ty2;
+    const bool x1in = px1 > tx1, y1in = py1 > ty1, x2in = px2 < tx2, y2in = py2 < ty2;
+    e.sx1 = tie_share(x1in, px1 == tx1); e.sy1 = tie_share(y1in, py1 == ty1);
+    e.sx2 = tie_share(x2in, px2 == tx2); e.sy2 = tie_share(y2in, py2 == ty2);
+    const float ltx = x1in ? px1 : tx1, lty = y1in ? py1 : ty1;
+    const float rbx = x2in ? px2 : tx2, rby = y2in ? py2 : ty2;
     const float w0 = (rbx - ltx) + 1.0f, h0 = (rby - lty) + 1.0f;
     e.w = (w0 < 0.0f) ? 0.0f : w0; e.h = (h0 < 0.0f) ? 0.0f : h0;
     e.ov = e.w * e.h;
@@ -243,17 +249,19 @@ __global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
                     g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
                     if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
                 }
-                // u = ov / un, un = ap + at - ov
+                // u = ov / un, un = ap + at - ov; both factors are formed as (v / un) / un, so that at
+                // ov == un (prediction == target) d/d ov is -2 d/d ap to the bit and the two halves below
+                // cancel it: the gradient at the loss's minimum is exactly 0
                 const float inv_un = 1.0f / q.un;
-                const float g_ov = gu * ((q.un + q.ov) * inv_un) * inv_un;
+                const float g_ov = gu * (((q.un + q.ov) * inv_un) * inv_un);
                 const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
                 const float g_w = g_ov * q.h, g_h = g_ov * q.w;      // w0, h0 > 0: both boxes hold the point
                 const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
                 // x1 = px - left, x2 = px + right: d/d left = -d/d x1
-                g_box[0] = g_pw + (q.x1in ? g_w : 0.0f);
-                g_box[1] = g_ph + (q.y1in ? g_h : 0.0f);
-                g_box[2] = g_pw + (q.x2in ? g_w : 0.0f);
-                g_box[3] = g_ph + (q.y2in ? g_h : 0.0f);
+                g_box[0] = g_pw + q.sx1 * g_w;
+                g_box[1] = g_ph + q.sy1 * g_h;
+                g_box[2] = g_pw + q.sx2 * g_w;
+                g_box[3] = g_ph + q.sy2 * g_h;
             }
         }
         if (BWD) {
@@ -382,14 +390,14 @@ __global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
                     if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
                 }
                 const float inv_un = 1.0f / q.un;
-                const float g_ov = gu * ((q.un + q.ov) * inv_un) * inv_un;
+                const float g_ov = gu * (((q.un + q.ov) * inv_un) * inv_un);    // as in k_point_box
                 const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
                 const float g_w = g_ov * q.h, g_h = g_ov * q.w;
                 const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
-                g_box[0] = g_pw + (q.x1in ? g_w : 0.0f);
-                g_box[1] = g_ph + (q.y1in ? g_h : 0.0f);
-                g_box[2] = g_pw + (q.x2in ? g_w : 0.0f);
-                g_box[3] = g_ph + (q.y2in ? g_h : 0.0f);
+                g_box[0] = g_pw + q.sx1 * g_w;
+                g_box[1] = g_ph + q.sy1 * g_h;
+                g_box[2] = g_pw + q.sx2 * g_w;
+                g_box[3] = g_ph + q.sy2 * g_h;
                 if (raw) {
                     // d = exp(scale x): dL/dx = (g d) scale, dL/dscale += (g d) x
                     float ts = 0.0f;

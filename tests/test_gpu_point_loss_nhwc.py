@@ -13,13 +13,13 @@ that autograd gives the raw-reg and scale gradients.  Bounds:
     instance's gradient on the same values (same fp32 arithmetic; the normalisers' last bits may differ);
   * grad_scale: |got - ref| <= 1e-4 x sum |g d x| (the sum of the yardstick's terms), exactly 0 for a
     level without positives."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_util as G
 import synth_fcos_loss as S
 
 pytestmark = pytest.mark.gpu
@@ -122,82 +122,20 @@ def _targets(gb, gl):
 
 def _rows(vals, iou_branch, dtype, wc, wr, fill=7.0):
     """(B, H, W, width) rows [cls | ctr | fill] and [reg | iou? | fill] per level, on the device"""
-    cc, ri = [], []
-    for l in range(NL):
-        cls, reg, ctr, iou = (torch.from_numpy(m[l]) for m in vals)
-        B, _, h, w = cls.shape
-        a = torch.full((B, h, w, wc), fill)
-        a[..., :S.C] = cls.permute(0, 2, 3, 1)
-        a[..., S.C] = ctr[:, 0]
-        b = torch.full((B, h, w, wr), fill)
-        b[..., :4] = reg.permute(0, 2, 3, 1)
-        if iou_branch:
-            b[..., 4] = iou[:, 0]
-        cc.append(a.to(DEV, dtype))
-        ri.append(b.to(DEV, dtype))
-    return cc, ri
+    return G.point_rows(vals, iou_branch, dtype, wc, wr, S.C, fill)
 
 
 def _ptrs(cc, ri, iou_branch, off_ctr=S.C, off_iou=4):
-    from iouaware import _lib
-    p, st = _lib.PointLevelPtrs(), _lib.PointPixStrides()
-    es = cc[0].element_size()
-    for l in range(NL):
-        p.cls[l], p.ctr[l] = cc[l].data_ptr(), cc[l].data_ptr() + off_ctr * es
-        p.reg[l] = ri[l].data_ptr()
-        p.iou[l] = ri[l].data_ptr() + off_iou * es if iou_branch else None
-        st.cls[l] = st.ctr[l] = cc[l].shape[-1]
-        st.reg[l] = st.iou[l] = ri[l].shape[-1]
-    return p, st
+    return G.point_row_ptrs(cc, ri, iou_branch, off_ctr, off_iou)
 
 
-class _Node(object):
-    """forward once, backward per upstream vector, through ctypes"""
+class _Node(G.PointRowsNode):
+    """forward once, backward per upstream vector, through ctypes (gpu_util.PointRowsNode)"""
 
     def __init__(self, name, iou_branch, vals, dtype, wc, wr, scaled, rounded=False):
-        from iouaware import _lib
         gb, gl = _case(name, rounded)[:2]
-        self.L, self.iou, self.B = _lib.lib(), iou_branch, len(gb)
-        self.geom = _geom()
-        self.lab, self.tgt, self.counts = _targets(gb, gl)
-        self.cc, self.ri = _rows(vals, iou_branch, dtype, wc, wr)
-        self.dt = _lib.IA_BF16 if dtype == torch.bfloat16 else _lib.IA_F32
-        self.p, self.st = _ptrs(self.cc, self.ri, iou_branch)
-        self.pt = _lib.PointTargets()
-        for l in range(NL):
-            self.pt.labels[l], self.pt.bbox_targets[l] = self.lab[l].data_ptr(), self.tgt[l].data_ptr()
-        self.pt.counts = self.counts.data_ptr()
-        self.cfg = _lib.PointLossCfg(2.0, 0.25, 1, 0)
-        self.sc = torch.from_numpy(SCALES).to(DEV) if scaled else None
-        self.nbytes = self.L.ia_point_head_loss_nhwc_workspace_bytes(self.geom.ref(), self.B)
-        assert self.nbytes > 0
-        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=DEV)
-        self.res = torch.full((6,), -7.0, device=DEV)
-
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    def fwd(self, **kw):
-        a = dict(geom=self.geom, p=self.p, st=self.st, dt=self.dt, B=self.B, sc=self.sc, ws=self.ws, n=self.nbytes)
-        a.update(kw)
-        return self.L.ia_point_head_loss_fwd_nhwc(
-            a['geom'].ref(), C.byref(a['p']), C.byref(a['st']), a['dt'], a['B'], C.byref(self.pt),
-            C.byref(self.cfg), self._p(a['sc']), self._p(a['ws']), a['n'], self._p(self.res), None)
-
-    def new_grads(self, fill=float('nan')):
-        return ([torch.full_like(t, fill) for t in self.cc], [torch.full_like(t, fill) for t in self.ri],
-                torch.full((NL,), fill, device=DEV) if self.sc is not None else None)
-
-    def bwd(self, gin, grads, packed=1, **kw):
-        g_cc, g_ri, g_sc = grads
-        gp, gst = _ptrs(g_cc, g_ri, self.iou)
-        a = dict(p=self.p, st=self.st, dt=self.dt, sc=self.sc, gp=gp, gst=gst, g_sc=g_sc, n=self.nbytes)
-        a.update(kw)
-        return self.L.ia_point_head_loss_bwd_nhwc(
-            self.geom.ref(), C.byref(a['p']), C.byref(a['st']), a['dt'], self.B, C.byref(self.pt),
-            C.byref(self.cfg), self._p(a['sc']), self._p(self.ws), a['n'], self._p(self.res),
-            self._p(gin), C.byref(a['gp']), C.byref(a['gst']), packed, self._p(a['g_sc']), None)
+        super(_Node, self).__init__(SIZES, S.STRIDES, S.C, S.RANGES, gb, gl, iou_branch, vals, dtype, wc, wr,
+                                    SCALES if scaled else None)
 
     def run(self):
         """-> losses {key: float}, raw gradient rows {which: (g_cc, g_ri, g_sc)}"""
@@ -216,15 +154,7 @@ class _Node(object):
 
 def _maps(grads, iou_branch):
     """gradient rows -> {kind: [L] (B, ch, H, W) float64 arrays}, 'scale': (L,)"""
-    g_cc, g_ri, g_sc = grads
-    f = lambda t: t.detach().double().cpu().permute(0, 3, 1, 2).numpy()   # noqa: E731
-    m = dict(cls=[f(t[..., :S.C]) for t in g_cc], ctr=[f(t[..., S.C:S.C + 1]) for t in g_cc],
-             reg=[f(t[..., :4]) for t in g_ri])
-    if iou_branch:
-        m['iou'] = [f(t[..., 4:5]) for t in g_ri]
-    if g_sc is not None:
-        m['scale'] = g_sc.double().cpu().numpy()
-    return m
+    return G.point_row_maps(grads, iou_branch, S.C)
 
 
 def _judge(tag, got, ref32, ref64, scale):
