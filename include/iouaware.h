@@ -437,6 +437,37 @@ int ia_conv1x1_strided(const void *x, const void *W_kn, const float *bias, const
 int ia_col2im3x3_nhwc(const void *dcol, void *dx, int B, int H, int W, int C, int stride, int dtype,
                       void *stream);
 
+/* Deformable 3x3 convolution, DCN v1 / v2 (reference mmdet/ops/dcn), fp32 on channels-last tensors
+ * (csrc/deform.hip).  Ho = (H + 2 pad - (2 dil + 1)) / stride + 1, Wo likewise; dg = deformable
+ * groups, C a multiple of 4 * dg; x and col 16-byte aligned; anything else: IA_E_ARG, checked
+ * before anything is enqueued.
+ *   ia_deform_im2col3x3_nhwc   col[(b, ho, wo)][(i * 3 + j) * C + c] = mask * bilinear sample of
+ *     x[b][.][.][c] at h = ho * stride - pad + i * dil + offset[pix][g * 18 + 2 (i * 3 + j)],
+ *     w = wo * stride - pad + j * dil + offset[pix][g * 18 + 2 (i * 3 + j) + 1], g = c / (C / dg):
+ *     0 unless -1 < h < H and -1 < w < W, else the four floor / floor + 1 corners, a corner outside
+ *     the map contributing 0.  offset / mask are rows per output pixel (b, ho, wo) with the given
+ *     pixel strides in floats (>= dg * 18 / dg * 9: channel slices of a wider channels-last tensor
+ *     qualify); mask NULL: v1, no modulation; mask_logits: the mask rows hold logits, the sigmoid
+ *     is taken here.  The row order is that of ia_im2col3x3_nhwc: the convolution is
+ *     ia_linear_bias_act with rows = B * Ho * Wo, k = 9 * C.  ia_deform_im2col3x3_bytes: col's size.
+ *   ia_deform_col2im3x3_nhwc   the adjoint, from dcol = dy . W^T (ia_linear_bias_act_wt), the
+ *     derivative of the same piecewise formula (corners from floor); each output may be NULL:
+ *       dx        (B, H, W, C), ZERO-FILLED HERE, then every column element added to its four
+ *                 corners with fp32 atomics: NOT bit-reproducible from run to run;
+ *       d_offset  dense rows (pix, dg * 18), d_mask dense rows (pix, dg * 9; needs mask): sums over
+ *                 the group's channels in a fixed order, every element written, the same bits in
+ *                 every run.  mask holds values here (no logits form).                            */
+size_t ia_deform_im2col3x3_bytes(int B, int H, int W, int C, int stride, int pad, int dil);
+int ia_deform_im2col3x3_nhwc(const float *x, const float *offset, int64_t offset_pix_stride,
+                             const float *mask, int64_t mask_pix_stride, int mask_logits,
+                             float *col, int B, int H, int W, int C, int stride, int pad,
+                             int dil, int deformable_groups, void *stream);
+int ia_deform_col2im3x3_nhwc(const float *dcol, const float *x, const float *offset,
+                             int64_t offset_pix_stride, const float *mask,
+                             int64_t mask_pix_stride, float *dx, float *d_offset, float *d_mask,
+                             int B, int H, int W, int C, int stride, int pad, int dil,
+                             int deformable_groups, void *stream);
+
 /* How the library kernel of a new GEMM shape is chosen.
  *   2  FROZEN (default): the entry of the tuning table below, else the library heuristic's first
  *      result.  Nothing is timed at run time, so a process computes the same bits in every run

@@ -13,5 +13,7 @@ from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, Registry,  # 
 from . import backbones, fpn, losses, head, fcos_head, detectors        # noqa: F401  (register)
 from .api import init_detector, inference_batch                         # noqa: F401
 from .preprocess import ImageTransform                                  # noqa: F401
+from .deform_conv import (DeformConv, DeformConvPack, ModulatedDeformConv,  # noqa: F401
+                          ModulatedDeformConvPack, deform_conv, modulated_deform_conv)
 
 __version__ = '0.1.0'

@@ -191,6 +191,10 @@ SIGNATURES = {
     'ia_im2col3x3_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
     'ia_im2col3x3_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'ia_col2im3x3_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'ia_deform_im2col3x3_bytes': (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    'ia_deform_im2col3x3_nhwc': (_i, [_vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'ia_deform_col2im3x3_nhwc': (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                                      _i, _i, _vp]),
     'ia_conv1x1_strided': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'ia_gemm_table_add': (_i, [_i64, _i64, _i64, _i, _i, _i, _i]),
     'ia_gemm_table_clear': (_i, []),

@@ -6,11 +6,15 @@ hand-written kernel.  Constructor kwargs, parameter names (`conv1`, `bn1`,
 `layerN.M.conv{1,2,3}`, `layerN.M.bn{1,2,3}`, `layerN.M.downsample.{0,1}`) and
 train()/init semantics follow the reference so its configs and checkpoints
 drop in (reference mmdet/models/backbones/resnet.py:88-267,333-527;
-resnext.py:12-91,157-226).  Deformable conv, GCNet and attention plugins are
-outside the IoU-aware RetinaNet path and are rejected explicitly.
+resnext.py:12-91,157-226).  `dcn=` puts a deformable convolution (DCN v1 / v2,
+iouaware/deform_conv.py: HIP kernels, fp32) in place of conv2 of the bottlenecks of the stages
+`stage_with_dcn` names; GCNet and attention plugins are outside the IoU-aware RetinaNet path and
+are rejected explicitly, as is `dcn` on a BasicBlock (the reference refuses it too) and on a
+grouped (ResNeXt) conv2.
 """
 import math
 
+import torch
 import torch.nn as nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
@@ -22,6 +26,14 @@ def _reject_plugins(dcn, gcb, gen_attention):
     if dcn is not None or gcb is not None or gen_attention is not None:
         raise NotImplementedError('dcn / gcb / gen_attention are outside the IoU-aware '
                                   'RetinaNet hot path of this build')
+
+
+def _dcn_cfg(dcn):
+    """-> (modulated, deformable_groups, fallback_on_stride) of a `dcn=dict(...)`"""
+    if not isinstance(dcn, dict):
+        raise AssertionError('dcn must be a dict or None')
+    return (bool(dcn.get('modulated', False)), int(dcn.get('deformable_groups', 1)),
+            bool(dcn.get('fallback_on_stride', False)))
 
 
 class BasicBlock(nn.Module):
@@ -64,7 +76,7 @@ class Bottleneck(nn.Module):
         super(Bottleneck, self).__init__()
         if style not in ('pytorch', 'caffe'):
             raise AssertionError(style)
-        _reject_plugins(dcn, gcb, gen_attention)
+        _reject_plugins(None, gcb, gen_attention)
         self.inplanes, self.planes, self.stride, self.dilation = inplanes, planes, stride, dilation
         self.style, self.with_cp, self.conv_cfg, self.norm_cfg = style, with_cp, conv_cfg, norm_cfg
         s1, s2 = (1, stride) if style == 'pytorch' else (stride, 1)
@@ -76,9 +88,29 @@ class Bottleneck(nn.Module):
         self.conv1 = build_conv_layer(conv_cfg, inplanes, width, kernel_size=1, stride=s1,
                                       bias=False)
         self.add_module(self.norm1_name, n1)
-        self.conv2 = build_conv_layer(conv_cfg, width, width, kernel_size=3, stride=s2,
-                                      padding=dilation, dilation=dilation, groups=groups,
-                                      bias=False)
+        self.dcn, self.with_dcn, self.with_modulated_dcn = dcn, False, False
+        modulated, dg, fallback = _dcn_cfg(dcn) if dcn is not None else (False, 1, False)
+        if dcn is None or (fallback and s2 > 1):
+            self.conv2 = build_conv_layer(conv_cfg, width, width, kernel_size=3, stride=s2,
+                                          padding=dilation, dilation=dilation, groups=groups,
+                                          bias=False)
+        else:
+            # conv2 as a deformable convolution; its offsets (modulated: and mask logits) come from
+            # conv2_offset, an ordinary convolution of the same geometry on the same input.
+            # dg * 18 offset channels, modulated dg * 27: offsets first, then dg * 9 mask logits
+            # (the reference slices a literal 18 / 9: the same for dg = 1)
+            from .deform_conv import DeformConv, ModulatedDeformConv
+            if conv_cfg is not None:
+                raise AssertionError('conv_cfg must be None for DCN')
+            if groups != 1:
+                raise NotImplementedError('dcn with groups=%d (ResNeXt): the HIP deformable '
+                                          'convolution supports groups=1 only' % groups)
+            self.with_dcn, self.with_modulated_dcn, self.deformable_groups = True, modulated, dg
+            self.conv2_offset = nn.Conv2d(width, dg * (27 if modulated else 18), 3, stride=s2,
+                                          padding=dilation, dilation=dilation)
+            self.conv2 = (ModulatedDeformConv if modulated else DeformConv)(
+                width, width, 3, stride=s2, padding=dilation, dilation=dilation,
+                deformable_groups=dg, bias=False)
         self.add_module(self.norm2_name, n2)
         self.conv3 = build_conv_layer(conv_cfg, width, planes * self.expansion, kernel_size=1,
                                       bias=False)
@@ -90,9 +122,21 @@ class Bottleneck(nn.Module):
     norm2 = property(lambda self: getattr(self, self.norm2_name))
     norm3 = property(lambda self: getattr(self, self.norm3_name))
 
+    def _conv2(self, out):
+        if not self.with_dcn:
+            return self.conv2(out)
+        if out.dtype in (torch.bfloat16, torch.float16):
+            raise TypeError('dcn: the deformable conv2 of this block is fp32 only, got a %s '
+                            'activation (a bf16 network with DCN blocks is not supported)' % out.dtype)
+        om = self.conv2_offset(out)
+        if not self.with_modulated_dcn:
+            return self.conv2(out, om)
+        n = 18 * self.deformable_groups
+        return self.conv2(out, om[:, :n], om[:, n:].sigmoid())
+
     def _residual(self, x):
         out = self.relu(self.norm1(self.conv1(x)))
-        out = self.relu(self.norm2(self.conv2(out)))
+        out = self.relu(self.norm2(self._conv2(out)))
         out = self.norm3(self.conv3(out))
         return out + (x if self.downsample is None else self.downsample(x))
 
@@ -159,7 +203,11 @@ class ResNet(nn.Module):
             raise AssertionError('strides / dilations must have num_stages entries')
         if max(out_indices) >= num_stages:
             raise AssertionError('out_indices exceed num_stages')
-        _reject_plugins(dcn, gcb, gen_attention)
+        _reject_plugins(None, gcb, gen_attention)
+        if dcn is not None:
+            _dcn_cfg(dcn)
+            if len(stage_with_dcn) != num_stages:
+                raise AssertionError('stage_with_dcn must have num_stages entries')
         self.depth, self.num_stages, self.strides, self.dilations = depth, num_stages, strides, dilations
         self.out_indices, self.style, self.frozen_stages = out_indices, style, frozen_stages
         self.conv_cfg, self.norm_cfg, self.with_cp, self.norm_eval = conv_cfg, norm_cfg, with_cp, norm_eval
@@ -183,8 +231,9 @@ class ResNet(nn.Module):
             planes = 64 * 2 ** i
             layer = make_res_layer(self.block, self.inplanes, planes, nblocks, stride=strides[i],
                                    dilation=dilations[i], style=style, with_cp=with_cp,
-                                   conv_cfg=conv_cfg, norm_cfg=norm_cfg, groups=self._groups,
-                                   base_width=self._base_width)
+                                   conv_cfg=conv_cfg, norm_cfg=norm_cfg,
+                                   dcn=dcn if dcn is not None and stage_with_dcn[i] else None,
+                                   groups=self._groups, base_width=self._base_width)
             self.inplanes = planes * self.block.expansion
             name = 'layer{}'.format(i + 1)
             self.add_module(name, layer)
@@ -218,6 +267,10 @@ class ResNet(nn.Module):
                 kaiming_init(m)
             elif isinstance(m, (_BatchNorm, nn.GroupNorm)):
                 constant_init(m, 1)
+        if self.dcn is not None:
+            for m in self.modules():
+                if isinstance(m, Bottleneck) and hasattr(m, 'conv2_offset'):
+                    constant_init(m.conv2_offset, 0)
         if self.zero_init_residual:
             for m in self.modules():
                 if isinstance(m, Bottleneck):

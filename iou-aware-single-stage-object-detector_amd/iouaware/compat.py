@@ -30,6 +30,9 @@ def install(force=False):
         raise RuntimeError('a different `mmdet` is already imported')
     from . import (anchors, api, bbox, detectors, fpn, head, layers, losses, nms_op, registry,
                    targets, backbones, dist as idist, focal_op, preprocess, fcos_head)
+    # (the package attribute `deform_conv` is the function; the module is reached by its full name)
+    import importlib
+    dcn = importlib.import_module(__package__ + '.deform_conv')
     root = _mod('mmdet', __version__='0.6.0+iouaware', __iouaware__=True)
     models = _mod('mmdet.models', **{k: getattr(registry, k) for k in (
         'BACKBONES', 'NECKS', 'ROI_EXTRACTORS', 'SHARED_HEADS', 'HEADS', 'LOSSES', 'DETECTORS',
@@ -77,6 +80,11 @@ def install(force=False):
                 SigmoidFocalLoss=focal_op.SigmoidFocalLoss,
                 sigmoid_focal_loss=focal_op.sigmoid_focal_loss)
     mops.nms_module, mops.sigmoid_focal_loss_module = ops_nms, ops_fl
+    dcn_names = {k: getattr(dcn, k) for k in ('DeformConv', 'DeformConvPack', 'ModulatedDeformConv',
+                                              'ModulatedDeformConvPack', 'deform_conv',
+                                              'modulated_deform_conv')}
+    mops.__dict__.update(dcn_names)
+    mops.dcn = _mod('mmdet.ops.dcn', **dcn_names)
 
     core = _mod('mmdet.core', AnchorGenerator=anchors.AnchorGenerator,
                 anchor_target=targets.anchor_target, delta2bbox=bbox.delta2bbox,

@@ -28,6 +28,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 
 from . import ops, train_fuse
 from .backbones import BasicBlock, Bottleneck, ResNet
+from .deform_conv import _DeformBase, _one
 from .layers import ConvModule, Scale
 from .winograd import plain_3x3
 
@@ -83,6 +84,8 @@ def _stamp_slots(module):
                 slots.append((m._parameters, 'bias'))
             elif isinstance(m, Scale):
                 slots.append((m._parameters, 'scale'))
+            elif isinstance(m, _DeformBase):                   # the deformable conv2 of a DCN block
+                slots.append((m._parameters, 'weight'))
     return slots, links
 
 
@@ -147,6 +150,32 @@ def _bottleneck_forward(self, x):
     return _bottleneck_run(self, x)[0]
 
 
+def _dcn_conv2(self, f, out):
+    """conv2 + folded BN + ReLU of a DCN block (backbones.Bottleneck._conv2) on the inference route:
+    conv2_offset on the own route that takes its shape -- im2col + GEMM where it has a stride,
+    Winograd at stride 1 where its output channels are a multiple of 4 (deformable_groups 2, 4, ..),
+    else the framework's convolution -- then the deformable im2col + the library GEMM with BN2
+    folded into weight and bias and ReLU in the epilogue; the modulated form hands the mask logits
+    over as they are (the sigmoid is taken in the kernel)"""
+    if out.dtype != torch.float32:
+        raise TypeError('dcn: the deformable conv2 of this block is fp32 only, got a %s activation '
+                        '(a bf16 network with DCN blocks is not supported)' % out.dtype)
+    if 'dcn2' not in f or not out.is_contiguous(memory_format=torch.channels_last):
+        return ops.channel_affine_act_(self._conv2(out), f['s2'], f['b2'], relu=True)
+    co, c2 = self.conv2_offset, self.conv2
+    if 'off_im2col' in f:
+        om = ops.conv3x3_im2col(out, f['off_im2col'], f['off_b'], stride=co.stride[0])
+    elif 'off_wino' in f and f['off_wino'].usable(out):
+        om = f['off_wino'](out)
+    else:
+        om = co(out).contiguous(memory_format=torch.channels_last)
+    n = 18 * self.deformable_groups
+    return ops.deform_conv3x3(out, om[:, :n], om[:, n:] if self.with_modulated_dcn else None, f['dcn2'],
+                              f['b2'], _one(c2.stride, 'stride'), _one(c2.padding, 'padding'),
+                              _one(c2.dilation, 'dilation'), self.deformable_groups, relu=True,
+                              mask_logits=True)
+
+
 def _bottleneck_run(self, x, h1=None, nxt=None):
     """-> (y, h).  h1: this block's conv1 + bn1 + ReLU output, already computed by the block in
     front (chained stage-1 boundary, ops.conv1x1_chain); nxt: the next block's folded copies -- the
@@ -171,7 +200,13 @@ def _bottleneck_run(self, x, h1=None, nxt=None):
         out, pre = self.conv1(x), (f['s1'], f['b1'], True)
     gw = f.get('gconv2')
     wino = f.get('wino2')
-    if gw is not None and out.dtype == torch.float32 \
+    if getattr(self, 'with_dcn', False):
+        # deformable conv2: in front of the Winograd / grouped / bf16 branches, none of which
+        # takes it (their folded copies are not made for a DCN block either, _fold)
+        if pre is not None:
+            out = ops.channel_affine_act_(out, f['s1'], f['b1'], relu=True)
+        out = _dcn_conv2(self, f, out)
+    elif gw is not None and out.dtype == torch.float32 \
             and out.is_contiguous(memory_format=torch.channels_last):
         # ResNeXt: grouped 3x3 conv2 + folded BN + ReLU on the MFMA kernel of csrc/gconv.hip
         if pre is not None:
@@ -238,6 +273,8 @@ def _chain_ok(blk, nxt, x):
     f, g = getattr(blk, '_ia_fused', None), getattr(nxt, '_ia_fused', None)
     if f is None or g is None or 'w3' not in f or 'w1' not in g or nxt.downsample is not None:
         return False
+    if getattr(blk, 'with_dcn', False) or getattr(nxt, 'with_dcn', False):
+        return False                      # DCN blocks run on their own, through _bottleneck_run's branch
     if blk.downsample is not None and 'wd' not in f:
         return False
     k, n = f['w3'].shape
@@ -541,16 +578,29 @@ def _fold(m):
                         f['wd_conv'] = (ds.weight.float() * f['sd'].view(-1, 1, 1, 1)).contiguous(
                             memory_format=torch.channels_last)
         c2 = m.conv2
-        if winograd and c2.groups > 1 and tuple(c2.kernel_size) == (3, 3) \
+        dcn = getattr(m, 'with_dcn', False)
+        if dcn and winograd and 'w1' in f and c2.in_channels % (4 * m.deformable_groups) == 0 \
+                and c2.groups == 1 and tuple(c2.kernel_size) == (3, 3) and c2.weight.dtype == torch.float32:
+            co = m.conv2_offset
+            f['dcn2'] = ops.conv3x3_weight_kn(c2.weight, f['s2'])            # BN scale folded in
+            if _im2col_ok(co):
+                f['off_im2col'] = ops.conv3x3_weight_kn(co.weight)
+                f['off_b'] = None if co.bias is None else co.bias.detach().float().contiguous()
+            elif _wino_ok(co):
+                from .winograd import WinogradConv3x3
+                f['off_wino'] = WinogradConv3x3(co.weight, co.bias, relu=False)
+        if dcn:
+            pass                           # none of the plain-convolution copies below
+        elif winograd and c2.groups > 1 and tuple(c2.kernel_size) == (3, 3) \
                 and tuple(c2.padding) == (1, 1) and tuple(c2.dilation) == (1, 1) \
                 and c2.stride[0] == c2.stride[1] and c2.stride[0] in (1, 2) and c2.bias is None \
                 and c2.in_channels == c2.out_channels \
                 and c2.in_channels // c2.groups in (4, 8, 16, 32) \
                 and c2.in_channels % (32 if c2.in_channels // c2.groups == 32 else 16) == 0:
             f['gconv2'] = ops.pack_grouped_weight(c2.weight, f['s2'])     # BN scale folded in
-        if winograd and _im2col_ok(c2) and c2.bias is None and 'w1' in f:
+        if not dcn and winograd and _im2col_ok(c2) and c2.bias is None and 'w1' in f:
             f['im2col2'] = ops.conv3x3_weight_kn(c2.weight, f['s2'])         # BN scale folded in
-        if winograd and _wino_ok(m.conv2) and m.conv2.bias is None:
+        if not dcn and winograd and _wino_ok(m.conv2) and m.conv2.bias is None:
             from .winograd import WinogradConv3x3
             with torch.no_grad():           # BN scale folded into the weights, shift = bias
                 w2 = m.conv2.weight.float() * f['s2'].view(-1, 1, 1, 1)

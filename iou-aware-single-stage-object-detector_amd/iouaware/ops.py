@@ -1152,6 +1152,198 @@ def conv3x3_weight_kn(weight, scale=None):
     return w.permute(2, 3, 1, 0).reshape(9 * w.shape[1], w.shape[0]).contiguous()
 
 
+# ------------------------------------------------------------------ deformable 3x3 convolution
+# the column buffer of one chunk of images stays under this many bytes (deform_conv3x3 and its
+# backward process the batch in chunks of whole images; one image is the smallest chunk)
+DEFORM_COL_CAP = 256 << 20
+
+
+def deform_out_hw(H, W, stride, padding, dilation):
+    e = 2 * int(dilation) + 1
+    return (H + 2 * padding - e) // stride + 1, (W + 2 * padding - e) // stride + 1
+
+
+def _rows_ps(t, what, B, ch, Ho, Wo):
+    """pixel stride (floats) of an fp32 (B, ch, Ho, Wo) tensor whose channels are contiguous per
+    pixel and whose pixels are evenly spaced in (b, ho, wo) order: a channels-last tensor or a
+    channel slice of one"""
+    if t.dtype != torch.float32:
+        raise TypeError('%s must be float32, got %s' % (what, t.dtype))
+    if tuple(t.shape) != (B, ch, Ho, Wo):
+        raise ValueError('%s must have shape %s, got %s' % (what, (B, ch, Ho, Wo), tuple(t.shape)))
+    ps = t.stride(3) if Wo > 1 else (t.stride(2) if Ho > 1 else (t.stride(0) if B > 1 else ch))
+    if t.stride(1) != 1 or ps < ch or (Ho > 1 and Wo > 1 and t.stride(2) != Wo * ps) \
+            or (B > 1 and t.stride(0) != Ho * Wo * ps):
+        raise ValueError('%s must be channels-last (or a channel slice of a channels-last tensor)' % what)
+    return int(ps)
+
+
+def _deform_check(x, offset, mask, stride, padding, dilation, dg):
+    _require_gpu(x, 'x')
+    _require_gpu(offset, 'offset')
+    if x.dtype != torch.float32:
+        raise TypeError('the deformable convolution kernels are fp32, got %s' % x.dtype)
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('x must be a channels-last (B, C, H, W) tensor')
+    stride, padding, dilation, dg = int(stride), int(padding), int(dilation), int(dg)
+    if stride < 1 or padding < 0 or dilation < 1 or dg < 1:
+        raise ValueError('stride / dilation / deformable_groups >= 1, padding >= 0')
+    B, Cc, H, W = (int(v) for v in x.shape)
+    if Cc % (4 * dg):
+        raise ValueError('deformable_groups: C = %d must be a multiple of 4 * deformable_groups = %d'
+                         % (Cc, 4 * dg))
+    Ho, Wo = deform_out_hw(H, W, stride, padding, dilation)
+    if Ho < 1 or Wo < 1:
+        raise ValueError('the %d x %d map is smaller than the dilated kernel' % (H, W))
+    ops_ = _rows_ps(offset, 'offset', B, dg * 18, Ho, Wo)
+    mps = 0
+    if mask is not None:
+        _require_gpu(mask, 'mask')
+        mps = _rows_ps(mask, 'mask', B, dg * 9, Ho, Wo)
+    return B, Cc, H, W, Ho, Wo, ops_, mps, (stride, padding, dilation, dg)
+
+
+def deform_im2col3x3(x, offset, mask=None, stride=1, padding=1, dilation=1, deformable_groups=1,
+                     mask_logits=False, out=None):
+    """the deformable column matrix (csrc/deform.hip, k_deform_im2col) of a channels-last fp32
+    (B, C, H, W) tensor: (B * Ho * Wo, 9 * C), row order of im2col3x3.  offset (B, dg * 18, Ho, Wo)
+    and mask (B, dg * 9, Ho, Wo; None: v1) channels-last or channel slices of a channels-last tensor;
+    mask_logits: the sigmoid is taken in the kernel.  Returns `out` (a contiguous fp32 matrix) or a
+    VIEW OF THE COLUMN BUFFER of this (device, stream), see im2col3x3."""
+    B, Cc, H, W, Ho, Wo, ops_, mps, (s, p, d, dg) = _deform_check(x, offset, mask, stride, padding,
+                                                                 dilation, deformable_groups)
+    rows = B * Ho * Wo
+    nbytes = rows * 9 * Cc * 4
+    if out is None:
+        col = _col_buffer(x.device, nbytes)
+    else:
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * 9 * Cc:
+            raise ValueError('out must be a contiguous fp32 (B * Ho * Wo, 9 * C) matrix')
+        col = out
+    _lib.check(_lib.lib().ia_deform_im2col3x3_nhwc(_ptr(x), _ptr(offset), ops_, _ptr(mask), mps,
+                                                   int(bool(mask_logits)), _ptr(col), B, H, W, Cc, s, p, d, dg,
+                                                   _stream()), 'ia_deform_im2col3x3_nhwc')
+    return out if out is not None else col[:nbytes].view(torch.float32).view(rows, 9 * Cc)
+
+
+def deform_col2im3x3(dcol, x, offset, mask=None, stride=1, padding=1, dilation=1, deformable_groups=1,
+                     need=(True, True, True), out=None):
+    """the adjoint of deform_im2col3x3 (k_deform_col2im) from dcol (B * Ho * Wo, 9 * C) ->
+    (dx, d_offset, d_mask), each None where `need` says so (d_mask also when mask is None):
+      dx        channels-last (B, C, H, W); zero-filled by the entry, then fp32 atomicAdd of every
+                column element to its four corners: NOT bit-reproducible from run to run (the one
+                such place on the training routes);
+      d_offset  (B, dg * 18, Ho, Wo) and d_mask (B, dg * 9, Ho, Wo), channels-last: sums over the
+                group's channels in a fixed order -- the same bits in every run.
+    out: optional (dx, d_offset, d_mask) tensors of those shapes and layouts to write into."""
+    B, Cc, H, W, Ho, Wo, ops_, mps, (s, p, d, dg) = _deform_check(x, offset, mask, stride, padding,
+                                                                 dilation, deformable_groups)
+    _require_gpu(dcol, 'dcol')
+    rows = B * Ho * Wo
+    if dcol.dtype != torch.float32 or not dcol.is_contiguous() or dcol.numel() != rows * 9 * Cc:
+        raise ValueError('dcol must be a contiguous fp32 (B * Ho * Wo, 9 * C) matrix')
+    cl = torch.channels_last
+    shapes = ((B, Cc, H, W), (B, dg * 18, Ho, Wo), (B, dg * 9, Ho, Wo))
+    want = (bool(need[0]), bool(need[1]), bool(need[2]) and mask is not None)
+    res = []
+    for i in range(3):
+        t = None
+        if want[i]:
+            t = out[i] if out is not None and out[i] is not None else \
+                torch.empty(shapes[i], dtype=torch.float32, device=x.device, memory_format=cl)
+            if tuple(t.shape) != shapes[i] or t.dtype != torch.float32 or not t.is_contiguous(memory_format=cl):
+                raise ValueError('out[%d] must be a channels-last fp32 tensor of shape %s' % (i, shapes[i]))
+        res.append(t)
+    if not any(want):
+        return None, None, None
+    _lib.check(_lib.lib().ia_deform_col2im3x3_nhwc(_ptr(dcol), _ptr(x), _ptr(offset), ops_, _ptr(mask), mps,
+                                                   _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), B, H, W, Cc,
+                                                   s, p, d, dg, _stream()), 'ia_deform_col2im3x3_nhwc')
+    return tuple(res)
+
+
+def _deform_chunk(x, stride, padding, dilation, col_cap):
+    """images per chunk: the column matrix of a chunk stays under col_cap bytes (at least one image)"""
+    B, Cc, H, W = x.shape
+    Ho, Wo = deform_out_hw(H, W, stride, padding, dilation)
+    per_image = max(Ho * Wo, 1) * 9 * Cc * 4
+    cap = DEFORM_COL_CAP if col_cap is None else int(col_cap)
+    return max(1, min(int(B), cap // per_image))
+
+
+def deform_conv3x3(x, offset, mask, w_kn, bias=None, stride=1, padding=1, dilation=1, deformable_groups=1,
+                   relu=False, mask_logits=False, col_cap=None, out=None):
+    """relu?(deformable conv3x3(x; offset, mask) + bias) of a channels-last fp32 (B, C, H, W) tensor
+    -> channels-last (B, Cout, Ho, Wo): deform_im2col3x3 + the library GEMM with bias / ReLU in its
+    epilogue, the batch in chunks of whole images whose column matrix stays under `col_cap` bytes
+    (default DEFORM_COL_CAP).  w_kn: (9 * C, Cout), `conv3x3_weight_kn(weight)`."""
+    B, Cc, H, W, Ho, Wo, _, _, (s, p, d, dg) = _deform_check(x, offset, mask, stride, padding, dilation,
+                                                             deformable_groups)
+    if w_kn.dim() != 2 or int(w_kn.shape[0]) != 9 * Cc or not w_kn.is_contiguous() or w_kn.dtype != torch.float32:
+        raise ValueError('weight must be a contiguous fp32 (9 * C, Cout) matrix')
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError('bias must be fp32')
+    n = int(w_kn.shape[1])
+    if out is None:
+        out = torch.empty((B, n, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    elif tuple(out.shape) != (B, n, Ho, Wo) or out.dtype != torch.float32 \
+            or not out.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('out must be a channels-last fp32 (B, Cout, Ho, Wo) tensor')
+    _ensure_gemm_table()
+    ws = _workspace(x.device, _LT_WS_BYTES)
+    L = _lib.lib()
+    step = _deform_chunk(x, s, p, d, col_cap)
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        col = deform_im2col3x3(x[b0:b1], offset[b0:b1], None if mask is None else mask[b0:b1], s, p, d, dg,
+                               mask_logits)
+        _lib.check(L.ia_linear_bias_act(_ptr(col), _ptr(w_kn), _ptr(bias), None, _ptr(out[b0:b1]),
+                                        (b1 - b0) * Ho * Wo, 9 * Cc, n, int(bool(relu)), _ptr(ws),
+                                        _LT_WS_BYTES, _stream()), 'ia_linear_bias_act (deform)')
+    return out
+
+
+def deform_conv3x3_backward(g, x, offset, mask, w_kn, stride=1, padding=1, dilation=1, deformable_groups=1,
+                            need=(True, True, True, True), col_cap=None, out=None):
+    """the three backward launches of deform_conv3x3 per chunk of images, from the channels-last fp32
+    output gradient g (B, Cout, Ho, Wo):  dcol = g . w_kn^T (conv3x3_dcol),  the adjoint gather
+    (deform_col2im3x3: dx by atomics, d_offset / d_mask reproducible),  and, with col built again
+    (as train_fuse.conv3x3_strided does),  dW = g^T . col (gemm_tn), the chunks added in order.
+    -> (dx, d_offset, d_mask, dW as (Cout, 9 * C)), None where `need` says so.
+    out: optional (dx, d_offset, d_mask) to write into."""
+    B, Cc, H, W, Ho, Wo, _, _, (s, p, d, dg) = _deform_check(x, offset, mask, stride, padding, dilation,
+                                                             deformable_groups)
+    n = int(w_kn.shape[1])
+    if g.dtype != torch.float32 or tuple(g.shape) != (B, n, Ho, Wo) \
+            or not g.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('g must be a channels-last fp32 (B, Cout, Ho, Wo) tensor')
+    cl = torch.channels_last
+    want = (bool(need[0]), bool(need[1]), bool(need[2]) and mask is not None)
+    shapes = ((B, Cc, H, W), (B, dg * 18, Ho, Wo), (B, dg * 9, Ho, Wo))
+    res = [None, None, None]
+    for i in range(3):
+        if want[i]:
+            res[i] = out[i] if out is not None and out[i] is not None else \
+                torch.empty(shapes[i], dtype=torch.float32, device=x.device, memory_format=cl)
+    dw = None
+    step = _deform_chunk(x, s, p, d, col_cap)
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        xc, oc, gc = x[b0:b1], offset[b0:b1], g[b0:b1]
+        mc = None if mask is None else mask[b0:b1]
+        if any(want):
+            # dcol and (below) the recomputed col are views of the ONE column buffer of this stream;
+            # on one stream program order keeps the reader of each in front of the next writer
+            dcol = conv3x3_dcol(gc, w_kn)
+            deform_col2im3x3(dcol, xc, oc, mc, s, p, d, dg, need=want,
+                             out=tuple(None if t is None else t[b0:b1] for t in res))
+        if need[3]:
+            col = deform_im2col3x3(xc, oc, mc, s, p, d, dg)
+            part = gemm_tn(gc.permute(0, 2, 3, 1).reshape(-1, n), col)
+            dw = part if dw is None else dw.add_(part)
+    return res[0], res[1], res[2], dw
+
+
 def conv1x1_strided(x, w_kn, bias=None, residual=None, stride=2, relu=False):
     """1x1 / stride-s convolution of a channels-last (B, k, H, W) tensor -> (B, n, Ho, Wo):
     relu?(x[:, :, ::s, ::s] . w_kn + bias + residual) as one strided-batched library GEMM reading

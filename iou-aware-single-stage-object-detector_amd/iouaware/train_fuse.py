@@ -402,6 +402,8 @@ def frozen(module, x):
 
 def bottleneck_usable(m, x):
     c2 = m.conv2
+    if getattr(m, 'with_dcn', False):
+        return False                 # DCN block: the module forward, conv2 on the deform_conv autograd op
     return (torch.is_grad_enabled() and _act_ok(x) and not m.with_cp
             and _eval_bn(m.norm1) and _eval_bn(m.norm2) and _eval_bn(m.norm3)
             and _gemm_ok(m.conv1) and _gemm_ok(m.conv3)
