@@ -1275,6 +1275,76 @@ int ia_point_head_loss_bwd_nhwc(const ia_point_head_geom *g, const ia_point_leve
                                 const ia_point_level_ptrs *grads, const ia_point_pix_strides *grad_strides,
                                 int grad_rows_packed, float *grad_scale, void *stream);
 
+/* ------------------------------------------------------------------ masked convolution
+ * (reference mmdet/ops/masked_conv): a stride-1 convolution evaluated only where a (B, H, W) mask is
+ * set, exactly 0 elsewhere.  fp32, channels-last.  Four stages; the GEMM between the gather and the
+ * scatter is ia_linear_bias_act on the caller's side (its row count is a host value).
+ *
+ * ia_mask_compact: mask (total = B * H * W bytes, nonzero = kept) -> idx (ascending flat pixel
+ *     indices b * H * W + y * W + x of the kept pixels; total entries of room), rank (total int32:
+ *     the pixel's row in idx, or -1), count (1 int32: the number kept).  Wave ballots, a prefix
+ *     scan over the per-workgroup counts, no atomics: the same row order in every run.
+ *     Workspace: ia_mask_compact_workspace_bytes(total).
+ * ia_logit_compact: the same from fp32 logits, a pixel kept where sigmoid(logit) >= thr (0 <= thr <= 1),
+ *     the expression ia_guided_rowmax / ia_guided_gather_decode apply to their `loc` maps: the masked
+ *     layers and the decode agree on every location.  No mask tensor, no extra launch.
+ * ia_masked_im2col: col[r][tap * C + c] for the rows [row0, row0 + rows) of the compacted order --
+ *     the im2col row (ksize 3: pad 1, row order of ia_im2col3x3_nhwc; ksize 1: the pixel's own C
+ *     values) of pixel idx[row0 + r] for row0 + r < count, zeros from the count on.  C % 4 == 0,
+ *     x and col 16-byte aligned.  count is the host's copy of ia_mask_compact's.
+ * ia_masked_scatter: out (total, n) channels-last rows from the GEMM result y (rows of ld floats,
+ *     row r = kept pixel r): out[p][c] = rank[p] >= 0 ? y[rank[p]][c] : +0.0f.  Every element is
+ *     written exactly once; y may be NULL when nothing is kept.                                    */
+size_t ia_mask_compact_workspace_bytes(int64_t total);
+int ia_mask_compact(const uint8_t *mask, int64_t total, int32_t *idx, int32_t *rank, int32_t *count,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int ia_logit_compact(const float *logits, float thr, int64_t total, int32_t *idx, int32_t *rank,
+                     int32_t *count, void *workspace, size_t workspace_bytes, void *stream);
+int ia_masked_im2col(const float *x, const int32_t *idx, int64_t count, int64_t row0, int64_t rows,
+                     float *col, int B, int H, int W, int C, int ksize, void *stream);
+int ia_masked_scatter(const float *y, int64_t ld, const int32_t *rank, float *out, int64_t total,
+                      int n, void *stream);
+
+/* ------------------------------------------------------------------ guided-anchor decode
+ * Post-conv path of IoUawareGARetinaHead (reference iou_aware_ga_retina_head.py get_bboxes on
+ * guided_anchor_head.py get_anchors): one square anchor per location (head.num_anchors must be 1,
+ * base_anchors[l][0]), the guided anchor delta2bbox(square, [0, 0, shape], anchoring_means,
+ * anchoring_stds, wh_ratio_clip 1e-6) without an image clamp, the box delta2bbox(guided anchor,
+ * bbox_pred, head.means, head.stds) clamped to the image; score sigmoid(cls) * sigmoid(iou); a
+ * location is kept when !use_loc_filter or sigmoid(loc) >= loc_filter_thr.  fp32 NCHW maps,
+ * sigmoid classification (head.layout IA_LAYOUT_NCHW, head.cls_activation IA_CLS_SIGMOID).
+ *
+ * ia_guided_rowmax: rowmax (B, N): the kept location's maximum over classes of the score, +0.0f
+ *     for a filtered-out one (the top-k's keys are ordered for scores >= 0); then ia_select_topk.
+ * ia_guided_gather_decode: boxes (B, R, 4), scores_t (B, C, Rs), best_score (B, R) of the selected
+ *     candidates; a filtered-out candidate gets a zero box, zero scores and best_score 0, which the
+ *     NMS skips at any score_thr >= 0.
+ * ia_guided_get_bboxes: the two kernels, ia_select_topk and ia_multiclass_nms in one call, on a
+ *     workspace of ia_guided_get_bboxes_workspace_bytes (256-byte aligned; the workspace of
+ *     ia_get_bboxes for the same head geometry, carved up the same way: ia_guided_workspace_layout).  score_thr < 0: IA_E_ARG.  An image without a
+ *     kept location gives num = 0.                                                                */
+typedef struct ia_guided_geom {
+    ia_head_geom head;
+    float anchoring_means[4], anchoring_stds[4];
+    float loc_filter_thr;
+    int32_t use_loc_filter;
+} ia_guided_geom;
+typedef struct ia_guided_level_ptrs {
+    const void *cls[IA_MAX_LEVELS], *reg[IA_MAX_LEVELS], *iou[IA_MAX_LEVELS];
+    const void *shape[IA_MAX_LEVELS], *loc[IA_MAX_LEVELS];
+} ia_guided_level_ptrs;
+int ia_guided_rowmax(const ia_guided_geom *g, const ia_guided_level_ptrs *p, int batch, float *rowmax,
+                     void *stream);
+int ia_guided_gather_decode(const ia_guided_geom *g, const ia_guided_level_ptrs *p, int batch,
+                            const int32_t *cand_idx, const float *img_hw, const float *scale_factor,
+                            int rescale, float *boxes, float *scores_t, float *best_score, void *stream);
+size_t ia_guided_get_bboxes_workspace_bytes(const ia_guided_geom *g, int batch);
+int ia_guided_workspace_layout(const ia_guided_geom *g, int batch, size_t offsets[8]);
+int ia_guided_get_bboxes(const ia_guided_geom *g, const ia_guided_level_ptrs *p, int batch,
+                         const float *img_hw, const float *scale_factor, int rescale, float score_thr,
+                         float iou_thr, int max_per_img, void *workspace, size_t workspace_bytes,
+                         float *dets, int32_t *labels, int32_t *rows, int32_t *num, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

@@ -47,6 +47,15 @@ static int ws_layout(const ia_head_geom *g, int batch, WsLayout &w)
     return 0;
 }
 
+int get_bboxes_select_offset(const ia_head_geom *g, int batch, size_t *offset)
+{
+    WsLayout w;
+    int rc = ws_layout(g, batch, w);
+    if (rc) return rc;
+    *offset = w.off[8];
+    return 0;
+}
+
 __global__ void k_test_math(int op, const float *x, const float *y, float *out, int64_t n)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;

@@ -181,6 +181,10 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
                         float *scores_t, float *best_score, int Rs, int kind, float score_thr,
                         int dtype, hipStream_t s);
 
+// byte offset of the top-k workspace inside the ia_get_bboxes workspace of (g, batch) (capi.hip): for
+// the decode stages of other heads that run on that workspace (guideddecode.hip)
+int get_bboxes_select_offset(const ia_head_geom *g, int batch, size_t *offset);
+
 // the IoU maps the score kind needs: every level's iou pointer set (IoU-aware kinds) or every one
 // NULL (IA_CLS_*_NOIOU)
 inline int check_iou_ptrs(const LevelTable &t, const ia_level_ptrs &p)

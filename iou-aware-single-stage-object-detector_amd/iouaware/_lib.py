@@ -101,6 +101,19 @@ class PointLossCfg(C.Structure):
                 ('exact_large_logits', C.c_int32)]
 
 
+class GuidedGeom(C.Structure):
+    """ia_guided_geom"""
+    _fields_ = [('head', HeadGeom), ('anchoring_means', C.c_float * 4), ('anchoring_stds', C.c_float * 4),
+                ('loc_filter_thr', C.c_float), ('use_loc_filter', C.c_int32)]
+
+
+class GuidedLevelPtrs(C.Structure):
+    """ia_guided_level_ptrs"""
+    _fields_ = [('cls', C.c_void_p * IA_MAX_LEVELS), ('reg', C.c_void_p * IA_MAX_LEVELS),
+                ('iou', C.c_void_p * IA_MAX_LEVELS), ('shape', C.c_void_p * IA_MAX_LEVELS),
+                ('loc', C.c_void_p * IA_MAX_LEVELS)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('src_h', C.c_int32), ('src_w', C.c_int32),
                 ('dst_h', C.c_int32), ('dst_w', C.c_int32), ('flip', C.c_int32)]
@@ -129,6 +142,7 @@ _G, _P = C.POINTER(HeadGeom), C.POINTER(LevelPtrs)
 _PG, _WG = C.POINTER(PointHeadGeom), C.POINTER(WinoGeom)
 _PP, _PT, _PC = C.POINTER(PointLevelPtrs), C.POINTER(PointTargets), C.POINTER(PointLossCfg)
 _PS = C.POINTER(PointPixStrides)
+_GG, _GP = C.POINTER(GuidedGeom), C.POINTER(GuidedLevelPtrs)
 
 # name -> (restype, argtypes); mirrors include/iouaware.h one to one
 SIGNATURES = {
@@ -328,6 +342,16 @@ SIGNATURES = {
     'ia_point_head_loss_fwd_nhwc': (_i, [_PG, _PP, _PS, _i, _i, _PT, _PC, _vp, _vp, _sz, _vp, _vp]),
     'ia_point_head_loss_bwd_nhwc': (_i, [_PG, _PP, _PS, _i, _i, _PT, _PC, _vp, _vp, _sz, _vp, _vp, _PP,
                                          _PS, _i, _vp, _vp]),
+    'ia_mask_compact_workspace_bytes': (_sz, [_i64]),
+    'ia_mask_compact': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ia_logit_compact': (_i, [_vp, _f, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ia_masked_im2col': (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
+    'ia_masked_scatter': (_i, [_vp, _i64, _vp, _vp, _i64, _i, _vp]),
+    'ia_guided_rowmax': (_i, [_GG, _GP, _i, _vp, _vp]),
+    'ia_guided_gather_decode': (_i, [_GG, _GP, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'ia_guided_get_bboxes_workspace_bytes': (_sz, [_GG, _i]),
+    'ia_guided_workspace_layout': (_i, [_GG, _i, C.POINTER(_sz * 8)]),
+    'ia_guided_get_bboxes': (_i, [_GG, _GP, _i, _vp, _vp, _i, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

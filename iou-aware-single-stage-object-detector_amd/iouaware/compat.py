@@ -7,7 +7,7 @@ layout finds this build's implementations:
     from mmdet.ops import sigmoid_focal_loss          # -> HIP focal-loss op
     from mmdet.core import bbox2result, multiclass_nms, delta2bbox ...
 
-Only the names on the IoU-aware RetinaNet and FCOS paths exist (SURVEY.md section 8);
+Only the names on the IoU-aware RetinaNet, FCOS and GA-RetinaNet (inference) paths exist (SURVEY.md section 8);
 everything else of mmdetection is deliberately absent.
 """
 import sys
@@ -29,7 +29,8 @@ def install(force=False):
             return existing
         raise RuntimeError('a different `mmdet` is already imported')
     from . import (anchors, api, bbox, detectors, fpn, head, layers, losses, nms_op, registry,
-                   targets, backbones, dist as idist, focal_op, preprocess, fcos_head)
+                   targets, backbones, dist as idist, focal_op, preprocess, fcos_head, ga_head,
+                   masked_conv)
     # (the package attribute `deform_conv` is the function; the module is reached by its full name)
     import importlib
     dcn = importlib.import_module(__package__ + '.deform_conv')
@@ -51,7 +52,9 @@ def install(force=False):
                                IoUawareRetinaHead=head.IoUawareRetinaHead,
                                RetinaHead=head.RetinaHead,
                                IoUawareFCOSHead=fcos_head.IoUawareFCOSHead,
-                               FCOSHead=fcos_head.FCOSHead)
+                               FCOSHead=fcos_head.FCOSHead,
+                               IoUawareGARetinaHead=ga_head.IoUawareGARetinaHead,
+                               FeatureAdaption=ga_head.FeatureAdaption)
     models.detectors = _mod('mmdet.models.detectors', BaseDetector=detectors.BaseDetector,
                             SingleStageDetector=detectors.SingleStageDetector,
                             RetinaNet=detectors.RetinaNet, FCOS=detectors.FCOS)
@@ -71,6 +74,7 @@ def install(force=False):
     models.FCOS, models.IoUawareFCOSHead = detectors.FCOS, fcos_head.IoUawareFCOSHead
     models.FCOSHead = fcos_head.FCOSHead
     models.RetinaHead = head.RetinaHead
+    models.IoUawareGARetinaHead = ga_head.IoUawareGARetinaHead
 
     ops_nms = _mod('mmdet.ops.nms', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
     ops_nms.nms_wrapper = _mod('mmdet.ops.nms.nms_wrapper', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
@@ -85,6 +89,9 @@ def install(force=False):
                                               'modulated_deform_conv')}
     mops.__dict__.update(dcn_names)
     mops.dcn = _mod('mmdet.ops.dcn', **dcn_names)
+    mc_names = dict(MaskedConv2d=masked_conv.MaskedConv2d, masked_conv2d=masked_conv.masked_conv2d)
+    mops.__dict__.update(mc_names)
+    mops.masked_conv = _mod('mmdet.ops.masked_conv', **mc_names)
 
     core = _mod('mmdet.core', AnchorGenerator=anchors.AnchorGenerator,
                 anchor_target=targets.anchor_target, delta2bbox=bbox.delta2bbox,
