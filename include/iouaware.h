@@ -334,6 +334,15 @@ int ia_wino_mid_transform(const ia_wino_geom *g, const float *M, int channels, i
  * ia_wino_input_transform; x, u_packed, M, pre_* 16-byte aligned.                            */
 int ia_wino_in_gemm(const ia_wino_geom *g, const float *const *x, int channels, const float *pre_scale,
                     const float *pre_shift, int pre_relu, const float *u_packed, float *M, void *stream);
+/* The whole 3x3 / stride-1 / pad-1 convolution of 64 -> 64 channels in one launch: input
+ * transform, the 36 products and the output transform (+bias, +ReLU), V and M never written to
+ * memory -- the bits that ia_wino_in_gemm followed by ia_wino_output_transform(groups = 1, one
+ * segment of all 64 channels into y) gives.  x, u_packed, pre_* as for ia_wino_in_gemm; bias (64)
+ * or NULL; y[l] (B, H_l, W_l, 64) channels-last per level, must not overlap x.  channels == 64;
+ * x, y, u_packed, bias, pre_* 16-byte aligned.                                               */
+int ia_wino_conv3x3_c64(const ia_wino_geom *g, const float *const *x, int channels, const float *pre_scale,
+                        const float *pre_shift, int pre_relu, const float *u_packed, const float *bias,
+                        int relu, float *const *y, void *stream);
 
 /* Training: gradient of the output transform, dM = A dY A^T per tile (dY (B,H,W,channels)
  * channels-last per level, zero outside the map), written as 36 matrices (36, tiles, channels)

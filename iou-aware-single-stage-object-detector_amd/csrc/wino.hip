@@ -19,7 +19,9 @@
 //                             geometry in one launch (the head's tower transitions): the
 //                             activation in between stays in LDS;
 //   k_wino_in_gemm (this file) k_wino_in and the 36 products of a 64 -> 64 convolution in one
-//                             launch (ResNet stage 1): V stays in LDS.
+//                             launch (ResNet stage 1): V stays in LDS;
+//   k_wino_conv (this file)   k_wino_in_gemm and k_wino_out of that convolution in one launch: M
+//                             stays in the accumulators.
 // Activations are channels-last fp32: a wavefront handles one tile x 256 channels, 16 bytes per
 // lane, so every load / store instruction moves one contiguous 1 KiB pixel row.  Both kernels
 // are HBM-bound streams (36 x 16 B in, 36 x 16 B out per lane; 36 in, 16 out).
@@ -221,8 +223,26 @@ struct WinoInGemmArgs {
     int32_t T, pre_relu, ngroups;
 };
 
-template <int C>
-__global__ void __launch_bounds__(4 * C) k_wino_in_gemm(WinoInGemmArgs a)
+// ---- The whole 64 -> 64 convolution in ONE launch (k_wino_conv, OUT = true below): the
+// accumulator layout of the product phase IS the lane layout of k_wino_out<true> -- after plane k
+// lane (p, q) of wavefront nb holds M[k][tile p][16 nb + 4 q .. + 3], the (tile, channel quad) a
+// lane of the output transform owns -- so the 36 planes of a lane's tile never leave its
+// registers: no M (309 MB written and read straight back at batch 8 of 200 x 336), no shuffle, no
+// LDS.  The expressions are those of k_wino_out in its order (at6 down the six columns, at6 along
+// the four rows, + bias, ReLU select), so y has the bits of the two launches.  The column
+// transform is evaluated as its operands arrive: at6 needs rows 1, 2 of a column for s12 / d12 and
+// rows 3, 4 for s34 / d34, so a column holds at most four values (st[0..3][j]) instead of six
+// accumulators, the same operations in the same association: 96 registers, growing while tmp dies
+// row by row, against 144 for all 36 accumulators.
+struct WinoConvArgs {
+    WinoInGemmArgs g;                     // g.M is not used
+    const float *bias;                    // (C) or NULL
+    float *y[IA_MAX_LEVELS];              // per level (B, H, W, C) channels-last
+    int32_t relu;
+};
+
+template <int C, bool OUT>
+__device__ __forceinline__ void wino_in_gemm_body(const WinoInGemmArgs &a, const WinoConvArgs *e)
 {
     static_assert(C == 64, "lane maps and the LDS swizzle are worked out for 16 quads per tile");
     constexpr int Q = C / 4, TPW = 64 / Q, NB = C / 16, J = C / 16;
@@ -303,8 +323,17 @@ __global__ void __launch_bounds__(4 * C) k_wino_in_gemm(WinoInGemmArgs a)
 #pragma unroll
     for (int j = 0; j < J; ++j) xo[j] = 4 * ((4 * j + q) ^ p);
     const float *const up = a.U + ((size_t)wave * J * 64 + lane) * 4;
-    float *const mp = a.M + ((size_t)(live ? tp : 0) * C + 16 * wave + 4 * q);
+    float *const mp = OUT ? nullptr : a.M + ((size_t)(live ? tp : 0) * C + 16 * wave + 4 * q);
     const size_t kstride = (size_t)a.T * C;
+    // the bias is the oldest load of the store phase, for the reason given in k_wino_out
+    float4 bz = f4(0.0f);
+    if (OUT) {
+        if (e->bias) bz = *reinterpret_cast<const float4 *>(e->bias + 16 * wave + 4 * q);
+    }
+    // the ReLU flag waits in a VECTOR register: as a scalar it was the one SGPR spilled over the loop
+    int relu_flag = OUT ? e->relu : 0;
+    if (OUT) asm volatile("" : "+v"(relu_flag));
+    float4 st[4][6];                                   // OUT: the column transform s = A^T m, as it forms
 
     // Planes go through the MFMA pipe in pairs, their two accumulator chains interleaved (40 cycles
     // of dependent latency against 32 of issue); the weights of the next pair are requested before
@@ -363,13 +392,81 @@ __global__ void __launch_bounds__(4 * C) k_wino_in_gemm(WinoInGemmArgs a)
 #pragma unroll
                     for (int g = 0; g < PG; ++g)
                         acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[g][j][cc], xv[g][j][cc], acc[g], 0, 0, 0);
-            if (live) {
+            if (!OUT) {
+                if (live) {
 #pragma unroll
-                for (int g = 0; g < PG; ++g) *reinterpret_cast<f32x4_t *>(mp + (size_t)(k + g) * kstride) = acc[g];
+                    for (int g = 0; g < PG; ++g) *reinterpret_cast<f32x4_t *>(mp + (size_t)(k + g) * kstride) = acc[g];
+                }
+            } else {
+                // at6 down column j = j6 + g, row i of it: o[0] = (m0 + s12) + s34, o[1] = d12 + 2 d34,
+                // o[2] = s12 + 4 s34, o[3] = (d12 + 8 d34) + m5
+#pragma unroll
+                for (int g = 0; g < PG; ++g) {
+                    const int j = j6 + g;
+                    const float4 m = make_float4(acc[g].x, acc[g].y, acc[g].z, acc[g].w);
+                    if (i == 0) st[0][j] = m;
+                    if (i == 1) st[1][j] = m;
+                    if (i == 2) {
+                        const float4 s12 = st[1][j] + m, d12 = st[1][j] - m;
+                        st[0][j] = st[0][j] + s12; st[1][j] = d12; st[2][j] = s12;
+                    }
+                    if (i == 3) st[3][j] = m;
+                    if (i == 4) {
+                        const float4 s34 = st[3][j] + m, d34 = st[3][j] - m;
+                        const float4 o0 = st[0][j] + s34, o1 = st[1][j] + 2.0f * d34, o2 = st[2][j] + 4.0f * s34,
+                                     o3 = st[1][j] + 8.0f * d34;
+                        st[0][j] = o0; st[1][j] = o1; st[2][j] = o2; st[3][j] = o3;
+                    }
+                    if (i == 5) st[3][j] = st[3][j] + m;
+                }
             }
         }
         if (i + 1 < 6) __syncthreads();
     }
+    if (OUT) {
+        // rows: Y = s A, + bias, ReLU, one float4 per pixel straight from the accumulator layout
+        // (16 tiles x 64 B per wavefront instruction).  A row past T (the last group) stores nothing.
+        // (L and T pass through `opaque`: the compiler otherwise shares the `i < L` masks, T - 1 and the
+        // `live` mask with the code in front of the loop and keeps them through it, 18 SGPRs spilled to
+        // VGPR lanes)
+        WinoLevels lv = a.lv;
+        lv.L = opaque(a.lv.L);
+        const int T = opaque(a.T);
+        const bool on = tp < T;
+        const int tq = on ? tp : T - 1;
+        int H, W;
+        const TileRef r = locate_tile(lv, tq, &H, &W);
+        float *const y0 = level_ptr<false>(e->y, r.l) + 16 * wave + 4 * q;
+        const bool relu = relu_flag != 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float4 o[4];
+            at6(st[i], o);
+            const int y = r.y0 + i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int xx = r.x0 + j;
+                if (!on || y >= H || xx >= W) continue;
+                float4 v = o[j] + bz;
+                if (relu) v = make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f,
+                                          v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
+                const size_t pix = ((size_t)r.b * H + y) * W + xx;
+                *reinterpret_cast<float4 *>(y0 + pix * C) = v;
+            }
+        }
+    }
+}
+
+template <int C>
+__global__ void __launch_bounds__(4 * C) k_wino_in_gemm(WinoInGemmArgs a)
+{
+    wino_in_gemm_body<C, false>(a, nullptr);
+}
+
+template <int C>
+__global__ void __launch_bounds__(4 * C) k_wino_conv(WinoConvArgs a)
+{
+    wino_in_gemm_body<C, true>(a.g, &a);
 }
 
 // one line of A dy: the adjoint of at6 (4 values -> 6), A = (A^T)^T
@@ -726,6 +823,34 @@ int ia_wino_in_gemm(const ia_wino_geom *g, const float *const *x, int channels, 
     a.ngroups = (int32_t)(((int64_t)a.T + 15) / 16);
     dim3 grid((unsigned)((a.ngroups + 7) / 8 * 8));
     hipLaunchKernelGGL(ia::k_wino_in_gemm<64>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    return ia::hip_status(hipGetLastError());
+}
+
+int ia_wino_conv3x3_c64(const ia_wino_geom *g, const float *const *x, int channels, const float *pre_scale,
+                        const float *pre_shift, int pre_relu, const float *u_packed, const float *bias,
+                        int relu, float *const *y, void *stream)
+{
+    ia::WinoConvArgs a;
+    int rc = ia::make_wino_levels(g, a.g.lv);
+    if (rc) return rc;
+    if (!x || !y || !u_packed || channels != 64) return IA_E_ARG;
+    if (((uintptr_t)u_packed & 15u) || ((uintptr_t)bias & 15u) || ((uintptr_t)pre_scale & 15u) ||
+        ((uintptr_t)pre_shift & 15u))
+        return IA_E_ARG;
+    for (int l = 0; l < IA_MAX_LEVELS; ++l) {
+        const bool on = l < a.g.lv.L;
+        a.g.x[l] = on ? x[l] : nullptr;
+        a.y[l] = on ? y[l] : nullptr;
+        if (on && (!x[l] || ((uintptr_t)x[l] & 15u) || !y[l] || ((uintptr_t)y[l] & 15u))) return IA_E_ARG;
+    }
+    if (pre_scale && !pre_shift) return IA_E_ARG;
+    a.g.U = u_packed; a.g.M = nullptr;
+    a.g.pre_scale = pre_scale; a.g.pre_shift = pre_shift; a.g.pre_relu = pre_relu ? 1 : 0;
+    a.g.T = a.g.lv.tile_off[a.g.lv.L];
+    a.g.ngroups = (int32_t)(((int64_t)a.g.T + 15) / 16);
+    a.bias = bias; a.relu = relu ? 1 : 0;
+    dim3 grid((unsigned)((a.g.ngroups + 7) / 8 * 8));
+    hipLaunchKernelGGL(ia::k_wino_conv<64>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return ia::hip_status(hipGetLastError());
 }
 

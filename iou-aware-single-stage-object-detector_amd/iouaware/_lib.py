@@ -196,6 +196,8 @@ SIGNATURES = {
                                       C.POINTER(WinoSeg), _vp]),
     'ia_wino_mid_transform': (_i, [C.POINTER(WinoGeom), _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     'ia_wino_in_gemm': (_i, [C.POINTER(WinoGeom), C.POINTER(C.c_void_p), _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    'ia_wino_conv3x3_c64': (_i, [C.POINTER(WinoGeom), C.POINTER(C.c_void_p), _i, _vp, _vp, _i, _vp, _vp, _i,
+                                 C.POINTER(C.c_void_p), _vp]),
     'ia_linear_bias_act': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_linear_bias_act_bf16': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_batched_gemm': (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _sz, _vp]),

@@ -215,6 +215,7 @@ def batched_gemm(v, u, out):
 
 
 FUSE_IN_GEMM = True    # False: input_transform + batched_gemm (tests compare the two bit for bit)
+FUSE_OUT = True        # False: ia_wino_in_gemm into M + output_transform (the same bits, two launches)
 _IN_GEMM_CHANNELS = (64,)      # ia_wino_in_gemm: Cin == Cout in this list
 
 
@@ -228,11 +229,24 @@ def pack_u_fragments(u):
             .view(b, n // 16, k // 16, 64, 4)
 
 
-def input_transform_gemm(plan, xs, u_packed, out, pre=None):
+def input_transform_gemm(plan, xs, u_packed, out, pre=None, epilogue=None):
     """out (36, T, C) = input_transform(xs) @ U in one launch (V stays on chip): the bits of
-    input_transform followed by ia_batched_gemm_stream.  Not a pure transform, so not `_timed`."""
+    input_transform followed by ia_batched_gemm_stream.  Not a pure transform, so not `_timed`.
+    epilogue = (bias or None, relu, ys), out None: the output transform runs on the accumulators in
+    the same launch (ia_wino_conv3x3_c64) and writes the per-level channels-last tensors ys -- the
+    bits of output_transform on `out`, M never written.  Returns ys."""
     ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
     ps, pb, pr = pre if pre is not None else (None, None, False)
+    if epilogue is not None:
+        bias, relu, ys = epilogue
+        if out is not None or len(ys) != len(xs):
+            raise ValueError('the one-launch form writes ys, one per level, and no M')
+        yptrs = (C.c_void_p * len(ys))(*[y.data_ptr() for y in ys])
+        _lib.check(_lib.lib().ia_wino_conv3x3_c64(C.byref(plan.geom), ptrs, int(xs[0].shape[1]), _ptr(ps),
+                                                  _ptr(pb), int(bool(pr)), _ptr(u_packed), _ptr(bias),
+                                                  int(bool(relu)), yptrs, _stream()),
+                   'ia_wino_conv3x3_c64')
+        return ys
     _lib.check(_lib.lib().ia_wino_in_gemm(C.byref(plan.geom), ptrs, int(xs[0].shape[1]), _ptr(ps), _ptr(pb),
                                           int(bool(pr)), _ptr(u_packed), _ptr(out), _stream()),
                'ia_wino_in_gemm')
@@ -273,6 +287,11 @@ class WinogradConv3x3(object):
                 and (self.cin, self.cout) in _STREAM_BMM_SHAPES and plan.T >= 4096
                 and x.dtype == torch.float32):
             # exactly where batched_gemm takes the streaming kernel: the same bits, V not written
+            if FUSE_OUT:
+                y = torch.empty((x.shape[0], self.cout) + tuple(x.shape[-2:]), dtype=torch.float32,
+                                device=x.device, memory_format=torch.channels_last)
+                input_transform_gemm(plan, [x], self.u_packed, None, pre, epilogue=(self.bias, self.relu, [y]))
+                return y
             m = input_transform_gemm(plan, [x], self.u_packed, plan.buf('m', (36, plan.T, self.cout)), pre)
         else:
             v = input_transform(plan, [x], 1, plan.buf('v', (36, plan.T, self.cin)), pre)
