@@ -411,6 +411,15 @@ int ia_batched_gemm(const float *A, const float *W, float *D, int batch, int64_t
  * matrix, its weights in LDS); no workspace.                                                    */
 int ia_batched_gemm_stream(const float *A, const float *W, float *D, int batch, int64_t rows, int k,
                            int n, void *stream);
+/* The same product for the large head shapes on bf16 MFMA (csrc/wino_split_gemm.hip): every fp32
+ * operand split exactly into three bf16 pieces, x = h + m + l, and the six terms hh, hm, mh, hl, lh,
+ * mm summed in fp32 (hh in its own accumulators, the other five in a second set, the two added once
+ * at the end): error in the fp32 class, the same bits in every run.  V is split inside the kernel;
+ * U3 is U split once and packed in fragment order, (batch, k / 16, ceil(n / 128) * 4, 3, 64, 8)
+ * bf16 (iouaware/winograd.py split3_pack_u).  k a multiple of 32, V and U3 16-byte aligned; no
+ * workspace.                                                                                    */
+int ia_batched_gemm_split3(const float *V, const void *U3, float *D, int batch, int64_t rows, int k,
+                           int n, void *stream);
 
 /* Convolutions with a stride as plain contractions with a FIXED reduction order (the library
  * convolution's fast fp32 channels-last kernels for these shapes split the reduction and add the

@@ -202,6 +202,7 @@ SIGNATURES = {
     'ia_linear_bias_act_bf16': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_batched_gemm': (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _sz, _vp]),
     'ia_batched_gemm_stream': (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
+    'ia_batched_gemm_split3': (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     'ia_linear_bias_act_wt': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     'ia_gemm_tuning': (_i, [_i]),
     'ia_im2col3x3_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -17,8 +17,10 @@ instead of 144: these convolutions are 63 % of the network's multiply-adds.  Tha
 convolutions.
 
 Numerics: fp32 throughout; the Winograd transforms reassociate the sums, outputs agree with a
-direct convolution to ~1e-5 of the activation scale (tests/test_gpu_winograd.py).  The weights are
-transformed once (fp64 -> fp32) when the runner is built: build it AFTER loading a checkpoint.
+direct convolution to ~1e-5 of the activation scale (tests/test_gpu_winograd.py).  The retina_cls
+product of WinogradHead runs on bf16 MFMA through an exact three-way split of both fp32 operands
+(ia_batched_gemm_split3, fp32-class error: tests/test_gpu_split_gemm.py).  The weights are
+transformed (fp64 -> fp32, and split) once when the runner is built: build it AFTER loading a checkpoint.
 """
 import collections
 import ctypes as C
@@ -191,16 +193,61 @@ STREAM_BMM = True
 _STREAM_BMM_SHAPES = ((64, 64),)      # (128, 128) and (256, 48) measured slower than the library: 137 / 148 vs 124 / 139 us
 
 
-def batched_gemm(v, u, out):
+SPLIT_GEMM = True
+# (k, n) of the head products that ia_batched_gemm_split3 serves (WinogradHead only): retina_cls (256 -> 720),
+# 1.27 x the library on the bench's own data (profiles/split_gemm_isolated_timing.txt).  Layer 0 (256 -> 2 x 256)
+# and the tower layers (256 -> 256) are 1.18-1.22 x faster too but stay on the library: they feed the reg tower,
+# and the box coordinates of two X-101 e2e fixtures, 0.9 x the 1e-4 bound off their fp64 evaluation on the
+# library, moved to 1.13-1.22 x with the split's other (not larger) rounding.  reg | iou
+# (256 -> 48) is HBM-bound: nothing to gain.
+_SPLIT_SHAPES = ((256, 720),)
+
+
+def split3_pack_u(u):
+    """U (batch, K, N) fp32 -> its exact three-way bf16 split u = h + m + l, packed in the fragment order
+    ia_batched_gemm_split3 reads: (batch, K/16, Np/32, 3, 64, 8) bf16, Np = N rounded up to 128, zero
+    columns beyond N; packed[b][s][cb][p][32 q + c][e] = piece p of u[b][16 s + 8 q + e][32 cb + c].
+    Built once with the weights (build the head AFTER loading a checkpoint)."""
+    b, k, n = u.shape
+    if k % 32:
+        raise ValueError('the split GEMM needs K in multiples of 32')
+    npad = (n + 127) // 128 * 128
+    u = u.to(torch.float32)
+    h = u.to(torch.bfloat16)
+    r = u - h.float()                       # exact: at most 16 significant bits
+    m = r.to(torch.bfloat16)
+    lo = (r - m.float()).to(torch.bfloat16)  # exact, and exactly representable
+    p = torch.zeros((b, 3, k, npad), dtype=torch.bfloat16, device=u.device)
+    p[:, 0, :, :n], p[:, 1, :, :n], p[:, 2, :, :n] = h, m, lo
+    # (b, piece, s, q, e, cb, c) -> (b, s, cb, piece, q, c, e), lane = 32 q + c
+    return p.view(b, 3, k // 16, 2, 8, npad // 32, 32).permute(0, 2, 5, 1, 3, 6, 4).contiguous() \
+            .view(b, k // 16, npad // 32, 3, 64, 8)
+
+
+def split_shape(u):
+    """the (k, n) of U (batch, k, n) is served by the split GEMM"""
+    return (int(u.shape[1]), int(u.shape[2])) in _SPLIT_SHAPES
+
+
+def batched_gemm(v, u, out, u3=None):
     """out[b] = v[b] @ u[b] through hipBLASLt (csrc/gemm.hip); the kernel of a shape comes from the
     committed tuning table (ops.gemm_table_load: found offline by timing the library's candidates,
-    worth ~20 % over the heuristic's pick at these shapes), never from a timing race at run time"""
+    worth ~20 % over the heuristic's pick at these shapes), never from a timing race at run time.
+    u3 = split3_pack_u(u): the shapes in _SPLIT_SHAPES run on ia_batched_gemm_split3 (bf16 MFMA, exact
+    three-way split of both operands, fp32-class error) while SPLIT_GEMM is on."""
     from . import ops
     ops._ensure_gemm_table()
     batch, rows, k = v.shape
     n = u.shape[2]
     if not (v.is_contiguous() and u.is_contiguous() and out.is_contiguous()):
         raise ValueError('batched_gemm needs contiguous stacks')
+    if SPLIT_GEMM and u3 is not None and (k, n) in _SPLIT_SHAPES and v.dtype == torch.float32:
+        if u3.dtype != torch.bfloat16 or tuple(u3.shape) != (batch, k // 16, (n + 127) // 128 * 4, 3, 64, 8) \
+                or not u3.is_contiguous():
+            raise ValueError('u3 is not split3_pack_u of this U')
+        _lib.check(_lib.lib().ia_batched_gemm_split3(_ptr(v), _ptr(u3), _ptr(out), int(batch), int(rows),
+                                                     int(k), int(n), _stream()), 'ia_batched_gemm_split3')
+        return out
     if STREAM_BMM and (k, n) in _STREAM_BMM_SHAPES and rows >= 4096 and v.dtype == torch.float32:
         # HBM-bound products (<= 16 K weights per matrix): this library's streaming MFMA kernel,
         # weights in LDS -- the library's kernels reach 3.4 TB/s on these shapes
@@ -336,6 +383,8 @@ class _WinogradTowers(object):
 
     FUSE_MID = True       # False: the two-launch route (tests compare the two bit for bit)
     mid_bias = None
+    u0_3 = None           # split3_pack_u of u0 / of each u[i], where a subclass routes the split GEMM
+    u_3 = None
 
     def __init__(self, head):
         convs_c, convs_r = list(head.cls_convs), list(head.reg_convs)
@@ -364,8 +413,9 @@ class _WinogradTowers(object):
         plan = _plan_for(self._plans, key, lambda: _Plan(sizes, B, dev))
         T, F = plan.T, self.F
         # layer 0
+        u3 = (lambda i: self.u_3[i]) if self.u_3 is not None else (lambda i: None)  # noqa: E731
         v = input_transform(plan, feats, 1, plan.buf('v', (36, T, self.cin)))
-        m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)))
+        m = batched_gemm(v, self.u0, plan.buf('m', (36, T, 2 * F)), self.u0_3)
         new = lambda c: [torch.empty((B, c, h, w), dtype=torch.float32, device=dev,  # noqa: E731
                                      memory_format=torch.channels_last) for (h, w) in sizes]
         if self.FUSE_MID and self.mid_bias is not None and F % MID_CHANNELS == 0:
@@ -375,7 +425,7 @@ class _WinogradTowers(object):
             for i, u in enumerate(self.u):
                 v = mid_transform(plan, m, 2 * F, groups, self.mid_bias[i], True,
                                   plan.buf('v', (72, T, F)), 2)
-                m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
+                m = batched_gemm(v, u, plan.buf('m', (72, T, F)), u3(i))
                 groups = 2
             v = mid_transform(plan, m, 2 * F, groups, self.mid_bias[self.n_layers - 1], True,
                               plan.buf('v', (72, T, F)), 2)
@@ -385,7 +435,7 @@ class _WinogradTowers(object):
         # layers 1..n-1: groups = 2
         for i, u in enumerate(self.u):
             v = input_transform(plan, acts, 2, plan.buf('v', (72, T, F)))
-            m = batched_gemm(v, u, plan.buf('m', (72, T, F)))
+            m = batched_gemm(v, u, plan.buf('m', (72, T, F)), u3(i))
             nxt = plan.acts('b' if acts is plan.acts('a', 2 * F) else 'a', 2 * F)
             self._layer_out(plan, m, 2, i + 1, nxt)
             acts = nxt
@@ -393,10 +443,10 @@ class _WinogradTowers(object):
         return plan, v, new
 
     @staticmethod
-    def _out_conv(plan, v, name, u, bias, segments):
+    def _out_conv(plan, v, name, u, bias, segments, u3=None):
         """one tower's output convolutions: a GEMM with u.shape[2] columns, scattered to `segments`"""
         n = u.shape[2]
-        m = batched_gemm(v, u, plan.buf(name, (36, plan.T, n)))
+        m = batched_gemm(v, u, plan.buf(name, (36, plan.T, n)), u3)
         output_transform(plan, m, n, 1, bias, False, segments)
 
 
@@ -425,6 +475,11 @@ class WinogradHead(_WinogradTowers):
         self.u_cls, self.b_cls, self.c_cls, _ = _pair(head.retina_cls, None, self.F, 1)
         self.u_ri, self.b_ri, self.c_reg, self.c_iou = _pair(head.retina_reg, head.retina_iou,
                                                              self.F, 16)
+        # the products in _SPLIT_SHAPES run on the split GEMM: their U split once, here
+        pack = lambda u: split3_pack_u(u) if split_shape(u) else None  # noqa: E731
+        self.u0_3 = pack(self.u0)
+        self.u_3 = [pack(u) for u in self.u]
+        self.u_cls3 = pack(self.u_cls)
 
     def _layer_out(self, plan, m, groups, i, acts):
         output_transform(plan, m, 2 * self.F, groups, self.b[i], True, [(0, 2 * self.F, acts, 0)])
@@ -437,7 +492,7 @@ class WinogradHead(_WinogradTowers):
         # gives their write-back time to drain before the row-max kernel streams them back in
         # (round 6, measured again in bench steps, 2 x 20 steps each: class logits LAST -> decode stage 0.133 ms
         # in-step against 0.120-0.121 this way; gpurun_out/r06_ab_clslast.txt)
-        self._out_conv(plan, v[:36], 'mc', self.u_cls, self.b_cls, [(0, self.c_cls, cls, 0)])
+        self._out_conv(plan, v[:36], 'mc', self.u_cls, self.b_cls, [(0, self.c_cls, cls, 0)], self.u_cls3)
         self._out_conv(plan, v[36:], 'mr', self.u_ri, self.b_ri,
                        [(0, self.c_reg, reg, 0), (self.c_reg, self.c_iou, iou, 0)])
         return cls, reg, iou

@@ -29,8 +29,9 @@ def px(x):
 
 ops.linear_bias_act = timed('1x1', lambda x, w, *a, **k: (px(x), w.shape[0], w.shape[1], 'res' if k.get('residual') is not None else ''),
                             lambda x, w, *a, **k: 2 * px(x) * w.shape[0] * w.shape[1], ops.linear_bias_act)
-wg.batched_gemm = timed('wino-gemm', lambda v, u, out: (v.shape[0], v.shape[1], v.shape[2], u.shape[2]),
-                        lambda v, u, out: 2 * v.shape[0] * v.shape[1] * v.shape[2] * u.shape[2], wg.batched_gemm)
+wg.batched_gemm = timed('wino-gemm', lambda v, u, out, u3=None: (v.shape[0], v.shape[1], v.shape[2], u.shape[2],
+                                                                 'split3' if wg.SPLIT_GEMM and u3 is not None else ''),
+                        lambda v, u, out, u3=None: 2 * v.shape[0] * v.shape[1] * v.shape[2] * u.shape[2], wg.batched_gemm)
 _strided = ops.conv1x1_strided
 ops.conv1x1_strided = timed('1x1-strided', lambda x, w, *a, **k: (px(x) // k.get('stride', 2) ** 2, w.shape[0], w.shape[1]),
                             lambda x, w, *a, **k: 2 * (px(x) // k.get('stride', 2) ** 2) * w.shape[0] * w.shape[1], _strided)
