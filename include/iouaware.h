@@ -1363,6 +1363,70 @@ int ia_guided_get_bboxes(const ia_guided_geom *g, const ia_guided_level_ptrs *p,
                          float iou_thr, int max_per_img, void *workspace, size_t workspace_bytes,
                          float *dets, int32_t *labels, int32_t *rows, int32_t *num, void *stream);
 
+/* ------------------------------------------------------------------ SSD: L2Norm and decode
+ * ia_l2norm_nchw: the L2Norm layer of SSDVGG (reference backbones/ssd_vgg.py) on an fp32 NCHW map:
+ *     norm = sqrtf(sum_c x^2) + eps, y = (weight[c] * x) / norm, the sum of squares over the channels
+ *     in ascending order in fp64, rounded once.  C >= 1, B >= 1, any H * W.  x and y must not overlap
+ *     (in place: IA_E_ARG).  No atomics, the same bits in every run.
+ *
+ * Post-conv path of SSDHead (reference anchor_heads/ssd_head.py on anchor_head.py get_bboxes,
+ * use_sigmoid_cls = False, no nms_pre).  ia_ssd_geom instead of ia_head_geom: the number of anchors
+ * differs per level.  LIMITS: num_levels <= IA_MAX_LEVELS (8), num_anchors[l] <= IA_MAX_ANCHORS (16);
+ * no limit on the rows R = sum_l H_l * W_l * A_l per image below 2^31 (stages 1-3 are pure geometry).
+ * fp32 NCHW maps only (dtype must be IA_F32): cls[l] (B, A_l * (C + 1), H_l, W_l), channel 0 of an
+ * anchor = background; reg[l] (B, A_l * 4, H_l, W_l).  Rows are numbered in the reference's order:
+ * level, then (y, x), then anchor.
+ *
+ * ia_ssd_geom_rows: R, and the prefix of the rows per level.
+ * ia_ssd_rowscore: best (B, R): the largest foreground softmax score of every row, with the bits of
+ *     ia_decode_fuse_rowmax under IA_CLS_SOFTMAX_NOIOU on that level alone.
+ * ia_ssd_compact: per image the rows with best > score_thr in ascending order -> kept_rows
+ *     (B, IA_MAX_CANDIDATES) int32 (the first IA_MAX_CANDIDATES of them; -1 behind the count),
+ *     kept_count (B) the TRUE count, overflow (B) = kept_count > IA_MAX_CANDIDATES.  Ballots and a
+ *     prefix scan, no atomics.  Workspace: ia_ssd_compact_workspace_bytes(batch, R), 4-byte aligned.
+ * ia_ssd_gather_decode: for the rows kept_rows[b * kept_stride + r], r < kept_count[b] <= Rk (any Rk
+ *     >= 1, kept_stride >= Rk): boxes (B, Rk, 4) = delta2bbox(anchor, bbox_pred, means, stds,
+ *     max_shape = img_hw[b]) (/ scale_factor[b] when rescale), scores_t (B, C, Rs) the C foreground
+ *     softmax scores class-major (Rs = Rk rounded up to 64), best_score (B, Rk) -- the bits of
+ *     ia_gather_decode under IA_CLS_SOFTMAX_NOIOU.  Rows r >= kept_count[b], and every row of an image
+ *     with kept_count[b] > Rk, get a zero box, zero scores and best_score 0.
+ * ia_ssd_get_bboxes: the three stages with Rk = min(R, IA_MAX_CANDIDATES), ia_multiclass_nms on the
+ *     compacted rows, and `rows` mapped back to anchor row ids.  An image with more than
+ *     IA_MAX_CANDIDATES kept rows gets overflow[b] = 1 and num[b] = 0 -- never a truncated result; the
+ *     caller resolves it through the stage entries.  score_thr < 0: IA_E_ARG.  Workspace:
+ *     ia_ssd_get_bboxes_workspace_bytes, 256-byte aligned; ia_ssd_workspace_layout gives the byte
+ *     offsets of row scores (B, R), kept_rows, kept_count, boxes, scores_t, best_score, keep_count
+ *     (B, C), keep_rows (B, C, Rs).                                                                */
+int ia_l2norm_nchw(const float *x, const float *weight, float eps, int B, int C, int H, int W, float *y,
+                   void *stream);
+typedef struct ia_ssd_geom {
+    int32_t num_levels;                       /* <= IA_MAX_LEVELS */
+    int32_t num_classes;                      /* C foreground classes; cls has A_l*(C+1) channels, channel 0 = background */
+    int32_t H[IA_MAX_LEVELS], W[IA_MAX_LEVELS], stride[IA_MAX_LEVELS];
+    int32_t num_anchors[IA_MAX_LEVELS];       /* A_l <= IA_MAX_ANCHORS, may differ per level */
+    float base_anchors[IA_MAX_LEVELS][IA_MAX_ANCHORS][4];
+    float means[4], stds[4];
+} ia_ssd_geom;
+typedef struct ia_ssd_level_ptrs {
+    const void *cls[IA_MAX_LEVELS], *reg[IA_MAX_LEVELS];
+} ia_ssd_level_ptrs;
+int ia_ssd_geom_rows(const ia_ssd_geom *g, int32_t *R, int32_t level_off[IA_MAX_LEVELS + 1]);
+int ia_ssd_rowscore(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype, float *best,
+                    void *stream);
+size_t ia_ssd_compact_workspace_bytes(int batch, int R);
+int ia_ssd_compact(const float *best, int batch, int R, float score_thr, int32_t *kept_rows, int32_t *kept_count,
+                   int32_t *overflow, void *workspace, size_t workspace_bytes, void *stream);
+int ia_ssd_gather_decode(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype,
+                         const int32_t *kept_rows, int kept_stride, const int32_t *kept_count, int Rk,
+                         const float *img_hw, const float *scale_factor, int rescale, float *boxes,
+                         float *scores_t, float *best_score, void *stream);
+size_t ia_ssd_get_bboxes_workspace_bytes(const ia_ssd_geom *g, int batch);
+int ia_ssd_workspace_layout(const ia_ssd_geom *g, int batch, size_t offsets[8]);
+int ia_ssd_get_bboxes(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype,
+                      const float *img_hw, const float *scale_factor, int rescale, float score_thr,
+                      float iou_thr, int max_per_img, void *workspace, size_t workspace_bytes, float *dets,
+                      int32_t *labels, int32_t *rows, int32_t *num, int32_t *overflow, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

@@ -31,6 +31,7 @@
 #include "ia_internal.hpp"
 #include "ia_math.hpp"
 #include "ia_rowmax_dev.hpp"
+#include "ia_softmax_dev.hpp"
 
 namespace ia {
 
@@ -241,22 +242,7 @@ struct SoftmaxRowArgs {
     int32_t anchors_per_img;
 };
 
-template <typename T>
-__device__ __forceinline__ void softmax_row_stats(const T *x, size_t cs, int Cin, float &m, float &s, float &e_fg)
-{
-    m = -__builtin_inff();
-    for (int c = 0; c < Cin; ++c) {
-        const float v = load_f32<T>(x + (size_t)c * cs);
-        m = (m < v) ? v : m;
-    }
-    s = 0.0f; e_fg = 0.0f;
-    for (int c = 0; c < Cin; ++c) {
-        const float e = expf_(load_f32<T>(x + (size_t)c * cs) - m);
-        s = s + e;
-        if (c >= 1) e_fg = (e_fg < e) ? e : e_fg;
-    }
-}
-
+// (softmax_row_stats: ia_softmax_dev.hpp, shared with ssddecode.hip)
 template <typename T, bool IOU>
 __global__ void __launch_bounds__(256) k_rowscore_softmax(SoftmaxRowArgs a)
 {

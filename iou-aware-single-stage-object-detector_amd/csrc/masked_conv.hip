@@ -22,12 +22,9 @@
 //                is not -- no memset, no atomics.
 #include "ia_internal.hpp"
 #include "ia_math.hpp"
+#include "ia_compact_dev.hpp"      // kMaskBlock, the ballot / scan pieces (shared with ssddecode.hip)
 
 namespace ia {
-
-constexpr int kMaskBlock = 256;          // pixels per workgroup of the compaction kernels
-
-__device__ __forceinline__ int mask_popc(unsigned long long v) { return __popcll(v); }
 
 // where the keep decision comes from: a byte mask, or location logits thresholded here with the
 // expression of the guided decode (guideddecode.hip, guided_keep): sigmoidf_(x) >= thr, false for NaN
@@ -46,16 +43,8 @@ __global__ void __launch_bounds__(kMaskBlock) k_mask_count(Src mask, int64_t tot
 {
     __shared__ int s_wave[kMaskBlock / 64];
     const int64_t p = (int64_t)blockIdx.x * kMaskBlock + threadIdx.x;
-    const bool keep = p < total && mask(p);
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = mask_popc(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-#pragma unroll
-        for (int w = 0; w < kMaskBlock / 64; ++w) n += s_wave[w];
-        block_count[blockIdx.x] = n;
-    }
+    const int n = block_keep_count(p < total && mask(p), s_wave);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = n;
 }
 
 __global__ void __launch_bounds__(256) k_mask_scan(const int32_t *block_count, int32_t *block_off, int64_t nblocks,
@@ -63,28 +52,8 @@ __global__ void __launch_bounds__(256) k_mask_scan(const int32_t *block_count, i
 {
     __shared__ int s_v[256];
     __shared__ int s_carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nblocks; base += 256) {
-        const int64_t i = base + tid;
-        const int v = i < nblocks ? block_count[i] : 0;
-        s_v[tid] = v;
-        __syncthreads();
-        // Hillis-Steele inclusive scan of the 256 values
-        for (int o = 1; o < 256; o <<= 1) {
-            const int add = tid >= o ? s_v[tid - o] : 0;
-            __syncthreads();
-            s_v[tid] += add;
-            __syncthreads();
-        }
-        const int carry = s_carry;
-        if (i < nblocks) block_off[i] = carry + s_v[tid] - v;
-        __syncthreads();
-        if (tid == 255) s_carry = carry + s_v[255];
-        __syncthreads();
-    }
-    if (tid == 0) count[0] = s_carry;
+    const int total = scan_block_counts(block_count, block_off, nblocks, s_v, &s_carry);
+    if (threadIdx.x == 0) count[0] = total;
 }
 
 template <typename Src>
@@ -94,13 +63,7 @@ __global__ void __launch_bounds__(kMaskBlock) k_mask_write(Src mask, int64_t tot
     __shared__ int s_wave[kMaskBlock / 64];
     const int64_t p = (int64_t)blockIdx.x * kMaskBlock + threadIdx.x;
     const bool keep = p < total && mask(p);
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = mask_popc(bal);
-    __syncthreads();
-    int r = block_off[blockIdx.x];
-    for (int w = 0; w < wave; ++w) r += s_wave[w];
-    r += mask_popc(bal & ((1ull << lane) - 1ull));
+    const int r = block_off[blockIdx.x] + block_keep_rank(keep, s_wave);
     if (p < total) {
         rank[p] = keep ? r : -1;
         if (keep) idx[r] = (int32_t)p;       // r < count <= total: inside idx

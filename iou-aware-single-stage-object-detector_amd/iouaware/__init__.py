@@ -10,7 +10,7 @@ libiouaware_hip.so (hand-written gfx950 kernels, C-ABI in include/iouaware.h).
 from .config import Config, ConfigDict                                  # noqa: F401
 from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, Registry,  # noqa: F401
                        build_backbone, build_detector, build_head, build_loss, build_neck)
-from . import backbones, fpn, losses, head, fcos_head, ga_head, detectors  # noqa: F401  (register)
+from . import backbones, fpn, losses, head, fcos_head, ga_head, ssd_vgg, ssd_head, detectors  # noqa: F401  (register)
 from .api import init_detector, inference_batch                         # noqa: F401
 from .preprocess import ImageTransform                                  # noqa: F401
 from .deform_conv import (DeformConv, DeformConvPack, ModulatedDeformConv,  # noqa: F401

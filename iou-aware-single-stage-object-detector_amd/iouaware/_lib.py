@@ -114,6 +114,20 @@ class GuidedLevelPtrs(C.Structure):
                 ('loc', C.c_void_p * IA_MAX_LEVELS)]
 
 
+class SsdGeom(C.Structure):
+    """ia_ssd_geom"""
+    _fields_ = [('num_levels', C.c_int32), ('num_classes', C.c_int32),
+                ('H', C.c_int32 * IA_MAX_LEVELS), ('W', C.c_int32 * IA_MAX_LEVELS),
+                ('stride', C.c_int32 * IA_MAX_LEVELS), ('num_anchors', C.c_int32 * IA_MAX_LEVELS),
+                ('base_anchors', ((C.c_float * 4) * IA_MAX_ANCHORS) * IA_MAX_LEVELS),
+                ('means', C.c_float * 4), ('stds', C.c_float * 4)]
+
+
+class SsdLevelPtrs(C.Structure):
+    """ia_ssd_level_ptrs"""
+    _fields_ = [('cls', C.c_void_p * IA_MAX_LEVELS), ('reg', C.c_void_p * IA_MAX_LEVELS)]
+
+
 class ImageDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('src_h', C.c_int32), ('src_w', C.c_int32),
                 ('dst_h', C.c_int32), ('dst_w', C.c_int32), ('flip', C.c_int32)]
@@ -143,6 +157,7 @@ _PG, _WG = C.POINTER(PointHeadGeom), C.POINTER(WinoGeom)
 _PP, _PT, _PC = C.POINTER(PointLevelPtrs), C.POINTER(PointTargets), C.POINTER(PointLossCfg)
 _PS = C.POINTER(PointPixStrides)
 _GG, _GP = C.POINTER(GuidedGeom), C.POINTER(GuidedLevelPtrs)
+_SG, _SP = C.POINTER(SsdGeom), C.POINTER(SsdLevelPtrs)
 
 # name -> (restype, argtypes); mirrors include/iouaware.h one to one
 SIGNATURES = {
@@ -355,6 +370,16 @@ SIGNATURES = {
     'ia_guided_get_bboxes_workspace_bytes': (_sz, [_GG, _i]),
     'ia_guided_workspace_layout': (_i, [_GG, _i, C.POINTER(_sz * 8)]),
     'ia_guided_get_bboxes': (_i, [_GG, _GP, _i, _vp, _vp, _i, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'ia_l2norm_nchw': (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp]),
+    'ia_ssd_geom_rows': (_i, [_SG, C.POINTER(C.c_int32), C.POINTER(C.c_int32 * (IA_MAX_LEVELS + 1))]),
+    'ia_ssd_rowscore': (_i, [_SG, _SP, _i, _i, _vp, _vp]),
+    'ia_ssd_compact_workspace_bytes': (_sz, [_i, _i]),
+    'ia_ssd_compact': (_i, [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ia_ssd_gather_decode': (_i, [_SG, _SP, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'ia_ssd_get_bboxes_workspace_bytes': (_sz, [_SG, _i]),
+    'ia_ssd_workspace_layout': (_i, [_SG, _i, C.POINTER(_sz * 8)]),
+    'ia_ssd_get_bboxes': (_i, [_SG, _SP, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                               _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

@@ -7,7 +7,7 @@ layout finds this build's implementations:
     from mmdet.ops import sigmoid_focal_loss          # -> HIP focal-loss op
     from mmdet.core import bbox2result, multiclass_nms, delta2bbox ...
 
-Only the names on the IoU-aware RetinaNet, FCOS and GA-RetinaNet (inference) paths exist (SURVEY.md section 8);
+Only the names on the IoU-aware RetinaNet, FCOS, GA-RetinaNet (inference) and SSD (inference) paths exist (SURVEY.md section 8);
 everything else of mmdetection is deliberately absent.
 """
 import sys
@@ -30,7 +30,7 @@ def install(force=False):
         raise RuntimeError('a different `mmdet` is already imported')
     from . import (anchors, api, bbox, detectors, fpn, head, layers, losses, nms_op, registry,
                    targets, backbones, dist as idist, focal_op, preprocess, fcos_head, ga_head,
-                   masked_conv)
+                   masked_conv, ssd_head, ssd_vgg)
     # (the package attribute `deform_conv` is the function; the module is reached by its full name)
     import importlib
     dcn = importlib.import_module(__package__ + '.deform_conv')
@@ -46,7 +46,9 @@ def install(force=False):
         k: getattr(registry, k) for k in ('build_backbone', 'build_neck', 'build_head',
                                           'build_loss', 'build_detector')})
     models.backbones = _mod('mmdet.models.backbones', ResNet=backbones.ResNet,
-                            ResNeXt=backbones.ResNeXt, make_res_layer=backbones.make_res_layer)
+                            ResNeXt=backbones.ResNeXt, make_res_layer=backbones.make_res_layer,
+                            SSDVGG=ssd_vgg.SSDVGG)
+    models.backbones.ssd_vgg = _mod('mmdet.models.backbones.ssd_vgg', SSDVGG=ssd_vgg.SSDVGG, L2Norm=ssd_vgg.L2Norm)
     models.necks = _mod('mmdet.models.necks', FPN=fpn.FPN)
     models.anchor_heads = _mod('mmdet.models.anchor_heads', AnchorHead=head.AnchorHead,
                                IoUawareRetinaHead=head.IoUawareRetinaHead,
@@ -54,7 +56,8 @@ def install(force=False):
                                IoUawareFCOSHead=fcos_head.IoUawareFCOSHead,
                                FCOSHead=fcos_head.FCOSHead,
                                IoUawareGARetinaHead=ga_head.IoUawareGARetinaHead,
-                               FeatureAdaption=ga_head.FeatureAdaption)
+                               FeatureAdaption=ga_head.FeatureAdaption,
+                               SSDHead=ssd_head.SSDHead)
     models.detectors = _mod('mmdet.models.detectors', BaseDetector=detectors.BaseDetector,
                             SingleStageDetector=detectors.SingleStageDetector,
                             RetinaNet=detectors.RetinaNet, FCOS=detectors.FCOS)
@@ -75,6 +78,7 @@ def install(force=False):
     models.FCOSHead = fcos_head.FCOSHead
     models.RetinaHead = head.RetinaHead
     models.IoUawareGARetinaHead = ga_head.IoUawareGARetinaHead
+    models.SSDHead, models.SSDVGG, models.L2Norm = ssd_head.SSDHead, ssd_vgg.SSDVGG, ssd_vgg.L2Norm
 
     ops_nms = _mod('mmdet.ops.nms', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
     ops_nms.nms_wrapper = _mod('mmdet.ops.nms.nms_wrapper', nms=nms_op.nms, soft_nms=nms_op.soft_nms)
