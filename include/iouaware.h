@@ -934,7 +934,13 @@ int ia_conv1x1_wide(const float *x, const float *w, const float *bias, const flo
  * reg tower: own inputs, weights, outputs).  cin % 32 == 0, cout even (per group).
  * ia_conv3x3_bf16_pack: weights (groups * cout, 3, 3, cin) bf16 (= a channels-last
  * (groups * cout, cin, 3, 3) tensor) -> the kernel's layout, ia_conv3x3_bf16_packed_bytes bytes,
- * once per model.  bias (groups * cout) fp32 or NULL.                                             */
+ * once per model.  bias (groups * cout) fp32 or NULL.
+ * ia_conv3x3_bf16_plan: the geometry ia_conv3x3_bf16_levels would launch for this descriptor, per
+ * level l < num_levels (host only: launches nothing, does not look at the pointers; any output may be
+ * NULL): variant[l] = 100 * MB + 10 * WM + WN of the kernel instance (414, 214, 222, 141 or 122: four
+ * wavefronts as WM x WN, each 32 * MB pixels x 64 channels), the TH[l] x TW[l] pixel tile and the
+ * tiles_y[l] x tiles_x[l] tiles per image.  The launcher's own code computes it (IA_CONV3_VARIANT, a
+ * timing aid read on every call, included).  IA_E_ARG where the launcher would refuse the sizes.    */
 typedef struct ia_conv3x3_desc {
     int32_t num_levels, batch, groups;
     int32_t cin, cout;                    /* channels per group                                   */
@@ -946,6 +952,8 @@ typedef struct ia_conv3x3_desc {
 size_t ia_conv3x3_bf16_packed_bytes(int cin, int cout, int groups);
 int ia_conv3x3_bf16_pack(const void *w, int cin, int cout, int groups, void *wp, void *stream);
 int ia_conv3x3_bf16_levels(const ia_conv3x3_desc *d, const void *wp, const float *bias, int relu, void *stream);
+int ia_conv3x3_bf16_plan(const ia_conv3x3_desc *d, int32_t *variant, int32_t *TH, int32_t *TW, int32_t *tiles_y,
+                         int32_t *tiles_x);
 
 /* ------------------------------------------------------------------ bf16 training of the convolution above
  * (csrc/conv3x3_bf16_bwd.hip): bf16 activations and gradients, fp32 master weights.

@@ -370,6 +370,78 @@ static void conv3_tile_shape_search(int H, int W, int max_px, int max_rows, int 
     }
 }
 
+// the checks of a call that do not look at the pointers (ia_conv3x3_bf16_levels adds those, ia_conv3x3_bf16_plan
+// launches nothing and stops here)
+static bool conv3_desc_ok(const ia_conv3x3_desc *d)
+{
+    if (!d || d->num_levels < 1 || d->num_levels > IA_MAX_LEVELS || d->batch < 1 || d->groups < 1 ||
+        d->groups > kCvMaxGroups || d->cin < 32 || (d->cin % kCvBK) || d->cout < 2 || (d->cout & 1) ||
+        d->x_stride < d->cin || (d->x_stride & 7) || d->y_stride < d->cout || (d->y_stride & 1))
+        return false;
+    for (int l = 0; l < d->num_levels; ++l)
+        if (d->H[l] < 1 || d->W[l] < 1) return false;
+    return true;
+}
+
+// One of the two launches of a call (pass 0: the large maps on (4, 1, 4); pass 1: the rest): the variant as
+// 100 * MB + 10 * WM + WN, and in `a` everything of the argument block that the geometry decides -- the
+// levels of this pass (a.L of them, possibly none; src[n] = the descriptor's level behind a's n-th), their
+// tile shapes, tile counts and offsets into the tile list (`tiles` in all).  The launcher and
+// ia_conv3x3_bf16_plan both come through here.  Reads IA_CONV3_VARIANT on every call.  -> 0 or IA_E_ARG
+static int conv3_plan_pass(const ia_conv3x3_desc *d, int pass, Conv3Args &a, int &variant, int64_t &tiles,
+                           int (&src)[IA_MAX_LEVELS])
+{
+    // Variant (MB, WM, WN): four wavefronts, tile = 32 * MB * WM pixels x 64 * WN channels.
+    //   Cout > 128: (2, 1, 4), 64-pixel tiles, three workgroups per CU -- measured best or tied on every
+    //   pyramid level against the 8-wavefront workgroups of round 3 (batch 16, 256 -> 256: 100 x 168
+    //   0.319 ms against 0.368 / 0.389 for 256 / 128 pixels; 50 x 84 0.095 against 0.139 / 0.123;
+    //   13 x 21 0.026 against 0.057 / 0.035); LARGE maps -- at least kCvBigTiles 128-pixel tiles in
+    //   the batch -- take (4, 1, 4) in a launch of their own: half the weight-fragment traffic per
+    //   pixel (100 x 168 at batch 16: 0.305 against 0.319 ms; 50 x 84: 0.112 against 0.095, stays);
+    //   Cout <= 128: (2, 2, 2), 128-pixel tiles x 128 channels -- the ResNet stage-2 / stage-1
+    //   bottlenecks (64 output channels: the second column of wavefronts multiplies zeros; a
+    //   256-pixel x 64-channel tile would need six patch pieces per thread).
+    // IA_CONV3_VARIANT = 41 / 21 forces (4, 1, 4) / (2, 1, 4) for every map where WN = 4 applies
+    // (tools/time_conv3x3_bf16.py).
+    const int wnc = d->cout <= 64 ? 1 : (d->cout <= 128 ? 2 : 4);
+    const char *force = getenv("IA_CONV3_VARIANT");
+    const int forced = (force && force[0] && force[1] == '1') ? force[0] - '0' : 0;
+    // Cout <= 64: (1, 4, 1) -- four wavefronts of 32 pixels x 64 channels, no padded MFMAs (ResNet
+    // stage 1, batch 16, 200 x 336: 0.168 ms against 0.269 for (2, 2, 2) and 0.246 for (1, 2, 2));
+    // 64 < Cout <= 128 stays on (2, 2, 2) (100 x 168: 0.123 against 0.128 for (1, 2, 2)).  "22" forces
+    // (2, 2, 2) for both, "12" forces (1, 2, 2) for 64 < Cout <= 128.
+    const bool f22 = force && force[0] == '2' && force[1] == '2', f12 = force && force[0] == '1' && force[1] == '2';
+    const bool narrow64 = (wnc == 1 && !f22) || (wnc == 2 && f12);
+    const int wnk = (wnc == 1 && !narrow64) ? 2 : wnc;         // "22" forced: 64 output channels on (2, 2, 2) as before
+    const int mb = (pass == 0 && wnc == 4) ? 4 : (narrow64 ? 1 : 2);
+    const int px = 32 * mb * (4 / wnk);
+    const int rows = px == 128 ? kCvMaxRows128 : kCvMaxRows64;
+    variant = 100 * mb + 10 * (4 / wnk) + wnk;
+    memset(&a, 0, sizeof(a));
+    a.B = d->batch; a.Cin = d->cin; a.Cout = d->cout; a.xs = d->x_stride; a.ys = d->y_stride;
+    a.ntile = (d->cout + kCvBN - 1) / kCvBN;
+    tiles = 0;
+    int n = 0;
+    for (int l = 0; l < d->num_levels; ++l) {
+        int th, tw;
+        conv3_tile_shape(d->H[l], d->W[l], 128, kCvMaxRows128, th, tw);
+        const int64_t big_tiles = (int64_t)d->batch * ((d->H[l] + th - 1) / th) * ((d->W[l] + tw - 1) / tw);
+        const bool big = wnc == 4 && (forced == 4 || (forced != 2 && big_tiles >= kCvBigTiles));
+        if (big != (pass == 0)) continue;
+        a.H[n] = d->H[l]; a.W[n] = d->W[l];
+        src[n] = l;
+        conv3_tile_shape(a.H[n], a.W[n], px, rows, a.TH[n], a.TW[n]);
+        a.tiles_y[n] = (a.H[n] + a.TH[n] - 1) / a.TH[n]; a.tiles_x[n] = (a.W[n] + a.TW[n] - 1) / a.TW[n];
+        a.tile_off[n] = (int32_t)tiles;
+        tiles += (int64_t)d->batch * a.tiles_y[n] * a.tiles_x[n];
+        if (tiles > 2147483647LL) return IA_E_ARG;
+        ++n;
+    }
+    a.L = n;
+    for (int l = n; l <= IA_MAX_LEVELS; ++l) a.tile_off[l] = (int32_t)tiles;
+    return 0;
+}
+
 }  // namespace ia
 
 extern "C" {
@@ -392,83 +464,57 @@ int ia_conv3x3_bf16_pack(const void *w, int Cin, int Cout, int groups, void *wp,
 
 int ia_conv3x3_bf16_levels(const ia_conv3x3_desc *d, const void *wp, const float *bias, int relu, void *stream)
 {
-    if (!d || !wp || d->num_levels < 1 || d->num_levels > IA_MAX_LEVELS || d->batch < 1 || d->groups < 1 ||
-        d->groups > ia::kCvMaxGroups || d->cin < 32 || (d->cin % ia::kCvBK) || d->cout < 2 || (d->cout & 1) ||
-        d->x_stride < d->cin || (d->x_stride & 7) || d->y_stride < d->cout || (d->y_stride & 1))
-        return IA_E_ARG;
+    if (!wp || !ia::conv3_desc_ok(d)) return IA_E_ARG;
     if ((uintptr_t)wp & 15u) return IA_E_ARG;
-    for (int l = 0; l < d->num_levels; ++l) {
-        if (d->H[l] < 1 || d->W[l] < 1) return IA_E_ARG;
+    for (int l = 0; l < d->num_levels; ++l)
         for (int g = 0; g < d->groups; ++g)
             if (!d->x[g][l] || !d->y[g][l] || ((uintptr_t)d->x[g][l] & 15u) || ((uintptr_t)d->y[g][l] & 3u))
                 return IA_E_ARG;
-    }
-    // Variant (MB, WM, WN): four wavefronts, tile = 32 * MB * WM pixels x 64 * WN channels.
-    //   Cout > 128: (2, 1, 4), 64-pixel tiles, three workgroups per CU -- measured best or tied on every
-    //   pyramid level against the 8-wavefront workgroups of round 3 (batch 16, 256 -> 256: 100 x 168
-    //   0.319 ms against 0.368 / 0.389 for 256 / 128 pixels; 50 x 84 0.095 against 0.139 / 0.123;
-    //   13 x 21 0.026 against 0.057 / 0.035); LARGE maps -- at least kCvBigTiles 128-pixel tiles in
-    //   the batch -- take (4, 1, 4) in a launch of their own: half the weight-fragment traffic per
-    //   pixel (100 x 168 at batch 16: 0.305 against 0.319 ms; 50 x 84: 0.112 against 0.095, stays);
-    //   Cout <= 128: (2, 2, 2), 128-pixel tiles x 128 channels -- the ResNet stage-2 / stage-1
-    //   bottlenecks (64 output channels: the second column of wavefronts multiplies zeros; a
-    //   256-pixel x 64-channel tile would need six patch pieces per thread).
-    // IA_CONV3_VARIANT = 41 / 21 forces (4, 1, 4) / (2, 1, 4) for every map where WN = 4 applies
-    // (tools/time_conv3x3_bf16.py).
-    const int wnc = d->cout <= 64 ? 1 : (d->cout <= 128 ? 2 : 4);
-    const char *force = getenv("IA_CONV3_VARIANT");
-    const int forced = (force && force[0] && force[1] == '1') ? force[0] - '0' : 0;
-    // Cout <= 64: (1, 4, 1) -- four wavefronts of 32 pixels x 64 channels, no padded MFMAs (ResNet
-    // stage 1, batch 16, 200 x 336: 0.168 ms against 0.269 for (2, 2, 2) and 0.246 for (1, 2, 2));
-    // 64 < Cout <= 128 stays on (2, 2, 2) (100 x 168: 0.123 against 0.128 for (1, 2, 2)).  "22" forces
-    // (2, 2, 2) for both, "12" forces (1, 2, 2) for 64 < Cout <= 128.
-    const bool f22 = force && force[0] == '2' && force[1] == '2', f12 = force && force[0] == '1' && force[1] == '2';
-    const bool narrow64 = (wnc == 1 && !f22) || (wnc == 2 && f12);
     hipStream_t st = (hipStream_t)stream;
-    const int wnk = (wnc == 1 && !narrow64) ? 2 : wnc;         // "22" forced: 64 output channels on (2, 2, 2) as before
     for (int pass = 0; pass < 2; ++pass) {            // pass 0: the large maps on (4, 1, 4); pass 1: the rest
-        const int mb = (pass == 0 && wnc == 4) ? 4 : (narrow64 ? 1 : 2);
-        const int px = 32 * mb * (4 / wnk);
-        const int rows = px == 128 ? ia::kCvMaxRows128 : ia::kCvMaxRows64;
         ia::Conv3Args a;
-        memset(&a, 0, sizeof(a));
-        a.wp = static_cast<const uint16_t *>(wp); a.bias = bias;
-        a.B = d->batch; a.Cin = d->cin; a.Cout = d->cout; a.xs = d->x_stride; a.ys = d->y_stride;
-        a.relu = relu ? 1 : 0; a.ntile = (d->cout + ia::kCvBN - 1) / ia::kCvBN;
-        int64_t tiles = 0;
-        int n = 0;
-        for (int l = 0; l < d->num_levels; ++l) {
-            int th, tw;
-            ia::conv3_tile_shape(d->H[l], d->W[l], 128, ia::kCvMaxRows128, th, tw);
-            const int64_t big_tiles = (int64_t)d->batch * ((d->H[l] + th - 1) / th) * ((d->W[l] + tw - 1) / tw);
-            const bool big = wnc == 4 && (forced == 4 || (forced != 2 && big_tiles >= ia::kCvBigTiles));
-            if (big != (pass == 0)) continue;
-            a.H[n] = d->H[l]; a.W[n] = d->W[l];
+        int variant, src[IA_MAX_LEVELS];
+        int64_t tiles;
+        if (ia::conv3_plan_pass(d, pass, a, variant, tiles, src)) return IA_E_ARG;
+        if (a.L == 0) continue;
+        a.wp = static_cast<const uint16_t *>(wp); a.bias = bias; a.relu = relu ? 1 : 0;
+        for (int n = 0; n < a.L; ++n)
             for (int g = 0; g < d->groups; ++g) {
-                a.x[g][n] = static_cast<const uint16_t *>(d->x[g][l]);
-                a.y[g][n] = static_cast<uint16_t *>(d->y[g][l]);
+                a.x[g][n] = static_cast<const uint16_t *>(d->x[g][src[n]]);
+                a.y[g][n] = static_cast<uint16_t *>(d->y[g][src[n]]);
             }
-            ia::conv3_tile_shape(a.H[n], a.W[n], px, rows, a.TH[n], a.TW[n]);
-            a.tiles_y[n] = (a.H[n] + a.TH[n] - 1) / a.TH[n]; a.tiles_x[n] = (a.W[n] + a.TW[n] - 1) / a.TW[n];
-            a.tile_off[n] = (int32_t)tiles;
-            tiles += (int64_t)d->batch * a.tiles_y[n] * a.tiles_x[n];
-            if (tiles > 2147483647LL) return IA_E_ARG;
-            ++n;
-        }
-        if (n == 0) continue;
-        a.L = n;
-        for (int l = n; l <= IA_MAX_LEVELS; ++l) a.tile_off[l] = (int32_t)tiles;
         const dim3 grid((unsigned)tiles, (unsigned)(d->groups * a.ntile));
         // both Cout > 128 variants with the fragment ring (PIPE = 2; the (2, 1, 4) variant at 168 registers:
         // still three wavefronts per SIMD; 50 x 84 at batch 16 0.090 -> 0.087 ms, the backbone's 256 -> 256 /
         // 512 -> 512 layers 0.091 -> 0.088 / 0.097 -> 0.094)
-        if (wnc == 4 && mb == 4) hipLaunchKernelGGL((ia::k_conv3x3_bf16<4, 1, 4, 2>), grid, dim3(256), 0, st, a);
-        else if (wnc == 4) hipLaunchKernelGGL((ia::k_conv3x3_bf16<2, 1, 4, 2>), grid, dim3(256), 0, st, a);
-        else if (mb == 1 && wnk == 1) hipLaunchKernelGGL((ia::k_conv3x3_bf16<1, 4, 1>), grid, dim3(256), 0, st, a);
-        else if (mb == 1) hipLaunchKernelGGL((ia::k_conv3x3_bf16<1, 2, 2>), grid, dim3(256), 0, st, a);
+        if (variant == 414) hipLaunchKernelGGL((ia::k_conv3x3_bf16<4, 1, 4, 2>), grid, dim3(256), 0, st, a);
+        else if (variant == 214) hipLaunchKernelGGL((ia::k_conv3x3_bf16<2, 1, 4, 2>), grid, dim3(256), 0, st, a);
+        else if (variant == 141) hipLaunchKernelGGL((ia::k_conv3x3_bf16<1, 4, 1>), grid, dim3(256), 0, st, a);
+        else if (variant == 122) hipLaunchKernelGGL((ia::k_conv3x3_bf16<1, 2, 2>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((ia::k_conv3x3_bf16<2, 2, 2, 2>), grid, dim3(256), 0, st, a);    // ring: 128 -> 128 at 100 x 168 0.095 -> 0.086 ms
         const int rc = ia::hip_status(hipGetLastError());
         if (rc) return rc;
+    }
+    return 0;
+}
+
+int ia_conv3x3_bf16_plan(const ia_conv3x3_desc *d, int32_t *variant, int32_t *TH, int32_t *TW, int32_t *tiles_y,
+                         int32_t *tiles_x)
+{
+    if (!ia::conv3_desc_ok(d)) return IA_E_ARG;
+    for (int pass = 0; pass < 2; ++pass) {
+        ia::Conv3Args a;
+        int v, src[IA_MAX_LEVELS];
+        int64_t tiles;
+        if (ia::conv3_plan_pass(d, pass, a, v, tiles, src)) return IA_E_ARG;
+        for (int n = 0; n < a.L; ++n) {
+            const int l = src[n];
+            if (variant) variant[l] = v;
+            if (TH) TH[l] = a.TH[n];
+            if (TW) TW[l] = a.TW[n];
+            if (tiles_y) tiles_y[l] = a.tiles_y[n];
+            if (tiles_x) tiles_x[l] = a.tiles_x[n];
+        }
     }
     return 0;
 }

@@ -298,6 +298,7 @@ SIGNATURES = {
     'ia_conv3x3_bf16_packed_bytes': (C.c_size_t, [_i, _i, _i]),
     'ia_conv3x3_bf16_pack': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'ia_conv3x3_bf16_levels': (_i, [_vp, _vp, _vp, _i, _vp]),
+    'ia_conv3x3_bf16_plan': (_i, [_vp] + [C.POINTER(C.c_int32)] * 5),
     'ia_conv3x3_bf16_wgrad_workspace_bytes': (C.c_size_t, [_vp]),
     'ia_conv3x3_bf16_wgrad_plan': (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'ia_conv3x3_bf16_wgrad_levels': (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),

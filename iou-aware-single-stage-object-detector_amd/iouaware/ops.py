@@ -776,6 +776,22 @@ def conv3x3_bf16_levels(xs, wp, bias, cout, ys, relu=False, cin=None):
     return ys
 
 
+def conv3x3_bf16_plan(sizes, cin, cout, batch=1, groups=1):
+    """-> per (H, W) of `sizes` the (variant, TH, TW, tiles_y, tiles_x) that conv3x3_bf16_levels would launch
+    for maps of these sizes: variant = 100 * MB + 10 * WM + WN of the kernel instance, the pixel tile, the
+    tiles per image (ia_conv3x3_bf16_plan: host only, needs no device).  cin / cout per group, dense tensors."""
+    d = _lib.Conv3x3Desc()
+    d.num_levels, d.batch, d.groups = len(sizes), int(batch), int(groups)
+    d.cin, d.cout, d.x_stride, d.y_stride = int(cin), int(cout), int(cin), int(cout)
+    if not 1 <= len(sizes) <= _lib.IA_MAX_LEVELS:
+        raise ValueError('conv3x3_bf16_plan: 1 to %d levels' % _lib.IA_MAX_LEVELS)
+    for l, (h, w) in enumerate(sizes):
+        d.H[l], d.W[l] = int(h), int(w)
+    out = [(C.c_int32 * _lib.IA_MAX_LEVELS)() for _ in range(5)]
+    _lib.check(_lib.lib().ia_conv3x3_bf16_plan(C.byref(d), *out), 'ia_conv3x3_bf16_plan')
+    return [tuple(int(o[l]) for o in out) for l in range(len(sizes))]
+
+
 def conv3x3_bf16(x, wp, bias, cout, relu=False):
     """one tensor, one group: see conv3x3_bf16_levels"""
     y = torch.empty((x.shape[0], cout, x.shape[2], x.shape[3]), dtype=torch.bfloat16, device=x.device,

@@ -7,23 +7,33 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize('B,H,W,ci,co,relu,bias', [
-    (1, 7, 11, 32, 256, False, False),        # one partial tile
-    (2, 13, 21, 64, 256, True, True),
-    (1, 25, 42, 256, 256, True, True),        # P5
-    (2, 50, 84, 256, 256, True, True),        # P4: 9 x 28 tiles
-    (1, 100, 168, 256, 256, False, True),     # P3: 10 x 24 tiles
-    (1, 33, 17, 96, 512, True, True),         # two column blocks, Cin not a power of two
-    (8, 100, 168, 64, 512, True, True),       # two column tiles, many workgroups
-    (2, 40, 56, 64, 64, True, True),          # ResNet stage 1: the (2, 2, 2) variant, second wavefront column all padding
-    (2, 37, 53, 128, 128, True, True),        # ResNet stage 2: (2, 2, 2), 128-pixel tiles with overhang
-    (1, 25, 42, 512, 512, True, True),        # ResNet stage 4
-    (1, 20, 30, 64, 96, False, True),         # 64 < Cout <= 128, partial second column
-    (16, 100, 168, 256, 256, True, True),     # config 3's head tower on P3 at its batch: the (4, 1, 4) variant with the fragment ring
-    (3, 61, 47, 160, 320, True, True),        # odd sizes, five chunks, a partial second column tile
-])
-def test_conv3x3_bf16_matches_fp64_convolution(B, H, W, ci, co, relu, bias):
+CASES = [
+    (1, 7, 11, 32, 256, False, False, None),        # one partial tile
+    (2, 13, 21, 64, 256, True, True, None),
+    (1, 25, 42, 256, 256, True, True, None),        # P5
+    (2, 50, 84, 256, 256, True, True, None),        # P4: 9 x 28 tiles
+    (1, 100, 168, 256, 256, False, True, None),     # P3: 10 x 24 tiles
+    (1, 33, 17, 96, 512, True, True, None),         # two column blocks, Cin not a power of two
+    (8, 100, 168, 64, 512, True, True, None),       # two column tiles, many workgroups
+    (2, 40, 56, 64, 64, True, True, None),          # ResNet stage 1: the (2, 2, 2) variant, second wavefront column all padding
+    (2, 37, 53, 128, 128, True, True, None),        # ResNet stage 2: (2, 2, 2), 128-pixel tiles with overhang
+    (1, 25, 42, 512, 512, True, True, None),        # ResNet stage 4
+    (1, 20, 30, 64, 96, False, True, None),         # 64 < Cout <= 128, partial second column
+    # the (4, 1, 4) variant with the fragment ring, eight chunks as in config 3's head tower, forced at a small map
+    # (at the tower's own size, batch 16 at 100 x 168, this was the file's slowest case; the product's route to the
+    # variant -- a launch of its own for the large map -- is pinned exactly in tests/test_gpu_conv3x3_bf16_edges.py)
+    (2, 25, 42, 256, 256, True, True, '41'),
+    (3, 61, 47, 160, 320, True, True, None),        # odd sizes, five chunks, a partial second column tile
+]
+
+
+@pytest.mark.parametrize('B,H,W,ci,co,relu,bias,force', CASES,
+                         ids=['-'.join(str(v) for v in c[:7]) + ('-forced' + c[7] if c[7] else '') for c in CASES])
+def test_conv3x3_bf16_matches_fp64_convolution(B, H, W, ci, co, relu, bias, force, monkeypatch):
     from iouaware import ops
+    if force:
+        monkeypatch.setenv('IA_CONV3_VARIANT', force)
+        assert ops.conv3x3_bf16_plan([(H, W)], ci, co, batch=B)[0][0] == 414
     g = torch.Generator(device='cuda').manual_seed(H * W + ci)
     x = torch.randn(B, ci, H, W, device='cuda', generator=g).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     w = (torch.randn(co, ci, 3, 3, device='cuda', generator=g) * (2.0 / (9 * ci)) ** 0.5).to(torch.bfloat16)
