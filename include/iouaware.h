@@ -1435,6 +1435,67 @@ int ia_ssd_get_bboxes(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batc
                       float iou_thr, int max_per_img, void *workspace, size_t workspace_bytes, float *dets,
                       int32_t *labels, int32_t *rows, int32_t *num, int32_t *overflow, void *stream);
 
+/* ------------------------------------------------------------------ SSD: training loss (csrc/ssdloss.hip)
+ * SSDHead.loss / loss_single of the reference (anchor_heads/ssd_head.py, IoU_balanced_* off) for a whole
+ * batch: softmax cross-entropy of every anchor row, hard-negative mining, smooth-L1 on the positives.
+ * Geometry, level pointers and row order are those of the decode entries above (fp32 NCHW maps consumed
+ * in place, dtype must be IA_F32; batch * num_levels <= 65535).  Targets are image-major:
+ * labels (B, R) int64 in 0..C (0 = background; a negative value is neither positive nor negative),
+ * label_weights (B, R) fp32, bbox_targets / bbox_weights (B, R, 4) fp32, 16-byte aligned.
+ * avg_factor: *avg_factor_dev (a device scalar) when non-NULL, else the host value avg_factor (> 0) --
+ * the convention of ia_head_targets.
+ *
+ * ia_ssd_loss_rows (stage 1): lse = max + log(sum exp(x - max)) through the softmax statistics of the
+ *     decode, ce = (lse - x[label]) * label_weight -> ce, lse (B, R).  box_partials (may be NULL):
+ *     (B, nparts) fp64, nparts from ia_ssd_loss_partials: every workgroup's sum over its rows of
+ *     sum_k bbox_weight_k * smoothl1(pred_k - target_k, beta) (|d| < beta: 0.5 d^2 / beta, else
+ *     |d| - 0.5 beta), each slot written by exactly one workgroup.  beta <= 0: IA_E_ARG.
+ * ia_ssd_mine (stage 2): per image num_pos = #(label > 0), num_neg = #(label == 0),
+ *     k = min(neg_pos_ratio * num_pos, num_neg), formed on the device; the k-th largest ce among the
+ *     negatives by an exact radix select (any R < 2^31; the keys stay in LDS for
+ *     R <= ia_ssd_mine_lds_rows()).  TIE RULE: with t the k-th largest value, a negative is selected
+ *     when ce > t, or when ce == t and it is among the first k - #(ce > t) such rows in ascending row
+ *     order (-0.0 counts as +0.0).  sel (B, R) uint8: 1 for positives and selected negatives;
+ *     counts (B, 2) int32 = (num_pos, k); losses (B, 2) fp32 = ((sum_pos ce + sum_selected ce) /
+ *     avg_factor, sum of the box partials / avg_factor): fp64 sums in a fixed order, rounded once.
+ *     k = 0 gives a classification loss of 0.  neg_pos_ratio < 0: IA_E_ARG.
+ * ia_ssd_loss_bwd: every element of every gradient map, exactly once (no memset needed): the C + 1 class
+ *     gradients of a row are grad_losses[b][0] / avg_factor * label_weight * (exp(x - lse) - [c == label])
+ *     when sel (exp(x - lse) is evaluated as exp(x - max) / sum on the row's softmax statistics, formed
+ *     again: lse rounded to fp32 would cost up to half an ulp of lse in the exponent), else +0.0; the box gradients grad_losses[b][1] / avg_factor * bbox_weight_k *
+ *     d smoothl1 (+0.0 where the weight is 0).  grads: the gradient maps, shaped like the head outputs,
+ *     not the head outputs themselves (IA_E_ARG).  grad_losses (B, 2) fp32 on the device.
+ * ia_ssd_head_loss_fwd / _bwd: the node: stage 1 + stage 2 (2 launches), and the backward (1 launch) on
+ *     the workspace the forward filled.  Workspace: ia_ssd_head_loss_workspace_bytes (0: unsupported
+ *     geometry / batch), 256-byte aligned, a smaller one is IA_E_ARG;
+ *     ia_ssd_head_loss_workspace_layout gives the byte offsets of ce (B, R) fp32, lse (B, R) fp32,
+ *     sel (B, R) uint8, counts (B, 2) int32 and the box partials (B, nparts) fp64.
+ * No floating-point atomics and none on global memory (the digit counters of the radix select are
+ * integer LDS atomics): the same bits in every run.  No host synchronisation.                          */
+int ia_ssd_mine_lds_rows(void);
+int ia_ssd_loss_partials(const ia_ssd_geom *g, int32_t *nparts);
+int ia_ssd_loss_rows(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype, const int64_t *labels,
+                     const float *label_weights, const float *bbox_targets, const float *bbox_weights, float beta,
+                     float *ce, float *lse, double *box_partials, void *stream);
+int ia_ssd_mine(const float *ce, const int64_t *labels, int batch, int R, int neg_pos_ratio,
+                const double *box_partials, int nparts, const float *avg_factor_dev, float avg_factor, uint8_t *sel,
+                int32_t *counts, float *losses, void *stream);
+int ia_ssd_loss_bwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype, const int64_t *labels,
+                    const float *label_weights, const float *bbox_targets, const float *bbox_weights, float beta,
+                    const uint8_t *sel, const float *grad_losses, const float *avg_factor_dev, float avg_factor,
+                    const ia_ssd_level_ptrs *grads, void *stream);
+size_t ia_ssd_head_loss_workspace_bytes(const ia_ssd_geom *g, int batch);
+int ia_ssd_head_loss_workspace_layout(const ia_ssd_geom *g, int batch, size_t offsets[5]);
+int ia_ssd_head_loss_fwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype,
+                         const int64_t *labels, const float *label_weights, const float *bbox_targets,
+                         const float *bbox_weights, const float *avg_factor_dev, float avg_factor, int neg_pos_ratio,
+                         float beta, void *workspace, size_t workspace_bytes, float *losses, void *stream);
+int ia_ssd_head_loss_bwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype,
+                         const int64_t *labels, const float *label_weights, const float *bbox_targets,
+                         const float *bbox_weights, const float *avg_factor_dev, float avg_factor, float beta,
+                         const void *workspace, size_t workspace_bytes, const float *grad_losses,
+                         const ia_ssd_level_ptrs *grads, void *stream);
+
 /* ------------------------------------------------------------------ self-test
  * Elementwise fp32 math used by the kernels, exposed so tests can pin the
  * device implementation bit-for-bit: op 0 exp, 1 log, 2 sigmoid, 3 sqrt,

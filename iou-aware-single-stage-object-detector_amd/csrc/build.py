@@ -15,9 +15,9 @@ SOURCES = ['capi.hip', 'decode.hip', 'select.hip', 'nms.hip', 'loss.hip', 'eleme
            'softnms.hip', 'preproc.hip', 'wino.hip', 'gemm.hip', 'lazynms.hip', 'headloss.hip', 'gconv.hip',
            'trainops.hip', 'bignms.hip', 'conv3x3_bf16.hip', 'conv3x3_bf16_bwd.hip', 'conv1x1_stream.hip', 'im2col.hip', 'nms64.hip', 'stem.hip',
            'groupnorm.hip', 'pointdecode.hip', 'pointloss.hip', 'gconv_bf16.hip', 'gconv_bwd.hip', 'deform.hip',
-           'masked_conv.hip', 'guideddecode.hip', 'wino_split_gemm.hip', 'l2norm.hip', 'ssddecode.hip']
+           'masked_conv.hip', 'guideddecode.hip', 'wino_split_gemm.hip', 'l2norm.hip', 'ssddecode.hip', 'ssdloss.hip']
 HEADERS = ['ia_math.hpp', 'ia_block.hpp', 'ia_internal.hpp', 'ia_loss.hpp', 'ia_headloss.hpp', 'ia_rowmax_dev.hpp', 'ia_gather_dev.hpp', 'ia_nms.hpp', 'ia_conv3.hpp', 'ia_wino.hpp', 'ia_softmax_dev.hpp',
-           'ia_compact_dev.hpp', '../../include/iouaware.h']
+           'ia_compact_dev.hpp', 'ia_ssd.hpp', '../../include/iouaware.h']
 OUT = os.path.join(HERE, 'libiouaware_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fhip-fp32-correctly-rounded-divide-sqrt', '-fno-gpu-rdc',

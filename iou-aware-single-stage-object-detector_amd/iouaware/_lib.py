@@ -381,6 +381,15 @@ SIGNATURES = {
     'ia_ssd_workspace_layout': (_i, [_SG, _i, C.POINTER(_sz * 8)]),
     'ia_ssd_get_bboxes': (_i, [_SG, _SP, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                _vp]),
+    'ia_ssd_mine_lds_rows': (_i, []),
+    'ia_ssd_loss_partials': (_i, [_SG, C.POINTER(C.c_int32)]),
+    'ia_ssd_loss_rows': (_i, [_SG, _SP, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    'ia_ssd_mine': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp]),
+    'ia_ssd_loss_bwd': (_i, [_SG, _SP, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _SP, _vp]),
+    'ia_ssd_head_loss_workspace_bytes': (_sz, [_SG, _i]),
+    'ia_ssd_head_loss_workspace_layout': (_i, [_SG, _i, C.POINTER(_sz * 5)]),
+    'ia_ssd_head_loss_fwd': (_i, [_SG, _SP, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _f, _vp, _sz, _vp, _vp]),
+    'ia_ssd_head_loss_bwd': (_i, [_SG, _SP, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _sz, _vp, _SP, _vp]),
     'ia_test_math': (_i, [_i, _vp, _vp, _vp, _i64, _vp]),
 }
 

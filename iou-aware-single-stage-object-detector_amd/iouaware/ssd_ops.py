@@ -1,6 +1,8 @@
-"""torch front-end of the SSD kernels: the L2Norm layer (csrc/l2norm.hip) and the post-conv path of
+"""torch front-end of the SSD kernels: the L2Norm layer (csrc/l2norm.hip), the post-conv path of
 SSDHead (csrc/ssddecode.hip): row scores, the compaction of the rows above score_thr, gather / decode,
-the shared batched NMS (ia_ssd_get_bboxes), and its stage entries.
+the shared batched NMS (ia_ssd_get_bboxes), and its stage entries; and the training loss
+(csrc/ssdloss.hip): cross-entropy rows, hard-negative mining, smooth-L1, as one autograd node
+(ssd_head_loss) and its stage entries.
 Device tensors only (fp32, NCHW; other layouts are converted), launched on the current torch stream,
 like ops.py."""
 import ctypes as C
@@ -10,8 +12,8 @@ import torch
 
 from . import _lib
 from ._lib import IA_F32, SsdGeom, SsdLevelPtrs
-from .ops import (_det_outputs, _meta_tensors, _ptr, _require_gpu, _state_workspace, _stream, nms_indices,
-                  to_nchw)
+from .ops import (_det_outputs, _meta_tensors, _own_workspace, _ptr, _require_gpu, _state_workspace, _stream,
+                  nms_indices, to_nchw)
 
 
 def l2norm(x, weight, eps=1e-10):
@@ -236,3 +238,172 @@ def ssd_get_bboxes_per_class(geom, cls, reg, img_shapes, scale_factors, rescale,
         n = d_all.shape[0]
         dets[b, :n], labels[b, :n], rows[b, :n], num[b] = d_all, l_all, r_all.to(torch.int32), n
     return dets, labels, rows, num
+
+
+# ------------------------------------------------------------------ training loss (csrc/ssdloss.hip)
+_SSD_LOSS_VIEWS = ('ce', 'lse', 'sel', 'counts', 'partials')
+
+
+def ssd_mine_lds_rows():
+    """rows up to which ia_ssd_mine keeps its keys in LDS (above: re-read from global memory)"""
+    return int(_lib.lib().ia_ssd_mine_lds_rows())
+
+
+def ssd_loss_partials(geom):
+    """number of fp64 box partial sums per image that ia_ssd_loss_rows writes"""
+    n = C.c_int32()
+    _lib.check(_lib.lib().ia_ssd_loss_partials(geom.ref(), C.byref(n)), 'ia_ssd_loss_partials')
+    return n.value
+
+
+def _ssd_targets(B, R, labels, label_weights, bbox_targets, bbox_weights):
+    """the four image-major target tensors, checked and made contiguous"""
+    out = []
+    for name, t, dtype, shape in (('labels', labels, torch.int64, (B, R)),
+                                  ('label_weights', label_weights, torch.float32, (B, R)),
+                                  ('bbox_targets', bbox_targets, torch.float32, (B, R, 4)),
+                                  ('bbox_weights', bbox_weights, torch.float32, (B, R, 4))):
+        _require_gpu(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError('%s has shape %s, expected %s' % (name, tuple(t.shape), shape))
+        out.append(t.detach().to(dtype).contiguous())
+    return out
+
+
+def _ssd_avg(avg_factor):
+    """-> (device pointer or NULL, host value, tensor kept alive): the convention of ia_head_targets"""
+    if isinstance(avg_factor, torch.Tensor):
+        _require_gpu(avg_factor, 'avg_factor')
+        t = avg_factor.detach().to(torch.float32).reshape(-1)[:1].contiguous()
+        return _ptr(t), 0.0, t
+    if not float(avg_factor) > 0:
+        raise ValueError('avg_factor=%r: must be positive' % (avg_factor,))
+    return C.c_void_p(0), float(avg_factor), None
+
+
+def _check_loss_cfg(neg_pos_ratio, beta):
+    if int(neg_pos_ratio) != neg_pos_ratio or neg_pos_ratio < 0:
+        raise ValueError('neg_pos_ratio=%r: must be an integer >= 0' % (neg_pos_ratio,))
+    if not float(beta) > 0:
+        raise ValueError('beta=%r: the smooth-L1 beta must be positive' % (beta,))
+
+
+def ssd_loss_rows(geom, cls, reg, labels, label_weights, bbox_targets, bbox_weights, beta=1.0):
+    """stage 1 -> ce (B, R), lse (B, R) fp32 and the box partial sums (B, nparts) fp64"""
+    _check_loss_cfg(0, beta)
+    p, B, keep = _ssd_ptrs(geom, cls, reg)
+    tg = _ssd_targets(B, geom.R, labels, label_weights, bbox_targets, bbox_weights)
+    dev = keep[0][0].device
+    ce = torch.empty((B, geom.R), dtype=torch.float32, device=dev)
+    lse = torch.empty_like(ce)
+    parts = torch.empty((B, ssd_loss_partials(geom)), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().ia_ssd_loss_rows(geom.ref(), C.byref(p), B, IA_F32, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]),
+                                           _ptr(tg[3]), float(beta), _ptr(ce), _ptr(lse), _ptr(parts), _stream()),
+               'ia_ssd_loss_rows')
+    return ce, lse, parts
+
+
+def ssd_mine(ce, labels, neg_pos_ratio, avg_factor=1.0, box_partials=None):
+    """stage 2 on ce (B, R) fp32 and labels (B, R) int64 -> sel (B, R) uint8, counts (B, 2) int32 =
+    (num_pos, k), losses (B, 2) fp32 (classification, box; box 0 without partials)"""
+    _check_loss_cfg(neg_pos_ratio, 1.0)
+    _require_gpu(ce, 'ce')
+    _require_gpu(labels, 'labels')
+    if ce.dim() != 2 or ce.dtype != torch.float32 or labels.dtype != torch.int64 or labels.shape != ce.shape:
+        raise ValueError('ce must be (B, R) float32 and labels (B, R) int64')
+    ce, labels = ce.contiguous(), labels.contiguous()
+    B, R = ce.shape
+    dev = ce.device
+    nparts = 0
+    if box_partials is not None:
+        _require_gpu(box_partials, 'box_partials')
+        if box_partials.dtype != torch.float64 or box_partials.dim() != 2 or box_partials.shape[0] != B:
+            raise ValueError('box_partials must be (B, nparts) float64')
+        box_partials = box_partials.contiguous()
+        nparts = box_partials.shape[1]
+    avg_p, avg_h, avg_keep = _ssd_avg(avg_factor)
+    sel = torch.empty((B, R), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    losses = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ia_ssd_mine(_ptr(ce), _ptr(labels), B, R, int(neg_pos_ratio), _ptr(box_partials), nparts,
+                                      avg_p, avg_h, _ptr(sel), _ptr(counts), _ptr(losses), _stream()), 'ia_ssd_mine')
+    return sel, counts, losses
+
+
+def ssd_loss_workspace_views(geom, B, ws):
+    """dict of views into the workspace of ia_ssd_head_loss_fwd (ia_ssd_head_loss_workspace_layout)"""
+    off = (C.c_size_t * 5)()
+    _lib.check(_lib.lib().ia_ssd_head_loss_workspace_layout(geom.ref(), B, C.byref(off)),
+               'ia_ssd_head_loss_workspace_layout')
+    shapes = ((torch.float32, (B, geom.R)), (torch.float32, (B, geom.R)), (torch.uint8, (B, geom.R)),
+              (torch.int32, (B, 2)), (torch.float64, (B, ssd_loss_partials(geom))))
+    out = {}
+    for i, (name, (dtype, shape)) in enumerate(zip(_SSD_LOSS_VIEWS, shapes)):
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        out[name] = ws[off[i]:off[i] + n].view(dtype).view(*shape)
+    return out
+
+
+class _SsdHeadLossFn(torch.autograd.Function):
+    """SSD's loss of a batch (csrc/ssdloss.hip): 2 launches forward, 1 backward, no host
+    synchronisation.  Outputs: loss_cls (B,), loss_bbox (B,)."""
+
+    @staticmethod
+    def forward(ctx, geom, targets, avg_factor, neg_pos_ratio, beta, workspace, grads, *outs):
+        L = geom.L
+        p, B, keep = _ssd_ptrs(geom, outs[:L], outs[L:])
+        dev = keep[0][0].device
+        tg = _ssd_targets(B, geom.R, *targets)
+        avg_p, avg_h, avg_keep = _ssd_avg(avg_factor)
+        nbytes = _lib.lib().ia_ssd_head_loss_workspace_bytes(geom.ref(), B)
+        if nbytes == 0:
+            raise _lib.IouAwareLibraryError('unsupported geometry / batch for ia_ssd_head_loss')
+        # own buffer: it carries lse and the selection from forward to backward
+        ws = _own_workspace(dev, nbytes) if workspace is None else workspace
+        if ws.numel() < nbytes:
+            raise ValueError('workspace has %d bytes, ia_ssd_head_loss needs %d' % (ws.numel(), nbytes))
+        losses = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().ia_ssd_head_loss_fwd(
+            geom.ref(), C.byref(p), B, IA_F32, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), _ptr(tg[3]), avg_p, avg_h,
+            int(neg_pos_ratio), float(beta), _ptr(ws), ws.numel(), _ptr(losses), _stream()), 'ia_ssd_head_loss_fwd')
+        ctx.geom, ctx.B, ctx.beta, ctx.ws, ctx.grads = geom, B, float(beta), ws, grads
+        ctx.keep = (p, keep, tg, (avg_p, avg_h, avg_keep))
+        ctx.set_materialize_grads(False)
+        return losses[:, 0], losses[:, 1]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box):
+        p, (cls, reg), tg, (avg_p, avg_h, _) = ctx.keep
+        geom, B, dev = ctx.geom, ctx.B, cls[0].device
+        z = torch.zeros(B, dtype=torch.float32, device=dev)
+        gin = torch.stack([z if g is None else g.detach().to(torch.float32).reshape(B) for g in (g_cls, g_box)],
+                          dim=1).contiguous()
+        grads = ctx.grads
+        if grads is None:
+            grads = [torch.empty_like(t) for t in cls + reg]
+        gp = SsdLevelPtrs()
+        for l in range(geom.L):
+            gp.cls[l], gp.reg[l] = grads[l].data_ptr(), grads[geom.L + l].data_ptr()
+        _lib.check(_lib.lib().ia_ssd_head_loss_bwd(
+            geom.ref(), C.byref(p), B, IA_F32, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), _ptr(tg[3]), avg_p, avg_h,
+            ctx.beta, _ptr(ctx.ws), ctx.ws.numel(), _ptr(gin), C.byref(gp), _stream()), 'ia_ssd_head_loss_bwd')
+        return (None,) * 7 + tuple(grads)
+
+
+def ssd_head_loss(geom, cls_scores, bbox_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factor,
+                  neg_pos_ratio=3, beta=1.0, workspace=None, grads=None):
+    """SSDHead's loss for a batch on the HIP node -> (loss_cls (B,), loss_bbox (B,)), differentiable in
+    the head outputs.  cls_scores / bbox_preds: per-level fp32 device tensors (other layouts are
+    converted by to_nchw); labels (B, R) int64 in 0..C, label_weights (B, R), bbox_targets / bbox_weights
+    (B, R, 4); avg_factor: a python number or a device scalar; neg_pos_ratio an integer >= 0; beta > 0.
+    Launched on the current stream, no device-to-host copy.
+    workspace / grads: caller-owned buffers (tests: guard checks); grads = the 2 L contiguous gradient
+    maps (class maps first) the backward writes and returns."""
+    _check_loss_cfg(neg_pos_ratio, beta)
+    outs = list(cls_scores) + list(bbox_preds)
+    if len(outs) != 2 * geom.L:
+        raise AssertionError('expected %d levels' % geom.L)
+    for t in outs:
+        _require_gpu(t, 'head output')
+    return _SsdHeadLossFn.apply(geom, (labels, label_weights, bbox_targets, bbox_weights), avg_factor,
+                                int(neg_pos_ratio), float(beta), workspace, grads, *outs)
