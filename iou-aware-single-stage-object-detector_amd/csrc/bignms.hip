@@ -30,23 +30,22 @@ static size_t sort_temp_bytes(int n) { return (size_t)n * 16 + ((size_t)4 << 20)
 
 static BigLayout big_layout(int n)
 {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     BigLayout w;
     size_t o = 0;
     const size_t N = (size_t)n;
-    w.keys_in = o; o = up(o + N * 8);
-    w.keys_out = o; o = up(o + N * 8);
-    w.sort_tmp = o; o = up(o + sort_temp_bytes(n));
-    w.sbox = o; o = up(o + N * 16);
-    w.sscore = o; o = up(o + N * 4);
-    w.supp = o; o = up(o + N * 4);
-    w.kept = o; o = up(o + N * 4);
-    w.kept_count = o; o = up(o + 256);
-    w.keepflag = o; o = up(o + N);
-    w.cdets = o; o = up(o + (size_t)kS * 5 * 4);
-    w.ckeep = o; o = up(o + (size_t)kS * 4);
-    w.ccount = o; o = up(o + 256);
-    w.inner = o; o = up(o + nms_single_workspace_bytes(kS));
+    w.keys_in = o; o = align256(o + N * 8);
+    w.keys_out = o; o = align256(o + N * 8);
+    w.sort_tmp = o; o = align256(o + sort_temp_bytes(n));
+    w.sbox = o; o = align256(o + N * 16);
+    w.sscore = o; o = align256(o + N * 4);
+    w.supp = o; o = align256(o + N * 4);
+    w.kept = o; o = align256(o + N * 4);
+    w.kept_count = o; o = align256(o + 256);
+    w.keepflag = o; o = align256(o + N);
+    w.cdets = o; o = align256(o + (size_t)kS * 5 * 4);
+    w.ckeep = o; o = align256(o + (size_t)kS * 4);
+    w.ccount = o; o = align256(o + 256);
+    w.inner = o; o = align256(o + nms_single_workspace_bytes(kS));
     w.total = o;
     return w;
 }

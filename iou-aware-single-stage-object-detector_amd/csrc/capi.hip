@@ -9,51 +9,65 @@
 
 namespace ia {
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 static void base_from_geom(const ia_head_geom *g, BaseAnchors &ba)
 {
     memcpy(ba.v, g->base_anchors, sizeof(ba.v));
 }
 
-struct WsLayout { size_t off[11]; size_t total; int32_t N, R, Rs; };
-
-static int ws_layout(const ia_head_geom *g, int batch, WsLayout &w)
+int carve_bboxes(const ia_head_geom *g, int batch, void *base, BboxWorkspace &w)
 {
-    LevelTable t;
+    LevelTable &t = w.t;
     int rc = make_level_table(g, t);
     if (rc) return rc;
     if (batch < 1) return IA_E_ARG;
+    w.batch = batch;
     w.N = t.anchor_off[t.num_levels];
     w.R = t.cand_off[t.num_levels];
     if (w.R > IA_MAX_CANDIDATES) return IA_E_LIMIT_BOXES;
     w.Rs = (w.R + 63) / 64 * 64;
-    size_t o = 0;
     const size_t B = (size_t)batch, C = (size_t)t.C;
-    w.off[0] = o; o = align_up(o + B * w.N * sizeof(float), 256);            // rowmax
-    w.off[1] = o; o = align_up(o + B * w.R * sizeof(int32_t), 256);          // cand_idx
-    w.off[2] = o; o = align_up(o + B * w.R * 4 * sizeof(float), 256);        // boxes
-    w.off[3] = o; o = align_up(o + B * C * w.Rs * sizeof(float), 256);       // scores_t
-    w.off[4] = o; o = align_up(o + B * C * sizeof(int32_t), 256);            // keep_count
-    w.off[5] = o; o = align_up(o + B * C * w.Rs * sizeof(int32_t), 256);     // keep_rows
-    w.off[6] = o; o = align_up(o + B * w.R * sizeof(float), 256);            // best_score
-    size_t noff[3];
-    w.off[7] = o; o = align_up(o + nms_workspace_bytes(batch, w.R, t.C, noff), 256);   // NMS stage
-    o = align_up(o + finalize_workspace_bytes(batch, w.Rs, t.C), 256);                 // + final keys
-    w.off[8] = o; o = align_up(o + select_workspace_bytes(t, batch), 256);             // top-k parts
-    w.off[9] = o; o = align_up(o + lazy_workspace_bytes(batch, w.Rs, t.C), 256);       // lazy NMS
-    w.off[10] = o; o = align_up(o + B * sizeof(int32_t), 256);                         // need_full
-    w.total = o;
+    Carver c(base);
+    w.off[0] = c.take(w.rowmax, B * w.N * sizeof(float));
+    w.off[1] = c.take(w.cand_idx, B * w.R * sizeof(int32_t));
+    w.off[2] = c.take(w.boxes, B * w.R * 4 * sizeof(float));
+    w.off[3] = c.take(w.scores_t, B * C * w.Rs * sizeof(float));
+    w.off[4] = c.take(w.keep_count, B * C * sizeof(int32_t));
+    w.off[5] = c.take(w.keep_rows, B * C * w.Rs * sizeof(int32_t));
+    w.off[6] = c.take(w.best_score, B * w.R * sizeof(float));
+    w.off[7] = c.take(w.nms, nms_tail_workspace_bytes(batch, w.R, t.C));
+    w.select_off = c.take(w.select, select_workspace_bytes(t, batch));
+    c.take(w.lazy, lazy_workspace_bytes(batch, w.Rs, t.C));
+    c.take(w.need_full, B * sizeof(int32_t));
+    w.bytes = c.bytes;
     return 0;
 }
 
-int get_bboxes_select_offset(const ia_head_geom *g, int batch, size_t *offset)
+int launch_bboxes_nms(const BboxWorkspace &w, float score_thr, float iou_thr, int max_per_img,
+                      int candidates, float *dets, int32_t *labels, int32_t *rows, int32_t *num,
+                      hipStream_t s)
 {
-    WsLayout w;
-    int rc = ws_layout(g, batch, w);
-    if (rc) return rc;
-    *offset = w.off[8];
-    return 0;
+    const NmsLazy lazy = {w.lazy, w.need_full, candidates};
+    return launch_nms_tail(w.boxes, w.scores_t, w.best_score, w.batch, w.R, w.Rs, w.t.C, score_thr,
+                           iou_thr, max_per_img, w.nms, candidates >= 0 ? &lazy : nullptr,
+                           w.keep_count, w.keep_rows, dets, labels, rows, num, s);
+}
+
+// the workspace of ia_multiclass_nms_lazy: the complete path's | lazy NMS | need_full (B) |
+// keep_count (B, C) | keep_rows (B, C, Rs)
+struct LazyNmsWorkspace { void *full, *lazy; int32_t *need_full, *keep_count, *keep_rows; size_t bytes; };
+
+static LazyNmsWorkspace carve_nms_lazy(int batch, int R, int C, void *base)
+{
+    const int Rs = (R + 63) / 64 * 64;
+    LazyNmsWorkspace w;
+    Carver c(base);
+    c.take(w.full, nms_tail_workspace_bytes(batch, R, C));
+    c.take(w.lazy, lazy_workspace_bytes(batch, Rs, C));
+    c.take(w.need_full, (size_t)batch * sizeof(int32_t));
+    c.take(w.keep_count, (size_t)batch * C * sizeof(int32_t));
+    c.take(w.keep_rows, (size_t)batch * C * Rs * sizeof(int32_t));
+    w.bytes = c.bytes;
+    return w;
 }
 
 __global__ void k_test_math(int op, const float *x, const float *y, float *out, int64_t n)
@@ -172,10 +186,7 @@ int ia_gather_decode(const ia_head_geom *g, const ia_level_ptrs *p, int batch, i
 size_t ia_multiclass_nms_workspace_bytes(int batch, int R, int C)
 {
     if (batch < 1 || R < 1 || R > IA_MAX_CANDIDATES || C < 1) return 0;
-    size_t off[3];
-    const int Rs = (R + 63) / 64 * 64;
-    return (ia::nms_workspace_bytes(batch, R, C, off) + 255) / 256 * 256 +
-           ia::finalize_workspace_bytes(batch, Rs, C);
+    return ia::nms_tail_workspace_bytes(batch, R, C);
 }
 
 int ia_multiclass_nms(const float *boxes, const float *scores_t, const float *best_score,
@@ -188,26 +199,16 @@ int ia_multiclass_nms(const float *boxes, const float *scores_t, const float *be
     if (!workspace) return IA_E_ARG;
     if (workspace_bytes < ia_multiclass_nms_workspace_bytes(batch, R, C) || workspace_bytes == 0)
         return IA_E_WORKSPACE;
-    int rc = ia::launch_nms(boxes, scores_t, best_score, batch, R, Rs, C, score_thr, iou_thr,
-                            workspace, keep_count, keep_rows, (hipStream_t)stream);
-    if (rc) return rc;
-    size_t off[3];
-    char *fin_ws = static_cast<char *>(workspace) +
-                   (ia::nms_workspace_bytes(batch, R, C, off) + 255) / 256 * 256;
-    return ia::launch_finalize(boxes, scores_t, keep_count, keep_rows, batch, R, Rs, C,
-                               max_per_img, fin_ws, dets, labels, rows, num, (hipStream_t)stream);
+    return ia::launch_nms_tail(boxes, scores_t, best_score, batch, R, Rs, C, score_thr, iou_thr,
+                               max_per_img, workspace, nullptr, keep_count, keep_rows, dets, labels,
+                               rows, num, (hipStream_t)stream);
 }
 
 // stage-level lazy NMS: lazy walk first, the complete path (gated) for the images it cannot finish
 size_t ia_multiclass_nms_lazy_workspace_bytes(int batch, int R, int C)
 {
-    const size_t full = ia_multiclass_nms_workspace_bytes(batch, R, C);
-    if (full == 0) return 0;
-    const int Rs = (R + 63) / 64 * 64;
-    return ia::align_up(full, 256) + ia::align_up(ia::lazy_workspace_bytes(batch, Rs, C), 256) +
-           ia::align_up((size_t)batch * sizeof(int32_t), 256) +                      // need_full
-           ia::align_up((size_t)batch * C * sizeof(int32_t), 256) +                  // keep_count
-           ia::align_up((size_t)batch * C * Rs * sizeof(int32_t), 256);              // keep_rows
+    if (ia_multiclass_nms_workspace_bytes(batch, R, C) == 0) return 0;
+    return ia::carve_nms_lazy(batch, R, C, nullptr).bytes;
 }
 
 int ia_multiclass_nms_lazy(const float *boxes, const float *scores_t, const float *best_score,
@@ -220,35 +221,18 @@ int ia_multiclass_nms_lazy(const float *boxes, const float *scores_t, const floa
     if (!workspace || candidates < 0) return IA_E_ARG;
     const size_t need = ia_multiclass_nms_lazy_workspace_bytes(batch, R, C);
     if (need == 0 || workspace_bytes < need) return IA_E_WORKSPACE;
-    char *ws = static_cast<char *>(workspace);
-    void *full_ws = ws;
-    ws += ia::align_up(ia_multiclass_nms_workspace_bytes(batch, R, C), 256);
-    void *lazy_ws = ws;
-    ws += ia::align_up(ia::lazy_workspace_bytes(batch, Rs, C), 256);
-    int32_t *need_full = reinterpret_cast<int32_t *>(ws);
-    ws += ia::align_up((size_t)batch * sizeof(int32_t), 256);
-    int32_t *kc = reinterpret_cast<int32_t *>(ws);
-    ws += ia::align_up((size_t)batch * C * sizeof(int32_t), 256);
-    int32_t *kr = reinterpret_cast<int32_t *>(ws);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ia::launch_lazy_nms(boxes, scores_t, batch, R, Rs, C, score_thr, iou_thr, max_per_img,
-                                 candidates, lazy_ws, dets, labels, rows, num, need_full, s);
-    if (rc) return rc;
-    if ((rc = ia::launch_nms(boxes, scores_t, best_score, batch, R, Rs, C, score_thr, iou_thr,
-                             full_ws, kc, kr, s, need_full)))
-        return rc;
-    size_t off[3];
-    char *fin_ws = static_cast<char *>(full_ws) +
-                   (ia::nms_workspace_bytes(batch, R, C, off) + 255) / 256 * 256;
-    return ia::launch_finalize(boxes, scores_t, kc, kr, batch, R, Rs, C, max_per_img, fin_ws, dets,
-                               labels, rows, num, s, need_full);
+    const ia::LazyNmsWorkspace w = ia::carve_nms_lazy(batch, R, C, workspace);
+    const ia::NmsLazy lazy = {w.lazy, w.need_full, candidates};
+    return ia::launch_nms_tail(boxes, scores_t, best_score, batch, R, Rs, C, score_thr, iou_thr,
+                               max_per_img, w.full, &lazy, w.keep_count, w.keep_rows, dets, labels,
+                               rows, num, (hipStream_t)stream);
 }
 
 size_t ia_multiclass_soft_nms_workspace_bytes(int batch, int R, int C)
 {
     if (batch < 1 || R < 1 || R > IA_MAX_CANDIDATES || C < 1) return 0;
     const int Rs = (R + 63) / 64 * 64;
-    return ia::align_up((size_t)batch * C * Rs * sizeof(float), 256) +
+    return ia::align256((size_t)batch * C * Rs * sizeof(float)) +
            ia::finalize_workspace_bytes(batch, Rs, C);
 }
 
@@ -268,7 +252,7 @@ int ia_multiclass_soft_nms(const float *boxes, const float *scores_t, int batch,
                                  (hipStream_t)stream);
     if (rc) return rc;
     char *fin_ws = static_cast<char *>(workspace) +
-                   ia::align_up((size_t)batch * C * Rs * sizeof(float), 256);
+                   ia::align256((size_t)batch * C * Rs * sizeof(float));
     return ia::launch_finalize(boxes, soft, keep_count, keep_rows, batch, R, Rs, C, max_per_img,
                                fin_ws, dets, labels, rows, num, (hipStream_t)stream);
 }
@@ -282,24 +266,22 @@ int ia_soft_nms(const float *dets, int n, float iou_thr, int method, float sigma
 
 size_t ia_get_bboxes_workspace_bytes(const ia_head_geom *g, int batch)
 {
-    ia::WsLayout w;
-    if (ia::ws_layout(g, batch, w)) return 0;
-    return w.total;
+    ia::BboxWorkspace w;
+    if (ia::carve_bboxes(g, batch, nullptr, w)) return 0;
+    return w.bytes;
 }
 
 size_t ia_get_bboxes_status_offset(const ia_head_geom *g, int batch)
 {
-    ia::WsLayout w;
-    if (ia::ws_layout(g, batch, w)) return 0;
-    ia::LevelTable t;
-    ia::make_level_table(g, t);
-    return w.off[8] + ia::select_workspace_status_offset(t, batch);
+    ia::BboxWorkspace w;
+    if (ia::carve_bboxes(g, batch, nullptr, w)) return 0;
+    return w.select_off + ia::select_workspace_status_offset(w.t, batch);
 }
 
 int ia_get_bboxes_workspace_layout(const ia_head_geom *g, int batch, size_t offsets[8])
 {
-    ia::WsLayout w;
-    int rc = ia::ws_layout(g, batch, w);
+    ia::BboxWorkspace w;
+    int rc = ia::carve_bboxes(g, batch, nullptr, w);
     if (rc) return rc;
     for (int i = 0; i < 8; ++i) offsets[i] = w.off[i];
     return 0;
@@ -318,21 +300,30 @@ int ia_get_bboxes_workspace_layout(const ia_head_geom *g, int batch, size_t offs
 static std::mutex g_stage_mu;
 static struct { void *ev[2]; void *stream; bool bound; } g_stage = {{nullptr, nullptr}, nullptr, false};
 
-static int decode_stage_launches(const ia_head_geom *g, const ia_level_ptrs *p, int batch, int dtype,
+// what the decode stages of the anchor and point entries check alike, in this order: geometry and
+// batch (the layout), the pointers, the workspace's size, its 256-byte alignment
+static int carve_checked(const ia_head_geom *g, const ia_level_ptrs *p, int batch, void *workspace,
+                         size_t workspace_bytes, ia::BboxWorkspace &w)
+{
+    int rc = ia::carve_bboxes(g, batch, workspace, w);
+    if (rc) return rc;
+    if (!p || !workspace) return IA_E_ARG;
+    if (workspace_bytes < w.bytes) return IA_E_WORKSPACE;
+    if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
+    return 0;
+}
+
+static int decode_stage_launches(const ia_head_geom *g, const ia_level_ptrs *p, int dtype,
                                  const float *img_hw, const float *scale_factor, int rescale,
-                                 char *ws, hipStream_t s, ia::WsLayout &w, ia::LevelTable &t);
+                                 hipStream_t s, const ia::BboxWorkspace &w);
 
 static int decode_stage_impl(const ia_head_geom *g, const ia_level_ptrs *p, int batch, int dtype,
                              const float *img_hw, const float *scale_factor, int rescale,
                              void *workspace, size_t workspace_bytes, hipStream_t s,
-                             ia::WsLayout &w, ia::LevelTable &t)
+                             ia::BboxWorkspace &w)
 {
-    int rc = ia::ws_layout(g, batch, w);
+    int rc = carve_checked(g, p, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
-    if (!p || !workspace) return IA_E_ARG;
-    if (workspace_bytes < w.total) return IA_E_WORKSPACE;
-    if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
-    char *ws = static_cast<char *>(workspace);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_stage_mu);
@@ -342,28 +333,22 @@ static int decode_stage_impl(const ia_head_geom *g, const ia_level_ptrs *p, int 
         }                                                           // else: another stream's call records nothing
     }
     if (e0 && (rc = ia::hip_status(hipEventRecord(e0, s)))) return rc;
-    rc = decode_stage_launches(g, p, batch, dtype, img_hw, scale_factor, rescale, ws, s, w, t);
+    rc = decode_stage_launches(g, p, dtype, img_hw, scale_factor, rescale, s, w);
     if (!rc && e1) rc = ia::hip_status(hipEventRecord(e1, s));
     return rc;
 }
 
-static int decode_stage_launches(const ia_head_geom *g, const ia_level_ptrs *p, int batch, int dtype,
+static int decode_stage_launches(const ia_head_geom *g, const ia_level_ptrs *p, int dtype,
                                  const float *img_hw, const float *scale_factor, int rescale,
-                                 char *ws, hipStream_t s, ia::WsLayout &w, ia::LevelTable &t)
+                                 hipStream_t s, const ia::BboxWorkspace &w)
 {
     int rc;
-    float *rowmax = reinterpret_cast<float *>(ws + w.off[0]);
-    int32_t *cand = reinterpret_cast<int32_t *>(ws + w.off[1]);
-    float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
-    float *scores_t = reinterpret_cast<float *>(ws + w.off[3]);
-    float *best = reinterpret_cast<float *>(ws + w.off[6]);
-    ia::make_level_table(g, t);
     ia::BaseAnchors ba;
     ia::base_from_geom(g, ba);
     // row-max (+ group maxima) and the top-k's filter in one launch where the layout allows
-    if ((rc = ia::launch_rowmax_select(t, *p, batch, dtype, rowmax, cand, ws + w.off[8], s))) return rc;
-    return ia::launch_gather(t, ba, g->means, g->stds, *p, batch, dtype, cand, img_hw, scale_factor,
-                             rescale, boxes, scores_t, best, w.Rs, s);
+    if ((rc = ia::launch_rowmax_select(w.t, *p, w.batch, dtype, w.rowmax, w.cand_idx, w.select, s))) return rc;
+    return ia::launch_gather(w.t, ba, g->means, g->stds, *p, w.batch, dtype, w.cand_idx, img_hw, scale_factor,
+                             rescale, w.boxes, w.scores_t, w.best_score, w.Rs, s);
 }
 
 // lazy_candidates < 0: the complete NMS for every image (keep_count / keep_rows of all classes
@@ -375,36 +360,13 @@ static int get_bboxes_impl(const ia_head_geom *g, const ia_level_ptrs *p, int ba
                            void *workspace, size_t workspace_bytes, float *dets, int32_t *labels,
                            int32_t *rows, int32_t *num, void *stream)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
+    ia::BboxWorkspace w;
     hipStream_t s = (hipStream_t)stream;
     int rc = decode_stage_impl(g, p, batch, dtype, img_hw, scale_factor, rescale, workspace,
-                               workspace_bytes, s, w, t);
+                               workspace_bytes, s, w);
     if (rc) return rc;
-    char *ws = static_cast<char *>(workspace);
-    float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
-    float *scores_t = reinterpret_cast<float *>(ws + w.off[3]);
-    int32_t *kc = reinterpret_cast<int32_t *>(ws + w.off[4]);
-    int32_t *kr = reinterpret_cast<int32_t *>(ws + w.off[5]);
-    float *best = reinterpret_cast<float *>(ws + w.off[6]);
-    void *nms_ws = ws + w.off[7];
-    const int32_t *gate = nullptr;
-    if (lazy_candidates >= 0) {
-        int32_t *need_full = reinterpret_cast<int32_t *>(ws + w.off[10]);
-        if ((rc = ia::launch_lazy_nms(boxes, scores_t, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
-                                      max_per_img, lazy_candidates, ws + w.off[9], dets, labels,
-                                      rows, num, need_full, s)))
-            return rc;
-        gate = need_full;
-    }
-    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.R, w.Rs, t.C, score_thr, iou_thr,
-                             nms_ws, kc, kr, s, gate)))
-        return rc;
-    size_t noff[3];
-    char *fin_ws = static_cast<char *>(nms_ws) +
-                   (ia::nms_workspace_bytes(batch, w.R, t.C, noff) + 255) / 256 * 256;
-    return ia::launch_finalize(boxes, scores_t, kc, kr, batch, w.R, w.Rs, t.C, max_per_img, fin_ws,
-                               dets, labels, rows, num, s, gate);
+    return ia::launch_bboxes_nms(w, score_thr, iou_thr, max_per_img, lazy_candidates, dets, labels,
+                                 rows, num, s);
 }
 
 int ia_profile_stage_events(void *begin, void *end)
@@ -420,10 +382,9 @@ int ia_decode_stage(const ia_head_geom *g, const ia_level_ptrs *p, int batch, in
                     const float *img_hw, const float *scale_factor, int rescale, void *workspace,
                     size_t workspace_bytes, void *stream)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
+    ia::BboxWorkspace w;
     return decode_stage_impl(g, p, batch, dtype, img_hw, scale_factor, rescale, workspace,
-                             workspace_bytes, (hipStream_t)stream, w, t);
+                             workspace_bytes, (hipStream_t)stream, w);
 }
 
 int ia_get_bboxes(const ia_head_geom *g, const ia_level_ptrs *p, int batch, int dtype,
@@ -468,35 +429,24 @@ int ia_point_workspace_layout(const ia_point_head_geom *g, int batch, size_t off
 static int point_decode_impl(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                              const float *img_hw, const float *scale_factor, int rescale,
                              void *workspace, size_t workspace_bytes, hipStream_t s,
-                             ia::WsLayout &w, ia::LevelTable &t, int kind, float score_thr,
-                             int dtype)
+                             ia::BboxWorkspace &w, int kind, float score_thr, int dtype)
 {
     ia_head_geom hg;
     int rc = ia::point_head_geom(g, hg);
     if (rc) return rc;
-    if ((rc = ia::ws_layout(&hg, batch, w))) return rc;
-    if (!p || !workspace) return IA_E_ARG;
-    if (workspace_bytes < w.total) return IA_E_WORKSPACE;
-    if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
-    ia::make_level_table(&hg, t);
-    char *ws = static_cast<char *>(workspace);
-    return ia::launch_point_decode(g, t, *p, batch, img_hw, scale_factor, rescale,
-                                   reinterpret_cast<float *>(ws + w.off[0]),
-                                   reinterpret_cast<int32_t *>(ws + w.off[1]), ws + w.off[8],
-                                   reinterpret_cast<float *>(ws + w.off[2]),
-                                   reinterpret_cast<float *>(ws + w.off[3]),
-                                   reinterpret_cast<float *>(ws + w.off[6]), w.Rs, kind, score_thr,
-                                   dtype, s);
+    if ((rc = carve_checked(&hg, p, batch, workspace, workspace_bytes, w))) return rc;
+    return ia::launch_point_decode(g, w.t, *p, batch, img_hw, scale_factor, rescale, w.rowmax,
+                                   w.cand_idx, w.select, w.boxes, w.scores_t, w.best_score, w.Rs,
+                                   kind, score_thr, dtype, s);
 }
 
 int ia_point_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
                              int dtype, const float *img_hw, const float *scale_factor, int rescale,
                              void *workspace, size_t workspace_bytes, void *stream)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
+    ia::BboxWorkspace w;
     return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
-                             (hipStream_t)stream, w, t, 0, 0.0f, dtype);
+                             (hipStream_t)stream, w, 0, 0.0f, dtype);
 }
 
 int ia_point_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
@@ -512,10 +462,9 @@ int ia_point_ctr_decode_stage_dt(const ia_point_head_geom *g, const ia_level_ptr
                                  int rescale, float score_thr, void *workspace,
                                  size_t workspace_bytes, void *stream)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
+    ia::BboxWorkspace w;
     return point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace, workspace_bytes,
-                             (hipStream_t)stream, w, t, 1, score_thr, dtype);
+                             (hipStream_t)stream, w, 1, score_thr, dtype);
 }
 
 int ia_point_ctr_decode_stage(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,
@@ -535,36 +484,13 @@ static int point_get_bboxes_impl(const ia_point_head_geom *g, const ia_level_ptr
                                  size_t workspace_bytes, float *dets, int32_t *labels,
                                  int32_t *rows, int32_t *num, hipStream_t s)
 {
-    ia::WsLayout w;
-    ia::LevelTable t;
+    ia::BboxWorkspace w;
     if (!dets || !labels || !rows || !num) return IA_E_ARG;
     int rc = point_decode_impl(g, p, batch, img_hw, scale_factor, rescale, workspace,
-                               workspace_bytes, s, w, t, kind, score_thr, dtype);
+                               workspace_bytes, s, w, kind, score_thr, dtype);
     if (rc) return rc;
-    char *ws = static_cast<char *>(workspace);
-    float *boxes = reinterpret_cast<float *>(ws + w.off[2]);
-    float *scores_t = reinterpret_cast<float *>(ws + w.off[3]);
-    int32_t *kc = reinterpret_cast<int32_t *>(ws + w.off[4]);
-    int32_t *kr = reinterpret_cast<int32_t *>(ws + w.off[5]);
-    float *best = reinterpret_cast<float *>(ws + w.off[6]);
-    void *nms_ws = ws + w.off[7];
-    const int32_t *gate = nullptr;
-    if (candidates >= 0) {
-        int32_t *need_full = reinterpret_cast<int32_t *>(ws + w.off[10]);
-        if ((rc = ia::launch_lazy_nms(boxes, scores_t, batch, w.R, w.Rs, t.C, stage_thr, iou_thr,
-                                      max_per_img, candidates, ws + w.off[9], dets, labels, rows,
-                                      num, need_full, s)))
-            return rc;
-        gate = need_full;
-    }
-    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.R, w.Rs, t.C, stage_thr, iou_thr,
-                             nms_ws, kc, kr, s, gate)))
-        return rc;
-    size_t noff[3];
-    char *fin_ws = static_cast<char *>(nms_ws) +
-                   (ia::nms_workspace_bytes(batch, w.R, t.C, noff) + 255) / 256 * 256;
-    return ia::launch_finalize(boxes, scores_t, kc, kr, batch, w.R, w.Rs, t.C, max_per_img, fin_ws,
-                               dets, labels, rows, num, s, gate);
+    return ia::launch_bboxes_nms(w, stage_thr, iou_thr, max_per_img, candidates, dets, labels, rows,
+                                 num, s);
 }
 
 int ia_point_get_bboxes_dt(const ia_point_head_geom *g, const ia_level_ptrs *p, int batch,

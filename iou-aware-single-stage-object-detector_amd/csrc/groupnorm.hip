@@ -633,7 +633,7 @@ size_t ia_groupnorm_workspace_bytes_dt(const ia_wino_geom *g, int channels, int 
 {
     ia::GnArgs a;
     if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
-    return ((size_t)a.blk_off[IA_MAX_LEVELS] * groups * sizeof(double2) + 255) / 256 * 256;
+    return ia::align256((size_t)a.blk_off[IA_MAX_LEVELS] * groups * sizeof(double2));
 }
 
 int ia_groupnorm_stats_dt(const ia_wino_geom *g, const void *const *x, int dtype, int channels,
@@ -691,7 +691,7 @@ size_t ia_groupnorm_saved_bytes_dt(const ia_wino_geom *g, int channels, int grou
 {
     ia::GnArgs a;
     if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
-    return ((size_t)a.num_levels * a.batch * groups * sizeof(double2) + 255) / 256 * 256;
+    return ia::align256((size_t)a.num_levels * a.batch * groups * sizeof(double2));
 }
 
 size_t ia_groupnorm_saved_bytes(const ia_wino_geom *g, int channels, int groups)
@@ -739,7 +739,7 @@ size_t ia_groupnorm_bwd_workspace_bytes_dt(const ia_wino_geom *g, int channels, 
     ia::GnArgs a;
     if (ia::gn_args_dt(g, channels, groups, dtype, a)) return 0;
     const size_t rows = (size_t)a.blk_off[IA_MAX_LEVELS];
-    return (rows * ((size_t)groups + channels) * sizeof(double2) + 255) / 256 * 256;
+    return ia::align256(rows * ((size_t)groups + channels) * sizeof(double2));
 }
 
 size_t ia_groupnorm_bwd_workspace_bytes(const ia_wino_geom *g, int channels, int groups)

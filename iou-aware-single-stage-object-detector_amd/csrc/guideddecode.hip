@@ -247,8 +247,8 @@ int ia_guided_gather_decode(const ia_guided_geom *g, const ia_guided_level_ptrs 
                                     (hipStream_t)stream);
 }
 
-// the workspace of ia_get_bboxes for the A = 1 geometry, used slot by slot as that entry uses it
-// (its top-k slot through get_bboxes_select_offset)
+// the workspace of ia_get_bboxes for the A = 1 geometry (carve_bboxes), used piece by piece as that
+// entry uses it
 size_t ia_guided_get_bboxes_workspace_bytes(const ia_guided_geom *g, int batch)
 {
     if (!g) return 0;
@@ -273,35 +273,16 @@ int ia_guided_get_bboxes(const ia_guided_geom *g, const ia_guided_level_ptrs *p,
     if (!(score_thr >= 0.0f)) return IA_E_ARG;      // the zero rows of filtered-out candidates must not pass
     if (!workspace || !dets || !labels || !rows || !num || !img_hw) return IA_E_ARG;
     if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
-    size_t off[8];
-    if ((rc = ia_get_bboxes_workspace_layout(&g->head, batch, off))) return rc;
-    const size_t need = ia_guided_get_bboxes_workspace_bytes(g, batch);
-    if (need == 0) return IA_E_LIMIT_BOXES;
-    if (workspace_bytes < need) return IA_E_WORKSPACE;
+    ia::BboxWorkspace w;
+    if ((rc = ia::carve_bboxes(&g->head, batch, workspace, w))) return rc;
+    if (workspace_bytes < w.bytes) return IA_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    float *rowmax = reinterpret_cast<float *>(ws + off[0]);
-    int32_t *cand = reinterpret_cast<int32_t *>(ws + off[1]);
-    float *boxes = reinterpret_cast<float *>(ws + off[2]);
-    float *scores_t = reinterpret_cast<float *>(ws + off[3]);
-    int32_t *kc = reinterpret_cast<int32_t *>(ws + off[4]);
-    int32_t *kr = reinterpret_cast<int32_t *>(ws + off[5]);
-    float *best = reinterpret_cast<float *>(ws + off[6]);
-    void *nms_ws = ws + off[7];
-    size_t sel_off;
-    if ((rc = ia::get_bboxes_select_offset(&g->head, batch, &sel_off))) return rc;
-    void *sel_ws = ws + sel_off;
-    if ((rc = ia::launch_guided_rowmax(a, rowmax, s))) return rc;
-    if ((rc = ia::launch_select(t, rowmax, batch, cand, sel_ws, s, false))) return rc;
-    if ((rc = ia::launch_guided_gather(a, cand, img_hw, scale_factor, rescale, boxes, scores_t, best, s)))
+    if ((rc = ia::launch_guided_rowmax(a, w.rowmax, s))) return rc;
+    if ((rc = ia::launch_select(t, w.rowmax, batch, w.cand_idx, w.select, s, false))) return rc;
+    if ((rc = ia::launch_guided_gather(a, w.cand_idx, img_hw, scale_factor, rescale, w.boxes, w.scores_t,
+                                       w.best_score, s)))
         return rc;
-    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, a.R, a.Rs, t.C, score_thr, iou_thr, nms_ws, kc,
-                             kr, s)))
-        return rc;
-    size_t noff[3];
-    char *fin_ws = static_cast<char *>(nms_ws) + (ia::nms_workspace_bytes(batch, a.R, t.C, noff) + 255) / 256 * 256;
-    return ia::launch_finalize(boxes, scores_t, kc, kr, batch, a.R, a.Rs, t.C, max_per_img, fin_ws, dets,
-                               labels, rows, num, s);
+    return ia::launch_bboxes_nms(w, score_thr, iou_thr, max_per_img, -1, dets, labels, rows, num, s);
 }
 
 }  // extern "C"

@@ -1006,8 +1006,8 @@ static size_t slot_bytes(int L, bool bal_cls)
 }
 static HLWorkspace carve(const HLLevels &lv, const void *workspace, bool bal_cls)
 {
-    const size_t slots = ((slot_bytes(lv.L, bal_cls) + 255) / 256) * 256;
-    const size_t pk = (((size_t)lv.pack_off[lv.L] * 4 + 255) / 256) * 256;
+    const size_t slots = align256(slot_bytes(lv.L, bal_cls));
+    const size_t pk = align256((size_t)lv.pack_off[lv.L] * 4);
     char *w = static_cast<char *>(const_cast<void *>(workspace));
     HLWorkspace r;
     r.sums = reinterpret_cast<double *>(w);

@@ -21,6 +21,26 @@ struct LevelTable {
 
 struct BaseAnchors { float v[IA_MAX_LEVELS][IA_MAX_ANCHORS][4]; };
 
+// every piece of every caller-owned workspace starts on a 256-byte boundary
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// Walks a workspace piece by piece, in the order of the take() calls.  The carve function of a
+// layout is the one place that knows its order and sizes: with a null base it answers the
+// *_workspace_bytes / *_workspace_layout queries (offsets and `bytes` only, every pointer stays
+// null); with the caller's pointer it hands out the typed pieces.
+struct Carver {
+    void *base;
+    size_t bytes = 0;
+    explicit Carver(const void *b) : base(const_cast<void *>(b)) {}
+    template <class T> size_t take(T *&piece, size_t nbytes)       // -> the piece's byte offset
+    {
+        const size_t at = bytes;
+        piece = base ? static_cast<T *>(static_cast<void *>(static_cast<char *>(base) + at)) : nullptr;
+        bytes = align256(at + nbytes);
+        return at;
+    }
+};
+
 inline int make_level_table(const ia_head_geom *g, LevelTable &t)
 {
     if (!g) return IA_E_ARG;
@@ -142,12 +162,19 @@ int launch_gather(const LevelTable &t, const BaseAnchors &ba, const float *means
                   const float *img_hw, const float *scale_factor, int rescale, float *boxes,
                   float *scores_t, float *best_score, int Rs, hipStream_t s);
 int nms_adj_words(int R);            // 64-bit words per adjacency row (padded)
-size_t nms_workspace_bytes(int batch, int R, int C, size_t off[3]);
-int launch_nms(const float *boxes, const float *scores_t, const float *best_score, int batch,
-               int R, int Rs, int C, float score_thr, float iou_thr, void *workspace,
-               int32_t *keep_count, int32_t *keep_rows, hipStream_t s,
-               const int32_t *gate = nullptr);       // gate (B): images with gate[b] == 0 are skipped
+// The NMS stages behind every decode stage (nms.hip), on one workspace "NMS stage | final keys"
+// (the final keys start at the next 256-byte boundary; the end is NOT rounded up: this is what
+// ia_multiclass_nms_workspace_bytes answers.  Rs is R padded to 64.)
+size_t nms_tail_workspace_bytes(int batch, int R, int C);
+// lazy (optional): the lazy walk first (lazynms.hip); the complete NMS and the final top-k then run
+// only for the images it could not finish (need_full[b] != 0)
+struct NmsLazy { void *workspace; int32_t *need_full; int candidates; };
+int launch_nms_tail(const float *boxes, const float *scores_t, const float *best_score, int batch,
+                    int R, int Rs, int C, float score_thr, float iou_thr, int max_per_img,
+                    void *workspace, const NmsLazy *lazy, int32_t *keep_count, int32_t *keep_rows,
+                    float *dets, int32_t *labels, int32_t *rows, int32_t *num, hipStream_t s);
 size_t finalize_workspace_bytes(int batch, int Rs, int C);
+// gate (B): images with gate[b] == 0 are skipped
 int launch_finalize(const float *boxes, const float *scores_t, const int32_t *keep_count,
                     const int32_t *keep_rows, int batch, int R, int Rs, int C, int max_per_img,
                     void *workspace, float *dets, int32_t *labels, int32_t *rows, int32_t *num,
@@ -181,9 +208,34 @@ int launch_point_decode(const ia_point_head_geom *pg, const LevelTable &t, const
                         float *scores_t, float *best_score, int Rs, int kind, float score_thr,
                         int dtype, hipStream_t s);
 
-// byte offset of the top-k workspace inside the ia_get_bboxes workspace of (g, batch) (capi.hip): for
-// the decode stages of other heads that run on that workspace (guideddecode.hip)
-int get_bboxes_select_offset(const ia_head_geom *g, int batch, size_t *offset);
+// The whole-path workspace of the anchor, point and guided heads (ia_get_bboxes_workspace_bytes),
+// in this order; carve_bboxes (capi.hip) is the one place that knows the sizes.  select: zeroed
+// once by its owner, stateful between calls (select.hip).
+struct BboxWorkspace {
+    float *rowmax;            // (B, N)
+    int32_t *cand_idx;        // (B, R)
+    float *boxes;             // (B, R, 4)
+    float *scores_t;          // (B, C, Rs)
+    int32_t *keep_count;      // (B, C)
+    int32_t *keep_rows;       // (B, C, Rs)
+    float *best_score;        // (B, R)
+    void *nms;                // NMS stage | final keys (launch_nms_tail)
+    void *select;             // top-k parts
+    void *lazy;               // lazy NMS
+    int32_t *need_full;       // (B)
+    size_t off[8];            // byte offsets of rowmax .. nms: what the *_workspace_layout entries hand out
+    size_t select_off;
+    size_t bytes;
+    int32_t batch, N, R, Rs;
+    LevelTable t;             // of the geometry it was carved for
+};
+// checks geometry and batch (R above IA_MAX_CANDIDATES: IA_E_LIMIT_BOXES); base may be null
+int carve_bboxes(const ia_head_geom *g, int batch, void *base, BboxWorkspace &w);
+// the NMS stages on a carved workspace whose decode stage has been enqueued; candidates < 0: the
+// complete NMS for every image, >= 0: lazy NMS first (0 = default candidate count)
+int launch_bboxes_nms(const BboxWorkspace &w, float score_thr, float iou_thr, int max_per_img,
+                      int candidates, float *dets, int32_t *labels, int32_t *rows, int32_t *num,
+                      hipStream_t s);
 
 // the IoU maps the score kind needs: every level's iou pointer set (IoU-aware kinds) or every one
 // NULL (IA_CLS_*_NOIOU)

@@ -230,13 +230,11 @@ __global__ void __launch_bounds__(kLazyThreads) k_lazy_greedy(LazyArgs a)
     }
 }
 
-static size_t lazy_align(size_t v) { return (v + 255) / 256 * 256; }
-
 size_t lazy_workspace_bytes(int batch, int Rs, int C)
 {
-    return lazy_align((size_t)batch * C * Rs * sizeof(uint64_t)) +
-           lazy_align((size_t)batch * kLazyParts * kLazyMax * sizeof(uint64_t)) +
-           lazy_align((size_t)batch * sizeof(int32_t));
+    return align256((size_t)batch * C * Rs * sizeof(uint64_t)) +
+           align256((size_t)batch * kLazyParts * kLazyMax * sizeof(uint64_t)) +
+           align256((size_t)batch * sizeof(int32_t));
 }
 
 int launch_lazy_nms(const float *boxes, const float *scores_t, int batch, int R, int Rs, int C,
@@ -262,9 +260,9 @@ int launch_lazy_nms(const float *boxes, const float *scores_t, int batch, int R,
     a.gate = nullptr;
     char *ws = static_cast<char *>(workspace);
     a.flat = reinterpret_cast<uint64_t *>(ws);
-    ws += lazy_align((size_t)batch * C * Rs * sizeof(uint64_t));
+    ws += align256((size_t)batch * C * Rs * sizeof(uint64_t));
     a.part_keys = reinterpret_cast<uint64_t *>(ws);
-    ws += lazy_align((size_t)batch * kLazyParts * kLazyMax * sizeof(uint64_t));
+    ws += align256((size_t)batch * kLazyParts * kLazyMax * sizeof(uint64_t));
     a.count = reinterpret_cast<int32_t *>(ws);
     a.boxes = boxes; a.scores_t = scores_t; a.dets = dets; a.labels = labels; a.rows = rows;
     a.num = num; a.need_full = need_full; a.thr = make_thr(iou_thr); a.score_thr = score_thr;

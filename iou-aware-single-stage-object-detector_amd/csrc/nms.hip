@@ -329,35 +329,35 @@ static uint32_t pow2_at_least(uint32_t v)
 int nms_adj_words(int R) { return ((R + 63) / 64 + kAdjGroup - 1) / kAdjGroup * kAdjGroup; }
 
 // workspace of the NMS stage: adjacency bit matrix | sorted rows (uint16) | participant counts
-size_t nms_workspace_bytes(int batch, int R, int C, size_t off[3])
+struct NmsWorkspace { uint64_t *adj; uint16_t *sorted_rows; int32_t *n_in; size_t bytes; };
+
+static NmsWorkspace carve_nms(int batch, int R, int C, void *base)
 {
     const size_t Rs = (size_t)(R + 63) / 64 * 64;
-    size_t o = 0;
-    off[0] = o; o += ((size_t)batch * R * nms_adj_words(R) * sizeof(uint64_t) + 255) / 256 * 256;
-    off[1] = o; o += ((size_t)batch * C * Rs * sizeof(uint16_t) + 255) / 256 * 256;
-    off[2] = o; o += ((size_t)batch * C * sizeof(int32_t) + 255) / 256 * 256;
-    return o;
+    NmsWorkspace w;
+    Carver c(base);
+    c.take(w.adj, (size_t)batch * R * nms_adj_words(R) * sizeof(uint64_t));
+    c.take(w.sorted_rows, (size_t)batch * C * Rs * sizeof(uint16_t));
+    c.take(w.n_in, (size_t)batch * C * sizeof(int32_t));
+    w.bytes = c.bytes;
+    return w;
 }
 
-int launch_nms(const float *boxes, const float *scores_t, const float *best_score, int batch,
-               int R, int Rs, int C, float score_thr, float iou_thr, void *workspace,
-               int32_t *keep_count, int32_t *keep_rows, hipStream_t s, const int32_t *gate)
+// gate (B): images with gate[b] == 0 are skipped
+static int launch_nms(const float *boxes, const float *scores_t, const float *best_score, int batch,
+                      int R, int Rs, int C, float score_thr, float iou_thr, void *workspace,
+                      int32_t *keep_count, int32_t *keep_rows, hipStream_t s, const int32_t *gate)
 {
     if (R > IA_MAX_CANDIDATES) return IA_E_LIMIT_BOXES;
     if (batch < 1 || R < 1 || C < 1 || Rs < R) return IA_E_ARG;
     if (!boxes || !scores_t || !workspace || !keep_count || !keep_rows) return IA_E_ARG;
-    size_t off[3];
-    nms_workspace_bytes(batch, R, C, off);
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *adj = reinterpret_cast<uint64_t *>(ws + off[0]);
-    uint16_t *sorted_rows = reinterpret_cast<uint16_t *>(ws + off[1]);
-    int32_t *n_in = reinterpret_cast<int32_t *>(ws + off[2]);
+    const NmsWorkspace w = carve_nms(batch, R, C, workspace);
     const int W = nms_adj_words(R);
-    int rc = launch_adj(boxes, 4, best_score, batch, R, W, make_thr(iou_thr), score_thr, adj, s, gate);
+    int rc = launch_adj(boxes, 4, best_score, batch, R, W, make_thr(iou_thr), score_thr, w.adj, s, gate);
     if (rc) return rc;
     SortArgs sa;
     sa.gate = gate;
-    sa.scores_t = scores_t; sa.sorted_rows = sorted_rows; sa.n_in = n_in; sa.score_thr = score_thr;
+    sa.scores_t = scores_t; sa.sorted_rows = w.sorted_rows; sa.n_in = w.n_in; sa.score_thr = score_thr;
     sa.R = R; sa.Rs = Rs; sa.C = C;
     size_t lds = sizeof(uint64_t) * (size_t)pow2_at_least((uint32_t)R);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_class_sort),
@@ -367,7 +367,7 @@ int launch_nms(const float *boxes, const float *scores_t, const float *best_scor
     if ((rc = hip_status(hipGetLastError()))) return rc;
     NmsArgs a;
     a.gate = gate;
-    a.sorted_rows = sorted_rows; a.n_in = n_in; a.adj = adj; a.keep_count = keep_count;
+    a.sorted_rows = w.sorted_rows; a.n_in = w.n_in; a.adj = w.adj; a.keep_count = keep_count;
     a.keep_rows = keep_rows; a.R = R; a.Rs = Rs; a.C = C; a.W = W; a.B = batch;
     a.Bpad = (batch + 7) / 8 * 8;
     hipLaunchKernelGGL(k_nms_resolve, dim3((unsigned)(C * a.Bpad)), dim3(kResThreads), 0, s, a);
@@ -394,9 +394,7 @@ __global__ void __launch_bounds__(kResThreads) k_nms_single(NmsSingleArgs a)
 
 size_t nms_single_workspace_bytes(int n)
 {
-    if (n < 1) return 0;
-    size_t off[3];
-    return nms_workspace_bytes(1, n, 1, off);
+    return n < 1 ? 0 : carve_nms(1, n, 1, nullptr).bytes;
 }
 
 int launch_nms_single(const float *dets, int n, float iou_thr, int32_t *keep, int32_t *count,
@@ -406,17 +404,13 @@ int launch_nms_single(const float *dets, int n, float iou_thr, int32_t *keep, in
     if (n < 0 || !count) return IA_E_ARG;
     if (n == 0) return hip_status(hipMemsetAsync(count, 0, sizeof(int32_t), s));
     if (!dets || !keep || !workspace) return IA_E_ARG;
-    size_t off[3];
-    if (workspace_bytes < nms_workspace_bytes(1, n, 1, off)) return IA_E_WORKSPACE;
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *adj = reinterpret_cast<uint64_t *>(ws + off[0]);
-    uint16_t *sorted_rows = reinterpret_cast<uint16_t *>(ws + off[1]);
-    int32_t *n_in = reinterpret_cast<int32_t *>(ws + off[2]);
+    const NmsWorkspace w = carve_nms(1, n, 1, workspace);
+    if (workspace_bytes < w.bytes) return IA_E_WORKSPACE;
     const int W = nms_adj_words(n);
-    int rc = launch_adj(dets, 5, nullptr, 1, n, W, make_thr(iou_thr), 0.0f, adj, s);
+    int rc = launch_adj(dets, 5, nullptr, 1, n, W, make_thr(iou_thr), 0.0f, w.adj, s);
     if (rc) return rc;
     SortSingleArgs sa;
-    sa.dets = dets; sa.sorted_rows = sorted_rows; sa.n_in = n_in; sa.n = n;
+    sa.dets = dets; sa.sorted_rows = w.sorted_rows; sa.n_in = w.n_in; sa.n = n;
     size_t lds = sizeof(uint64_t) * (size_t)pow2_at_least((uint32_t)n);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dets_sort),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -424,7 +418,7 @@ int launch_nms_single(const float *dets, int n, float iou_thr, int32_t *keep, in
     hipLaunchKernelGGL(k_dets_sort, dim3(1), dim3(kSortThreads), lds, s, sa);
     if ((rc = hip_status(hipGetLastError()))) return rc;
     NmsSingleArgs a;
-    a.sorted_rows = sorted_rows; a.n_in = n_in; a.adj = adj; a.keep = keep; a.count = count;
+    a.sorted_rows = w.sorted_rows; a.n_in = w.n_in; a.adj = w.adj; a.keep = keep; a.count = count;
     a.n = n; a.W = W;
     hipLaunchKernelGGL(k_nms_single, dim3(1), dim3(kResThreads), 0, s, a);
     return hip_status(hipGetLastError());
@@ -616,6 +610,35 @@ int launch_finalize(const float *boxes, const float *scores_t, const int32_t *ke
     if ((rc = hip_status(hipGetLastError()))) return rc;
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)batch), dim3(kFinalThreads), 0, s, a);
     return hip_status(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ the stages in sequence
+size_t nms_tail_workspace_bytes(int batch, int R, int C)
+{
+    return align256(carve_nms(batch, R, C, nullptr).bytes) + finalize_workspace_bytes(batch, (R + 63) / 64 * 64, C);
+}
+
+// each stage's own checks answer in the order of the stages
+int launch_nms_tail(const float *boxes, const float *scores_t, const float *best_score, int batch,
+                    int R, int Rs, int C, float score_thr, float iou_thr, int max_per_img,
+                    void *workspace, const NmsLazy *lazy, int32_t *keep_count, int32_t *keep_rows,
+                    float *dets, int32_t *labels, int32_t *rows, int32_t *num, hipStream_t s)
+{
+    int rc;
+    const int32_t *gate = nullptr;
+    if (lazy) {
+        if ((rc = launch_lazy_nms(boxes, scores_t, batch, R, Rs, C, score_thr, iou_thr, max_per_img,
+                                  lazy->candidates, lazy->workspace, dets, labels, rows, num,
+                                  lazy->need_full, s)))
+            return rc;
+        gate = lazy->need_full;
+    }
+    if ((rc = launch_nms(boxes, scores_t, best_score, batch, R, Rs, C, score_thr, iou_thr, workspace,
+                         keep_count, keep_rows, s, gate)))
+        return rc;
+    char *fin_ws = static_cast<char *>(workspace) + align256(carve_nms(batch, R, C, nullptr).bytes);
+    return launch_finalize(boxes, scores_t, keep_count, keep_rows, batch, R, Rs, C, max_per_img, fin_ws,
+                           dets, labels, rows, num, s, gate);
 }
 
 }  // namespace ia

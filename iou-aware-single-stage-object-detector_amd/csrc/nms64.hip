@@ -117,21 +117,20 @@ struct Nms64Layout { size_t keys_in, keys_out, vals_in, vals_out, adj, flags, so
 
 static int nms64_layout(int n, Nms64Layout &w)
 {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t N = (size_t)n, words = (N + 63) / 64;
     size_t o = 0;
-    w.keys_in = o; o = up(o + N * 8);
-    w.keys_out = o; o = up(o + N * 8);
-    w.vals_in = o; o = up(o + N * 4);
-    w.vals_out = o; o = up(o + N * 4);
-    w.adj = o; o = up(o + N * words * 8);
-    w.flags = o; o = up(o + N * 4);
+    w.keys_in = o; o = align256(o + N * 8);
+    w.keys_out = o; o = align256(o + N * 8);
+    w.vals_in = o; o = align256(o + N * 4);
+    w.vals_out = o; o = align256(o + N * 4);
+    w.adj = o; o = align256(o + N * words * 8);
+    w.flags = o; o = align256(o + N * 4);
     size_t need = 0;
     hipError_t e = rocprim::radix_sort_pairs_desc(nullptr, need, (uint64_t *)nullptr, (uint64_t *)nullptr,
                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, N, 0, 64, (hipStream_t)0);
     if (e != hipSuccess) return (int)e;
     w.sort_bytes = need;
-    w.sort_tmp = o; o = up(o + need);
+    w.sort_tmp = o; o = align256(o + need);
     w.total = o;
     return 0;
 }

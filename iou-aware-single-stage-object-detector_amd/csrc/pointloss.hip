@@ -509,9 +509,9 @@ struct PtWorkspace { double *sums; float *fgin, *fres; int32_t *lab32; float *w3
 
 static PtWorkspace carve_point(const HLLevels &lv, void *workspace)
 {
-    const size_t slots = ((sizeof(double) * (lv.L + kPtSums) * IA_LOSS_SLOTS + 255) / 256) * 256;
-    const size_t fint = ((sizeof(float) * 2 * (3 * lv.L + 4) + 255) / 256) * 256;
-    const size_t pk = ((packed_pad(lv) * 4 + 255) / 256) * 256;
+    const size_t slots = align256(sizeof(double) * (lv.L + kPtSums) * IA_LOSS_SLOTS);
+    const size_t fint = align256(sizeof(float) * 2 * (3 * lv.L + 4));
+    const size_t pk = align256(packed_pad(lv) * 4);
     char *w = static_cast<char *>(workspace);
     PtWorkspace r;
     r.sums = reinterpret_cast<double *>(w);
@@ -570,9 +570,9 @@ struct PtNhwcWorkspace { double *sums; float *fgin, *fres; double *scale_sums; s
 
 static PtNhwcWorkspace carve_point_nhwc(int L, void *workspace)
 {
-    const size_t slots = ((sizeof(double) * (L + kPtSums) * IA_LOSS_SLOTS + 255) / 256) * 256;
-    const size_t fint = ((sizeof(float) * 2 * (3 * L + 4) + 255) / 256) * 256;
-    const size_t ss = ((sizeof(double) * L * IA_LOSS_SLOTS + 255) / 256) * 256;
+    const size_t slots = align256(sizeof(double) * (L + kPtSums) * IA_LOSS_SLOTS);
+    const size_t fint = align256(sizeof(float) * 2 * (3 * L + 4));
+    const size_t ss = align256(sizeof(double) * L * IA_LOSS_SLOTS);
     char *w = static_cast<char *>(workspace);
     PtNhwcWorkspace r;
     r.sums = reinterpret_cast<double *>(w);

@@ -794,18 +794,17 @@ struct SelLayout { size_t seg_v, chunk_count, groupmax, cand, total; };
 
 static SelLayout layout(const LevelTable &t, const SelPlan &p, int batch)
 {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     SelLayout w;
     const size_t B = (size_t)batch;
     size_t o = 0;
-    w.seg_v = o; o = up(o + B * (size_t)t.num_levels * sizeof(uint64_t));
+    w.seg_v = o; o = align256(o + B * (size_t)t.num_levels * sizeof(uint64_t));
     // (+2: status words of the fused launch's bounded spin: id of the last call that timed out,
     // number of calls that fell back)
-    w.chunk_count = o; o = up(o + (B * (size_t)p.chunk_off[IA_MAX_LEVELS] + 2) * sizeof(uint32_t));
-    w.groupmax = o; o = up(o + (size_t)p.goff[IA_MAX_LEVELS] * sizeof(uint32_t));
+    w.chunk_count = o; o = align256(o + (B * (size_t)p.chunk_off[IA_MAX_LEVELS] + 2) * sizeof(uint32_t));
+    w.groupmax = o; o = align256(o + (size_t)p.goff[IA_MAX_LEVELS] * sizeof(uint32_t));
     w.cand = o;
     if (p.chunk_off[IA_MAX_LEVELS] > 0)
-        o = up(o + B * (size_t)t.anchor_off[t.num_levels] * sizeof(uint64_t));
+        o = align256(o + B * (size_t)t.anchor_off[t.num_levels] * sizeof(uint64_t));
     w.total = o > 0 ? o : 256;
     return w;
 }

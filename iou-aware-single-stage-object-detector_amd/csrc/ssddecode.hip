@@ -230,33 +230,43 @@ __global__ void __launch_bounds__(256) k_ssd_map_rows(const int32_t *kept_rows, 
     if (over && threadIdx.x == 0) num[b] = 0;
 }
 
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+// workspace of ia_ssd_get_bboxes, in this order; off: the byte offsets of the first eight pieces
+// (ia_ssd_workspace_layout)
+struct SsdWorkspace {
+    float *row_score;         // (B, R)
+    int32_t *kept_rows;       // (B, IA_MAX_CANDIDATES)
+    int32_t *kept_count;      // (B)
+    float *boxes;             // (B, Rk, 4)
+    float *scores_t;          // (B, C, Rs)
+    float *best_score;        // (B, Rk)
+    int32_t *keep_count;      // (B, C)
+    int32_t *keep_rows;       // (B, C, Rs)
+    void *compact;            // compaction parts
+    void *nms;                // NMS stage | final keys (launch_nms_tail)
+    size_t off[8];
+    size_t bytes;
+    int32_t R, Rk, Rs;
+};
 
-// workspace of ia_ssd_get_bboxes: 0 row scores (B, R) | 1 kept_rows (B, IA_MAX_CANDIDATES) | 2 kept_count (B)
-// | 3 boxes (B, Rk, 4) | 4 scores_t (B, C, Rs) | 5 best_score (B, Rk) | 6 keep_count (B, C) | 7 keep_rows
-// (B, C, Rs) | 8 compaction parts | 9 NMS stage + final keys
-struct SsdLayout { size_t off[10]; size_t total; int32_t R, Rk, Rs; };
-
-static int ssd_layout(const SsdTable &t, int batch, SsdLayout &w)
+static int carve_ssd(const SsdTable &t, int batch, void *base, SsdWorkspace &w)
 {
     if (batch < 1 || batch > 65535) return IA_E_ARG;
     w.R = t.row_off[t.num_levels];
     w.Rk = w.R < IA_MAX_CANDIDATES ? w.R : IA_MAX_CANDIDATES;
     w.Rs = (w.Rk + 63) / 64 * 64;
     const size_t B = (size_t)batch, C = (size_t)t.C;
-    size_t o = 0, noff[3];
-    w.off[0] = o; o = align256(o + B * w.R * sizeof(float));
-    w.off[1] = o; o = align256(o + B * IA_MAX_CANDIDATES * sizeof(int32_t));
-    w.off[2] = o; o = align256(o + B * sizeof(int32_t));
-    w.off[3] = o; o = align256(o + B * w.Rk * 4 * sizeof(float));
-    w.off[4] = o; o = align256(o + B * C * w.Rs * sizeof(float));
-    w.off[5] = o; o = align256(o + B * w.Rk * sizeof(float));
-    w.off[6] = o; o = align256(o + B * C * sizeof(int32_t));
-    w.off[7] = o; o = align256(o + B * C * w.Rs * sizeof(int32_t));
-    w.off[8] = o; o = align256(o + ssd_compact_bytes(batch, w.R));
-    w.off[9] = o; o = align256(o + nms_workspace_bytes(batch, w.Rk, t.C, noff));
-    o = align256(o + finalize_workspace_bytes(batch, w.Rs, t.C));
-    w.total = o;
+    Carver c(base);
+    w.off[0] = c.take(w.row_score, B * w.R * sizeof(float));
+    w.off[1] = c.take(w.kept_rows, B * IA_MAX_CANDIDATES * sizeof(int32_t));
+    w.off[2] = c.take(w.kept_count, B * sizeof(int32_t));
+    w.off[3] = c.take(w.boxes, B * w.Rk * 4 * sizeof(float));
+    w.off[4] = c.take(w.scores_t, B * C * w.Rs * sizeof(float));
+    w.off[5] = c.take(w.best_score, B * w.Rk * sizeof(float));
+    w.off[6] = c.take(w.keep_count, B * C * sizeof(int32_t));
+    w.off[7] = c.take(w.keep_rows, B * C * w.Rs * sizeof(int32_t));
+    c.take(w.compact, ssd_compact_bytes(batch, w.R));
+    c.take(w.nms, nms_tail_workspace_bytes(batch, w.Rk, t.C));
+    w.bytes = c.bytes;
     return 0;
 }
 
@@ -316,19 +326,19 @@ int ia_ssd_gather_decode(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int b
 size_t ia_ssd_get_bboxes_workspace_bytes(const ia_ssd_geom *g, int batch)
 {
     ia::SsdTable t;
-    ia::SsdLayout w;
-    if (ia::make_ssd_table(g, nullptr, t) || ia::ssd_layout(t, batch, w)) return 0;
-    return w.total;
+    ia::SsdWorkspace w;
+    if (ia::make_ssd_table(g, nullptr, t) || ia::carve_ssd(t, batch, nullptr, w)) return 0;
+    return w.bytes;
 }
 
 int ia_ssd_workspace_layout(const ia_ssd_geom *g, int batch, size_t offsets[8])
 {
     ia::SsdTable t;
-    ia::SsdLayout w;
+    ia::SsdWorkspace w;
     if (!offsets) return IA_E_ARG;
     int rc = ia::make_ssd_table(g, nullptr, t);
     if (rc) return rc;
-    if ((rc = ia::ssd_layout(t, batch, w))) return rc;
+    if ((rc = ia::carve_ssd(t, batch, nullptr, w))) return rc;
     for (int i = 0; i < 8; ++i) offsets[i] = w.off[i];
     return 0;
 }
@@ -339,7 +349,7 @@ int ia_ssd_get_bboxes(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batc
                       int32_t *num, int32_t *overflow, void *stream)
 {
     ia::SsdTable t;
-    ia::SsdLayout w;
+    ia::SsdWorkspace w;
     if (!p || dtype != IA_F32) return IA_E_ARG;
     int rc = ia::make_ssd_table(g, p, t);
     if (rc) return rc;
@@ -348,34 +358,20 @@ int ia_ssd_get_bboxes(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batc
     if (((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
     if (max_per_img > IA_MAX_PER_IMG) return IA_E_LIMIT_PER_IMG;
     if (max_per_img < 1) return IA_E_ARG;
-    if ((rc = ia::ssd_layout(t, batch, w))) return rc;
-    if (workspace_bytes < w.total) return IA_E_WORKSPACE;
+    if ((rc = ia::carve_ssd(t, batch, workspace, w))) return rc;
+    if (workspace_bytes < w.bytes) return IA_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    float *best_all = reinterpret_cast<float *>(ws + w.off[0]);
-    int32_t *kept_rows = reinterpret_cast<int32_t *>(ws + w.off[1]);
-    int32_t *kept_count = reinterpret_cast<int32_t *>(ws + w.off[2]);
-    float *boxes = reinterpret_cast<float *>(ws + w.off[3]);
-    float *scores_t = reinterpret_cast<float *>(ws + w.off[4]);
-    float *best = reinterpret_cast<float *>(ws + w.off[5]);
-    int32_t *kc = reinterpret_cast<int32_t *>(ws + w.off[6]);
-    int32_t *kr = reinterpret_cast<int32_t *>(ws + w.off[7]);
-    void *compact_ws = ws + w.off[8];
-    void *nms_ws = ws + w.off[9];
-    if ((rc = ia::launch_ssd_rowscore(t, batch, best_all, s))) return rc;
-    if ((rc = ia::launch_ssd_compact(best_all, batch, w.R, score_thr, kept_rows, kept_count, overflow, compact_ws, s)))
+    if ((rc = ia::launch_ssd_rowscore(t, batch, w.row_score, s))) return rc;
+    if ((rc = ia::launch_ssd_compact(w.row_score, batch, w.R, score_thr, w.kept_rows, w.kept_count, overflow,
+                                     w.compact, s)))
         return rc;
-    if ((rc = ia::launch_ssd_gather(g, t, batch, kept_rows, IA_MAX_CANDIDATES, kept_count, w.Rk, img_hw, scale_factor,
-                                    rescale, boxes, scores_t, best, s)))
+    if ((rc = ia::launch_ssd_gather(g, t, batch, w.kept_rows, IA_MAX_CANDIDATES, w.kept_count, w.Rk, img_hw,
+                                    scale_factor, rescale, w.boxes, w.scores_t, w.best_score, s)))
         return rc;
-    if ((rc = ia::launch_nms(boxes, scores_t, best, batch, w.Rk, w.Rs, t.C, score_thr, iou_thr, nms_ws, kc, kr, s)))
+    if ((rc = ia::launch_nms_tail(w.boxes, w.scores_t, w.best_score, batch, w.Rk, w.Rs, t.C, score_thr, iou_thr,
+                                  max_per_img, w.nms, nullptr, w.keep_count, w.keep_rows, dets, labels, rows, num, s)))
         return rc;
-    size_t noff[3];
-    char *fin_ws = static_cast<char *>(nms_ws) + ia::align256(ia::nms_workspace_bytes(batch, w.Rk, t.C, noff));
-    if ((rc = ia::launch_finalize(boxes, scores_t, kc, kr, batch, w.Rk, w.Rs, t.C, max_per_img, fin_ws, dets, labels,
-                                  rows, num, s)))
-        return rc;
-    hipLaunchKernelGGL(ia::k_ssd_map_rows, dim3((unsigned)batch), dim3(256), 0, s, kept_rows, overflow, max_per_img,
+    hipLaunchKernelGGL(ia::k_ssd_map_rows, dim3((unsigned)batch), dim3(256), 0, s, w.kept_rows, overflow, max_per_img,
                        rows, num);
     return ia::hip_status(hipGetLastError());
 }

@@ -358,12 +358,18 @@ static int launch_ssdloss_bwd(const SsdTable &t, int batch, const SsdTargets &tg
 }
 
 // ------------------------------------------------------------------ workspace of the node
-// 0 ce (B, R) f32 | 1 lse (B, R) f32 | 2 sel (B, R) u8 | 3 counts (B, 2) i32 | 4 box partials (B, nparts) f64
-struct SsdLossLayout { size_t off[5]; size_t total; int32_t R, nparts; };
+// in this order; off: the pieces' byte offsets (ia_ssd_head_loss_workspace_layout)
+struct SsdLossWorkspace {
+    float *ce, *lse;          // (B, R) each
+    uint8_t *sel;             // (B, R)
+    int32_t *counts;          // (B, 2)
+    double *parts;            // box partials (B, nparts)
+    size_t off[5];
+    size_t bytes;
+    int32_t R, nparts;
+};
 
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-static int ssdloss_layout(const SsdTable &t, int batch, SsdLossLayout &w)
+static int carve_ssdloss(const SsdTable &t, int batch, const void *base, SsdLossWorkspace &w)
 {
     int rc;
     if ((rc = check_rows_batch(t, batch))) return rc;
@@ -372,13 +378,13 @@ static int ssdloss_layout(const SsdTable &t, int batch, SsdLossLayout &w)
     if (np > 2147483647LL) return IA_E_ARG;
     w.nparts = (int32_t)np;
     const size_t B = (size_t)batch;
-    size_t o = 0;
-    w.off[0] = o; o = up256(o + B * w.R * sizeof(float));
-    w.off[1] = o; o = up256(o + B * w.R * sizeof(float));
-    w.off[2] = o; o = up256(o + B * w.R);
-    w.off[3] = o; o = up256(o + B * 2 * sizeof(int32_t));
-    w.off[4] = o; o = up256(o + B * w.nparts * sizeof(double));
-    w.total = o;
+    Carver c(base);
+    w.off[0] = c.take(w.ce, B * w.R * sizeof(float));
+    w.off[1] = c.take(w.lse, B * w.R * sizeof(float));
+    w.off[2] = c.take(w.sel, B * w.R);
+    w.off[3] = c.take(w.counts, B * 2 * sizeof(int32_t));
+    w.off[4] = c.take(w.parts, B * w.nparts * sizeof(double));
+    w.bytes = c.bytes;
     return 0;
 }
 
@@ -437,19 +443,19 @@ int ia_ssd_loss_bwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch,
 size_t ia_ssd_head_loss_workspace_bytes(const ia_ssd_geom *g, int batch)
 {
     ia::SsdTable t;
-    ia::SsdLossLayout w;
-    if (ia::make_ssd_table(g, nullptr, t) || ia::ssdloss_layout(t, batch, w)) return 0;
-    return w.total;
+    ia::SsdLossWorkspace w;
+    if (ia::make_ssd_table(g, nullptr, t) || ia::carve_ssdloss(t, batch, nullptr, w)) return 0;
+    return w.bytes;
 }
 
 int ia_ssd_head_loss_workspace_layout(const ia_ssd_geom *g, int batch, size_t offsets[5])
 {
     ia::SsdTable t;
-    ia::SsdLossLayout w;
+    ia::SsdLossWorkspace w;
     if (!offsets) return IA_E_ARG;
     int rc = ia::make_ssd_table(g, nullptr, t);
     if (rc) return rc;
-    if ((rc = ia::ssdloss_layout(t, batch, w))) return rc;
+    if ((rc = ia::carve_ssdloss(t, batch, nullptr, w))) return rc;
     for (int i = 0; i < 5; ++i) offsets[i] = w.off[i];
     return 0;
 }
@@ -460,25 +466,20 @@ int ia_ssd_head_loss_fwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int b
                          float beta, void *workspace, size_t workspace_bytes, float *losses, void *stream)
 {
     ia::SsdTable t;
-    ia::SsdLossLayout w;
+    ia::SsdLossWorkspace w;
     if (!p || dtype != IA_F32) return IA_E_ARG;
     int rc = ia::make_ssd_table(g, p, t);
     if (rc) return rc;
     if (neg_pos_ratio < 0 || !(beta > 0.0f)) return IA_E_ARG;
     if (!avg_factor_dev && !(avg_factor > 0.0f)) return IA_E_ARG;
     if (!workspace || !losses || ((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
-    if ((rc = ia::ssdloss_layout(t, batch, w))) return rc;
-    if (workspace_bytes < w.total) return IA_E_ARG;
+    if ((rc = ia::carve_ssdloss(t, batch, workspace, w))) return rc;
+    if (workspace_bytes < w.bytes) return IA_E_ARG;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    float *ce = reinterpret_cast<float *>(ws + w.off[0]), *lse = reinterpret_cast<float *>(ws + w.off[1]);
-    uint8_t *sel = reinterpret_cast<uint8_t *>(ws + w.off[2]);
-    int32_t *counts = reinterpret_cast<int32_t *>(ws + w.off[3]);
-    double *parts = reinterpret_cast<double *>(ws + w.off[4]);
     const ia::SsdTargets tg = {labels, label_weights, bbox_targets, bbox_weights};
-    if ((rc = ia::launch_ssdloss_rows(t, batch, tg, beta, ce, lse, parts, s))) return rc;
-    return ia::launch_ssd_mine(ce, labels, batch, w.R, neg_pos_ratio, parts, w.nparts, avg_factor_dev, avg_factor, sel,
-                               counts, losses, s);
+    if ((rc = ia::launch_ssdloss_rows(t, batch, tg, beta, w.ce, w.lse, w.parts, s))) return rc;
+    return ia::launch_ssd_mine(w.ce, labels, batch, w.R, neg_pos_ratio, w.parts, w.nparts, avg_factor_dev, avg_factor,
+                               w.sel, w.counts, losses, s);
 }
 
 int ia_ssd_head_loss_bwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int batch, int dtype,
@@ -488,17 +489,16 @@ int ia_ssd_head_loss_bwd(const ia_ssd_geom *g, const ia_ssd_level_ptrs *p, int b
                          const ia_ssd_level_ptrs *grads, void *stream)
 {
     ia::SsdTable t;
-    ia::SsdLossLayout w;
+    ia::SsdLossWorkspace w;
     if (!p || dtype != IA_F32) return IA_E_ARG;
     int rc = ia::make_ssd_table(g, p, t);
     if (rc) return rc;
     if (!workspace || ((uintptr_t)workspace & 255u) != 0) return IA_E_ARG;
-    if ((rc = ia::ssdloss_layout(t, batch, w))) return rc;
-    if (workspace_bytes < w.total) return IA_E_ARG;
-    const char *ws = static_cast<const char *>(workspace);
+    if ((rc = ia::carve_ssdloss(t, batch, workspace, w))) return rc;
+    if (workspace_bytes < w.bytes) return IA_E_ARG;
     const ia::SsdTargets tg = {labels, label_weights, bbox_targets, bbox_weights};
-    return ia::launch_ssdloss_bwd(t, batch, tg, beta, reinterpret_cast<const uint8_t *>(ws + w.off[2]), grad_losses, avg_factor_dev,
-                                  avg_factor, grads, (hipStream_t)stream);
+    return ia::launch_ssdloss_bwd(t, batch, tg, beta, w.sel, grad_losses, avg_factor_dev, avg_factor, grads,
+                                  (hipStream_t)stream);
 }
 
 }  // extern "C"
