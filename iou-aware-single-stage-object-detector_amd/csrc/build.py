@@ -17,7 +17,7 @@ SOURCES = ['capi.hip', 'decode.hip', 'select.hip', 'nms.hip', 'loss.hip', 'eleme
            'groupnorm.hip', 'pointdecode.hip', 'pointloss.hip', 'gconv_bf16.hip', 'gconv_bwd.hip', 'deform.hip',
            'masked_conv.hip', 'guideddecode.hip', 'wino_split_gemm.hip', 'l2norm.hip', 'ssddecode.hip', 'ssdloss.hip']
 HEADERS = ['ia_math.hpp', 'ia_block.hpp', 'ia_internal.hpp', 'ia_loss.hpp', 'ia_headloss.hpp', 'ia_rowmax_dev.hpp', 'ia_gather_dev.hpp', 'ia_nms.hpp', 'ia_conv3.hpp', 'ia_wino.hpp', 'ia_softmax_dev.hpp',
-           'ia_compact_dev.hpp', 'ia_ssd.hpp', '../../include/iouaware.h']
+           'ia_compact_dev.hpp', 'ia_ssd.hpp', 'ia_gconv.hpp', '../../include/iouaware.h']
 OUT = os.path.join(HERE, 'libiouaware_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fhip-fp32-correctly-rounded-divide-sqrt', '-fno-gpu-rdc',

@@ -50,13 +50,6 @@ constexpr int kCvMaxPatchPx64 = 128;      // ... two pieces per thread (8 x 8, 4
 constexpr int kCvBigTiles = 2048;         // maps with this many 128-pixel tiles in the batch take (4, 1, 4)
 constexpr int kCvBN = 256;
 
-__device__ __forceinline__ uint32_t bf16_rne(float f)
-{
-    uint32_t u = to_bits(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 // MB = 32-pixel accumulator blocks per wavefront: 4 (256-pixel tiles) or 2 (128-pixel tiles, for
 // feature maps whose 256-pixel tiles would leave most of the chip's workgroup slots empty)
 // WM x WN wavefronts, each 32 * MB pixels x 64 output channels: a tile of 32 * MB * WM pixels and

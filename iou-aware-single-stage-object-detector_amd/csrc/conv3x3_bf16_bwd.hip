@@ -220,13 +220,6 @@ __global__ void __launch_bounds__(256) k_conv3x3_bf16_wgrad_reduce(const float *
     dw[(((int64_t)g * Cout + co) * Cin + ci) * 9 + tap] = v;
 }
 
-__device__ __forceinline__ uint16_t wg_bf16_rne(float f)
-{
-    const uint32_t u = to_bits(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 // fp32 (groups * Cout, Cin, 3, 3) -> the fragment order of k_conv3x3_pack (conv3x3_bf16.hip) for a
 // convolution with Kin input and Kout output channels: (Cin, Cout), or -- adjoint -- (Cout rounded up to
 // 32, Cin) with w'[ci][co][tap] = w[co][ci][8 - tap] and zero rows for the padded input channels
@@ -255,7 +248,7 @@ __global__ void __launch_bounds__(256) k_conv3x3_pack_f32(const float *w, uint16
     } else {
         if (n < Cout) v = w[(((int64_t)g * Cout + n) * Cin + k) * 9 + tap];
     }
-    wp[idx] = wg_bf16_rne(v);
+    wp[idx] = (uint16_t)f32_to_bf16(v);
 }
 
 // ------------------------------------------------------------------ ReLU backward + bias gradient

@@ -25,41 +25,7 @@ struct AffineArgs {
 constexpr int kEwThreads = 256;
 constexpr int kEwPerThread = 16;      // elements per thread per workgroup (4 x 16 B for fp32)
 
-template <typename T> struct Pack;
-template <> struct Pack<float> {
-    static constexpr int N = 4;
-    using V = float4;
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[4]) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-    static __device__ __forceinline__ V pack(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Pack<uint16_t> {
-    static constexpr int N = 8;
-    using V = uint4;
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[8])
-    {
-        v[0] = from_bits(q.x << 16); v[1] = from_bits(q.x & 0xffff0000u);
-        v[2] = from_bits(q.y << 16); v[3] = from_bits(q.y & 0xffff0000u);
-        v[4] = from_bits(q.z << 16); v[5] = from_bits(q.z & 0xffff0000u);
-        v[6] = from_bits(q.w << 16); v[7] = from_bits(q.w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ uint32_t rne(float f)       // fp32 -> bf16 bits, round-nearest-even
-    {
-        uint32_t u = to_bits(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    }
-    static __device__ __forceinline__ V pack(const float (&v)[8])
-    {
-        V q;
-        q.x = rne(v[0]) | (rne(v[1]) << 16); q.y = rne(v[2]) | (rne(v[3]) << 16);
-        q.z = rne(v[4]) | (rne(v[5]) << 16); q.w = rne(v[6]) | (rne(v[7]) << 16);
-        return q;
-    }
-};
-
-template <typename T> __device__ __forceinline__ void store_f32(T *p, float v);
-template <> __device__ __forceinline__ void store_f32<float>(float *p, float v) { *p = v; }
-template <> __device__ __forceinline__ void store_f32<uint16_t>(uint16_t *p, float v) { *p = (uint16_t)Pack<uint16_t>::rne(v); }
+template <typename T> using Pack = Elems<T, 16 / sizeof(T)>;        // 16 bytes: four floats, eight bf16
 
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(kEwThreads) k_affine_act(AffineArgs a)
@@ -90,7 +56,7 @@ __global__ void __launch_bounds__(kEwThreads) k_affine_act(AffineArgs a)
                     if (has_res) y = y + (w[j] * rs + rb);
                     v[j] = (a.relu && !(y > 0.0f)) ? ((y != y) ? y : 0.0f) : y;
                 }
-                *reinterpret_cast<V *>(x + i) = Pack<T>::pack(v);
+                Pack<T>::store(x + i, v);
             }
         }
     } else {
@@ -185,7 +151,7 @@ __global__ void __launch_bounds__(kEwThreads) k_affine_act_nhwc(AffineArgs a, in
                 if (has_res) y = y + (w[j] * rs[j] + rb[j]);
                 v[j] = (a.relu && !(y > 0.0f)) ? ((y != y) ? y : 0.0f) : y;
             }
-            *reinterpret_cast<V *>(x + idx[u]) = Pack<T>::pack(v);
+            Pack<T>::store(x + idx[u], v);
         }
         c0 += step_mod;
         if (c0 >= C) c0 -= C;
@@ -251,7 +217,7 @@ __global__ void __launch_bounds__(kEwThreads) k_affine_act_nhwc_fast(AffineArgs 
             }
         }
         if (ok[u])
-            *reinterpret_cast<V *>(x + base + (int64_t)u * kEwThreads * N) = Pack<T>::pack(v);
+            Pack<T>::store(x + base + (int64_t)u * kEwThreads * N, v);
     }
 }
 
@@ -408,7 +374,7 @@ __global__ void __launch_bounds__(256) k_affine_relu_maxpool(PoolArgs a)
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) m[j] = (m[j] > 0.f) ? m[j] : 0.f;
-    *reinterpret_cast<V *>(static_cast<T *>(a.out) + (((size_t)b * a.Ho + yo) * a.Wo + xo) * a.C + c) = Pack<T>::pack(m);
+    Pack<T>::store(static_cast<T *>(a.out) + (((size_t)b * a.Ho + yo) * a.Wo + xo) * a.C + c, m);
 }
 
 }  // namespace ia
@@ -483,7 +449,7 @@ __global__ void __launch_bounds__(256) k_upsample_add(UpAddArgs a)
     Pack<T>::unpack(vq, v);
 #pragma unroll
     for (int j = 0; j < N; ++j) v[j] += u[j];             // bf16: one rounding of the fp32 sum, like eager's add
-    *f = Pack<T>::pack(v);
+    Pack<T>::store(reinterpret_cast<T *>(f), v);
 }
 
 }  // namespace ia

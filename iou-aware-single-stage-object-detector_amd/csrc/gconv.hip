@@ -23,46 +23,9 @@
 // (no change: five wavefronts per SIMD already hide the 40-cycle dependent latency), several rows
 // per wavefront to amortise the operand loads (no change).
 #include <string.h>
-#include "ia_internal.hpp"
+#include "ia_gconv.hpp"
 
 namespace ia {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Lanes are (pixel i = lane & 15, channel quad kk = lane >> 4): a DPP row holds the 16 pixels of
-// one quad.  value of pixel i-1: row_shr:1 of the centre, lane 0 from the previous tile's lane 15
-// (row_ror:1 of it); value of pixel i+1: row_shl:1, lane 15 from the next tile's lane 0
-// (row_ror:15 of it).  Lanes without a DPP source keep `old` (bound_ctrl = 0).
-__device__ __forceinline__ float dpp_shr1(float old, float src)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-        __builtin_bit_cast(int, old), __builtin_bit_cast(int, src), 0x111, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float dpp_shl1(float old, float src)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-        __builtin_bit_cast(int, old), __builtin_bit_cast(int, src), 0x101, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_ror(float src)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-        0, __builtin_bit_cast(int, src), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ f32x4 shift_from_left(const f32x4 &c, const f32x4 &prev)
-{
-    f32x4 o;
-    o.x = dpp_shr1(dpp_ror<0x121>(prev.x), c.x); o.y = dpp_shr1(dpp_ror<0x121>(prev.y), c.y);
-    o.z = dpp_shr1(dpp_ror<0x121>(prev.z), c.z); o.w = dpp_shr1(dpp_ror<0x121>(prev.w), c.w);
-    return o;
-}
-__device__ __forceinline__ f32x4 shift_from_right(const f32x4 &c, const f32x4 &next)
-{
-    f32x4 o;
-    o.x = dpp_shl1(dpp_ror<0x12F>(next.x), c.x); o.y = dpp_shl1(dpp_ror<0x12F>(next.y), c.y);
-    o.z = dpp_shl1(dpp_ror<0x12F>(next.z), c.z); o.w = dpp_shl1(dpp_ror<0x12F>(next.w), c.w);
-    return o;
-}
 
 struct GConvArgs {
     const float *x;            // (B, H, W, C) channels-last
@@ -83,20 +46,8 @@ __global__ void __launch_bounds__(256) k_gconv3x3(GConvArgs a)
     const int row = blockIdx.x;                        // (b, yo)
     const int b = row / a.Ho, yo = row - b * a.Ho;
     const int cbase = sg * 16 * NB;
-    // B operands: w[t][ci][c][co] for this lane
     float w[9][NB][4][NB];
-    {
-        const float *wp = a.wpack + (size_t)sg * 9 * NB * 4 * NB * 64 + lane;
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int ci = 0; ci < NB; ++ci)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int co = 0; co < NB; ++co)
-                        w[t][ci][c][co] = wp[(size_t)(((t * NB + ci) * 4 + c) * NB + co) * 64];
-    }
+    gconv_load_w<NB>(a.wpack, sg, lane, w);
     float bz[NB];
 #pragma unroll
     for (int co = 0; co < NB; ++co) bz[co] = a.bias ? a.bias[cbase + 16 * co + i] : 0.0f;
@@ -120,11 +71,7 @@ __global__ void __launch_bounds__(256) k_gconv3x3(GConvArgs a)
             const int xc = (xo >= a.W) ? a.W - 1 : xo;
             const float *p = xb + ((size_t)yc * a.W + xc) * a.C;
 #pragma unroll
-            for (int ci = 0; ci < NB; ++ci) {
-                const f32x4 q = *reinterpret_cast<const f32x4 *>(p + 16 * ci);   // unconditional
-                f32x4 z; z.x = z.y = z.z = z.w = 0.0f;
-                dst[r][ci] = in ? q : z;
-            }
+            for (int ci = 0; ci < NB; ++ci) dst[r][ci] = gconv_load16(p + 16 * ci, in);
         }
     };
     if (STRIDE == 1) {
@@ -162,40 +109,23 @@ __global__ void __launch_bounds__(256) k_gconv3x3(GConvArgs a)
                 const int xc = (xi < 0) ? 0 : ((xi >= a.W) ? a.W - 1 : xi);
                 const float *p = xb + ((size_t)yc * a.W + xc) * a.C;
 #pragma unroll
-                for (int ci = 0; ci < NB; ++ci) {
-                    const f32x4 q = *reinterpret_cast<const f32x4 *>(p + 16 * ci);   // unconditional
-                    f32x4 z; z.x = z.y = z.z = z.w = 0.0f;
-                    v[t][ci] = in ? q : z;
-                }
+                for (int ci = 0; ci < NB; ++ci) v[t][ci] = gconv_load16(p + 16 * ci, in);
             }
         }
         f32x4 acc[NB];
 #pragma unroll
         for (int co = 0; co < NB; ++co) { acc[co].x = acc[co].y = acc[co].z = acc[co].w = 0.0f; }
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
+        for (int t = 0; t < 9; ++t) gconv_mfma_tap<NB>(v[t], w[t], acc);
 #pragma unroll
-            for (int ci = 0; ci < NB; ++ci) {
-                const float e[4] = {v[t][ci].x, v[t][ci].y, v[t][ci].z, v[t][ci].w};
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int co = 0; co < NB; ++co)
-                        acc[co] = __builtin_amdgcn_mfma_f32_16x16x4f32(e[c], w[t][ci][c][co], acc[co],
-                                                                       0, 0, 0);
-            }
-        // D: column (lane & 15) = output channel, row 4 * (lane >> 4) + r = pixel of the tile
-#pragma unroll
-        for (int co = 0; co < NB; ++co) {
-            const float o[4] = {acc[co].x, acc[co].y, acc[co].z, acc[co].w};
+        for (int co = 0; co < NB; ++co)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int px = tile * 16 + 4 * kk + r;
-                float val = o[r] + bz[co];
+                float val = acc[co][r] + bz[co];
                 if (a.relu) val = (val > 0.0f) ? val : 0.0f;
-                if (px < a.Wo) yb[(size_t)px * a.C + 16 * co] = val;
+                acc[co][r] = val;
             }
-        }
+        gconv_store_tile<NB>(yb, a.C, a.Wo, kk, acc, [&](int j) { return tile * 16 + j; });
         if (STRIDE == 1) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
@@ -215,29 +145,16 @@ extern "C" {
 // host-side weight arrangement: (C, Cg, 3, 3) grouped weight (+ per-output-channel scale) ->
 // (SG, 9, NB, 4, NB, 64) B operands.  Element [sg][t][ci][c][co][lane] = scale[o] * W[o][in][t]
 // with o = sg*16*NB + 16*co + (lane & 15), in = 16*ci + 4*(lane >> 4) + c (inside the
-// supergroup), zero when o and in belong to different groups.
+// supergroup), zero when o and in belong to different groups: gconv_pack_elem of ia_gconv.hpp, the
+// function the device pack (k_gconv_pack) calls per thread.
 int ia_grouped_conv3x3_pack(const float *weight, const float *scale, int channels, int groups,
                             float *wpack)
 {
-    if (!weight || !wpack || channels < 16 || groups < 1 || channels % groups) return IA_E_ARG;
-    const int cg = channels / groups;
-    if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return IA_E_ARG;
-    const int nb = (cg == 32) ? 2 : 1, sgc = 16 * nb;
-    if (channels % sgc) return IA_E_ARG;
-    const int SG = channels / sgc;
-    for (int sg = 0; sg < SG; ++sg)
-        for (int t = 0; t < 9; ++t)
-            for (int ci = 0; ci < nb; ++ci)
-                for (int c = 0; c < 4; ++c)
-                    for (int co = 0; co < nb; ++co)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int o = sg * sgc + 16 * co + (lane & 15);
-                            const int in = sg * sgc + 16 * ci + 4 * (lane >> 4) + c;
-                            float v = 0.0f;
-                            if (o / cg == in / cg)
-                                v = weight[((size_t)o * cg + (in % cg)) * 9 + t] * (scale ? scale[o] : 1.0f);
-                            wpack[((((((size_t)sg * 9 + t) * nb + ci) * 4 + c) * nb + co) * 64) + lane] = v;
-                        }
+    int nb = 1;
+    const int cg = ia::gconv_channels(channels, groups, &nb);
+    if (!weight || !wpack || !cg) return IA_E_ARG;
+    const int64_t total = (int64_t)(channels / (16 * nb)) * 9 * nb * 4 * nb * 64;
+    for (int64_t q = 0; q < total; ++q) wpack[q] = ia::gconv_pack_elem(weight, scale, cg, nb, q, false);
     return 0;
 }
 
@@ -245,14 +162,10 @@ int ia_grouped_conv3x3_nhwc(const float *x, const float *wpack, const float *bia
                             int batch, int H, int W, int channels, int groups, int stride, int relu,
                             void *stream)
 {
-    if (!x || !wpack || !y || batch < 1 || H < 1 || W < 1 || channels < 16 || groups < 1 ||
-        channels % groups || (stride != 1 && stride != 2))
-        return IA_E_ARG;
+    int nb = 1;
+    if (!x || !wpack || !y || batch < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2)) return IA_E_ARG;
     if (((uintptr_t)x & 15u) || ((uintptr_t)y & 15u)) return IA_E_ARG;
-    const int cg = channels / groups;
-    if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return IA_E_ARG;
-    const int nb = (cg == 32) ? 2 : 1;
-    if (channels % (16 * nb)) return IA_E_ARG;
+    if (!ia::gconv_channels(channels, groups, &nb)) return IA_E_ARG;
     ia::GConvArgs a;
     a.x = x; a.wpack = wpack; a.bias = bias; a.y = y;
     a.B = batch; a.H = H; a.W = W; a.C = channels;
@@ -262,10 +175,7 @@ int ia_grouped_conv3x3_nhwc(const float *x, const float *wpack, const float *bia
     if (rows > 2147483647LL) return IA_E_ARG;
     dim3 grid((unsigned)rows, (unsigned)((a.SG + 3) / 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (nb == 1 && stride == 1) hipLaunchKernelGGL((ia::k_gconv3x3<1, 1>), grid, block, 0, s, a);
-    else if (nb == 1) hipLaunchKernelGGL((ia::k_gconv3x3<1, 2>), grid, block, 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((ia::k_gconv3x3<2, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((ia::k_gconv3x3<2, 2>), grid, block, 0, s, a);
+    GCONV_DISPATCH(nb, stride, ia::k_gconv3x3, grid, block, s, a);
     return ia::hip_status(hipGetLastError());
 }
 

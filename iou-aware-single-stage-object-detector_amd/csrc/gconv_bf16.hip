@@ -22,41 +22,13 @@
 //   * out-of-image taps: unconditional loads from clamped addresses, zeroed by a mask.
 // No atomics, no LDS, a fixed reduction order: the same bits on every launch.
 #include <string.h>
-#include "ia_internal.hpp"
+#include "ia_gconv.hpp"
 
 namespace ia {
 
-typedef float gb_f32x4 __attribute__((ext_vector_type(4)));
 typedef float gb_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gb_bf16x2 __attribute__((ext_vector_type(2)));
-
-// see gconv.hip: a DPP row holds the 16 pixels of one channel octet
-__device__ __forceinline__ uint32_t gb_shr1(uint32_t old, uint32_t src)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, 0x111, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t gb_shl1(uint32_t old, uint32_t src)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, 0x101, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t gb_ror(uint32_t src)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, CTRL, 0xf, 0xf, false);
-}
-// pixel i - 1: row_shr:1 of the centre, lane 0 from the previous tile's lane 15 (row_ror:1)
-__device__ __forceinline__ uint4 gb_from_left(const uint4 &c, const uint4 &prev)
-{
-    return make_uint4(gb_shr1(gb_ror<0x121>(prev.x), c.x), gb_shr1(gb_ror<0x121>(prev.y), c.y),
-                      gb_shr1(gb_ror<0x121>(prev.z), c.z), gb_shr1(gb_ror<0x121>(prev.w), c.w));
-}
-// pixel i + 1: row_shl:1 of the centre, lane 15 from the next tile's lane 0 (row_ror:15)
-__device__ __forceinline__ uint4 gb_from_right(const uint4 &c, const uint4 &next)
-{
-    return make_uint4(gb_shl1(gb_ror<0x12F>(next.x), c.x), gb_shl1(gb_ror<0x12F>(next.y), c.y),
-                      gb_shl1(gb_ror<0x12F>(next.z), c.z), gb_shl1(gb_ror<0x12F>(next.w), c.w));
-}
 
 constexpr int kGbSG = 32;                 // channels per supergroup
 
@@ -125,8 +97,8 @@ __global__ void __launch_bounds__(256) k_gconv3x3_bf16(GConvBf16Args a)
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 v[3 * r + 1] = cur[r];
-                v[3 * r + 0] = gb_from_left(cur[r], prv[r]);
-                v[3 * r + 2] = gb_from_right(cur[r], nxt[r]);
+                v[3 * r + 0] = shift_from_left(cur[r], prv[r]);
+                v[3 * r + 2] = shift_from_right(cur[r], nxt[r]);
             }
         } else {
             const int xo = tile * 16 + i;              // this lane's output pixel
@@ -142,7 +114,7 @@ __global__ void __launch_bounds__(256) k_gconv3x3_bf16(GConvBf16Args a)
                 v[t] = make_uint4(q.x & mk, q.y & mk, q.z & mk, q.w & mk);
             }
         }
-        gb_f32x4 acc[2];
+        f32x4 acc[2];
 #pragma unroll
         for (int co = 0; co < 2; ++co) { acc[co].x = acc[co].y = acc[co].z = acc[co].w = 0.0f; }
 #pragma unroll
@@ -174,19 +146,10 @@ __global__ void __launch_bounds__(256) k_gconv3x3_bf16(GConvBf16Args a)
     }
 }
 
-static uint16_t gb_bf16_rne(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 static bool gb_shape_ok(int channels, int groups)
 {
-    if (channels < kGbSG || groups < 1 || channels % groups || channels % kGbSG) return false;
-    const int cg = channels / groups;
-    return cg == 4 || cg == 8 || cg == 16 || cg == 32;
+    if (channels < kGbSG || channels % kGbSG) return false;
+    return gconv_cg(channels, groups) != 0;
 }
 
 }  // namespace ia
@@ -218,7 +181,7 @@ int ia_grouped_conv3x3_pack_bf16(const float *weight, const float *scale, int ch
                         uint16_t v = 0;
                         if (o / cg == in / cg) {
                             const float wv = weight[((size_t)o * cg + (in % cg)) * 9 + t];
-                            v = ia::gb_bf16_rne(scale ? wv * scale[o] : wv);
+                            v = ia::bf16_rne_host(scale ? wv * scale[o] : wv);
                         }
                         wpack[(((((size_t)sg * 9 + t) * 2 + co) * 64) + lane) * 8 + j] = v;
                     }

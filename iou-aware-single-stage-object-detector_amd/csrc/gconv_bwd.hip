@@ -35,11 +35,9 @@
 //             rows_per_slice * Wo / 4 MFMA steps (<= 256 unless a single row is longer) or
 //             slices / 4 adds.  The slice count aims at ~2048 wavefronts: more only adds
 //             workspace traffic (9 * 16 * NB * C floats per slice).
-#include "ia_internal.hpp"
+#include "ia_gconv.hpp"
 
 namespace ia {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDwWaves = 2048;         // wavefronts the weight gradient aims at (256 CUs x 8)
 constexpr int kDwMaxPixels = 1024;     // pixels of one slice (unless one row is longer): the fp32 chain
@@ -56,24 +54,7 @@ __global__ void __launch_bounds__(256) k_gconv_pack(GPackArgs a)
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (a.adjoint == 2 ? 2 * total : total)) return;
     const bool adj = (a.adjoint == 1) || (idx >= total);     // adjoint 2: the plain pack, then the adjoint one
-    int64_t q = (idx >= total) ? idx - total : idx;
-    const int lane = (int)(q & 63); q >>= 6;
-    const int co = (int)(q % a.NB); q /= a.NB;
-    const int c = (int)(q & 3); q >>= 2;
-    const int ci = (int)(q % a.NB); q /= a.NB;
-    const int t = (int)(q % 9);
-    const int sg = (int)(q / 9);
-    const int sgc = 16 * a.NB;
-    const int o = sg * sgc + 16 * co + (lane & 15);
-    const int in = sg * sgc + 16 * ci + 4 * (lane >> 4) + c;
-    float v = 0.0f;
-    if (o / a.cg == in / a.cg) {
-        if (adj)
-            v = a.weight[((size_t)in * a.cg + (o % a.cg)) * 9 + (8 - t)];
-        else
-            v = a.weight[((size_t)o * a.cg + (in % a.cg)) * 9 + t] * (a.scale ? a.scale[o] : 1.0f);
-    }
-    a.wpack[idx] = v;
+    a.wpack[idx] = gconv_pack_elem(a.weight, a.scale, a.cg, a.NB, (idx >= total) ? idx - total : idx, adj);
 }
 
 struct GDxArgs {
@@ -266,20 +247,6 @@ __global__ void __launch_bounds__(256) k_gconv_dw_reduce(const float *part, floa
     if (in / cg == o / cg) dw[((size_t)o * cg + (in % cg)) * 9 + t] = sum;
 }
 
-// the shapes ia_grouped_conv3x3_nhwc takes; -> channels per group (0: not covered)
-static int gconv_shape(int batch, int H, int W, int channels, int groups, int stride, int *nb)
-{
-    if (batch < 1 || H < 1 || W < 1 || channels < 16 || groups < 1 || channels % groups ||
-        (stride != 1 && stride != 2))
-        return 0;
-    const int cg = channels / groups;
-    if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return 0;
-    *nb = (cg == 32) ? 2 : 1;
-    if (channels % (16 * *nb)) return 0;
-    if ((int64_t)batch * H > 2147483647LL) return 0;
-    return cg;
-}
-
 static int dw_rows_per_slice(int64_t rows, int Wo, int units)
 {
     int64_t want = (kDwWaves + units - 1) / units;                 // slices
@@ -363,10 +330,7 @@ int ia_grouped_conv3x3_bwd_weight_nhwc(const float *x, const float *dz, float *d
     const int slices = (a.rows + a.rows_per_slice - 1) / a.rows_per_slice;
     dim3 grid((unsigned)slices, (unsigned)((a.SG * nb + 3) / 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (nb == 1 && stride == 1) hipLaunchKernelGGL((ia::k_gconv_dw<1, 1>), grid, block, 0, s, a);
-    else if (nb == 1) hipLaunchKernelGGL((ia::k_gconv_dw<1, 2>), grid, block, 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((ia::k_gconv_dw<2, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((ia::k_gconv_dw<2, 2>), grid, block, 0, s, a);
+    GCONV_DISPATCH(nb, stride, ia::k_gconv_dw, grid, block, s, a);
     int st = ia::hip_status(hipGetLastError());
     if (st) return st;
     const int n = channels * 16 * nb * 9;              // accumulator elements of one slice

@@ -174,19 +174,6 @@ __device__ __forceinline__ void bal_wave_sums(double *sums, int L, int l, double
     }
 }
 
-template <typename T> struct MLPack;
-template <> struct MLPack<float> {
-    typedef float V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[4]) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-};
-template <> struct MLPack<uint16_t> {
-    typedef uint16_t V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[4])
-    {
-        v[0] = bf16_to_f32(q.x); v[1] = bf16_to_f32(q.y); v[2] = bf16_to_f32(q.z); v[3] = bf16_to_f32(q.w);
-    }
-};
-
 template <typename T, bool BWD, bool BAL_CLS = false>
 __global__ void __launch_bounds__(64) k_focal_ml(typename FocalSel<BAL_CLS>::ML a)
 {
@@ -231,7 +218,7 @@ __global__ void __launch_bounds__(64) k_focal_ml(typename FocalSel<BAL_CLS>::ML 
         // Software pipeline over groups of K class planes with two register buffers in ping-pong
         // (no register copies, so the waits stay counted): while one group is evaluated the next
         // group's 8 KiB per wavefront are in flight.
-        using V = typename MLPack<T>::V;
+        using V = typename Elems<T, 4>::XV;
         const T *src = cls + pc[0];
         auto issue = [&](V (&q)[K], int c0) {
 #pragma unroll
@@ -248,8 +235,8 @@ __global__ void __launch_bounds__(64) k_focal_ml(typename FocalSel<BAL_CLS>::ML 
             for (int i = 0; i < K; i += 2) {
                 if (c0 + i < cend) {                       // wave-uniform
                     float v[8], t[8], rq[8], lg[8];
-                    MLPack<T>::unpack(q[i], *reinterpret_cast<float (*)[4]>(&v[0]));
-                    MLPack<T>::unpack(q[i + 1], *reinterpret_cast<float (*)[4]>(&v[4]));
+                    Elems<T, 4>::unpack(q[i], *reinterpret_cast<float (*)[4]>(&v[0]));
+                    Elems<T, 4>::unpack(q[i + 1], *reinterpret_cast<float (*)[4]>(&v[4]));
 #pragma unroll
                     for (int k = 0; k < 8; ++k)
                         t[k] = __builtin_amdgcn_exp2f(__builtin_fminf(v[k], kXMax) * kLog2e);
@@ -610,10 +597,10 @@ __global__ void __launch_bounds__(256) k_focal_nhwc(typename FocalSel<BAL_CLS>::
         const int an = (int)(((float)r + 0.5f) * inv_c4);
         const int64_t anchor = pix * A + an;
         cq[u] = r - an * C4;
-        using V = typename MLPack<T>::V;
+        using V = typename Elems<T, 4>::XV;
         const V q = __builtin_nontemporal_load(reinterpret_cast<const V *>(cls + pix * ps + 4 * r));
         float x4[4];
-        MLPack<T>::unpack(q, x4);
+        Elems<T, 4>::unpack(q, x4);
         v[u] = make_float4(x4[0], x4[1], x4[2], x4[3]);
         labv[u] = labels[2 * anchor];
         lwv[u] = UNITW ? 1.0f : lwp[anchor];

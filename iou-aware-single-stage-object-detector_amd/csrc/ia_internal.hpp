@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/iouaware.h"
+#include "ia_math.hpp"
 
 namespace ia {
 
@@ -245,6 +246,9 @@ inline int check_iou_ptrs(const LevelTable &t, const ia_level_ptrs &p)
         if ((p.iou[l] != nullptr) != t.iou()) return IA_E_ARG;
     return 0;
 }
+
+// the host-side bf16 packs round with the kernels' own f32_to_bf16: one function, no twin to drift
+inline uint16_t bf16_rne_host(float f) { return (uint16_t)f32_to_bf16(f); }
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 

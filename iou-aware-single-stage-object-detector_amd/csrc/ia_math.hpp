@@ -17,8 +17,8 @@
 
 namespace ia {
 
-__device__ __forceinline__ float from_bits(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t to_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
+__host__ __device__ __forceinline__ float from_bits(uint32_t u) { return __builtin_bit_cast(float, u); }
+__host__ __device__ __forceinline__ uint32_t to_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 __device__ __forceinline__ float expf_(float x)
 {
@@ -151,8 +151,10 @@ __device__ __forceinline__ float ordered_key_inv(uint32_t k)
 // bf16 (raw bits) -> fp32
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return from_bits((uint32_t)h << 16); }
 
-// fp32 -> bf16 (raw bits), round to nearest even; a NaN stays a (quiet) NaN
-__device__ __forceinline__ uint32_t f32_to_bf16(float f)
+// fp32 -> bf16 (raw bits), round to nearest even; a NaN stays a (quiet) NaN.  THE rounding of the
+// library: every bf16 store of a kernel goes through it, and the host-side packs do too
+// (bf16_rne_host of ia_internal.hpp is this function).
+__host__ __device__ __forceinline__ uint32_t f32_to_bf16(float f)
 {
     const uint32_t u = to_bits(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
@@ -179,5 +181,49 @@ __device__ __forceinline__ uint4 f32_to_bf16x8(const float (&v)[8])
 template <typename T> __device__ __forceinline__ float load_f32(const T *p);
 template <> __device__ __forceinline__ float load_f32<float>(const float *p) { return *p; }
 template <> __device__ __forceinline__ float load_f32<uint16_t>(const uint16_t *p) { return bf16_to_f32(*p); }
+template <typename T> __device__ __forceinline__ void store_f32(T *p, float v);
+template <> __device__ __forceinline__ void store_f32<float>(float *p, float v) { *p = v; }
+template <> __device__ __forceinline__ void store_f32<uint16_t>(uint16_t *p, float v) { *p = (uint16_t)f32_to_bf16(v); }
+
+// N consecutive values of T (float, or bf16 as raw uint16_t) <-> float[N], one vector access each;
+// a bf16 store rounds every value once with f32_to_bf16.  V is the memory vector, XV the same bytes
+// as an ext_vector_type (what __builtin_nontemporal_load takes); unpack reads either spelling.
+template <typename T, int N> struct Elems;
+template <> struct Elems<float, 4> {
+    static constexpr int N = 4;
+    using V = float4;
+    typedef float XV __attribute__((ext_vector_type(4)));
+    template <typename Q> static __device__ __forceinline__ void unpack(const Q &q, float (&v)[4])
+    {
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    static __device__ __forceinline__ void load(const float *p, float (&v)[4]) { unpack(*reinterpret_cast<const V *>(p), v); }
+    static __device__ __forceinline__ void store(float *p, const float (&v)[4])
+    {
+        *reinterpret_cast<V *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+};
+template <> struct Elems<uint16_t, 4> {
+    static constexpr int N = 4;
+    using V = ushort4;
+    typedef uint16_t XV __attribute__((ext_vector_type(4)));
+    template <typename Q> static __device__ __forceinline__ void unpack(const Q &q, float (&v)[4])
+    {
+        v[0] = bf16_to_f32(q.x); v[1] = bf16_to_f32(q.y); v[2] = bf16_to_f32(q.z); v[3] = bf16_to_f32(q.w);
+    }
+    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[4]) { unpack(*reinterpret_cast<const V *>(p), v); }
+    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[4])
+    {
+        *reinterpret_cast<uint2 *>(p) = make_uint2(f32_to_bf16(v[0]) | (f32_to_bf16(v[1]) << 16),
+                                                   f32_to_bf16(v[2]) | (f32_to_bf16(v[3]) << 16));
+    }
+};
+template <> struct Elems<uint16_t, 8> {
+    static constexpr int N = 8;
+    using V = uint4;
+    static __device__ __forceinline__ void unpack(const V &q, float (&v)[8]) { bf16x8_to_f32(q, v); }
+    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[8]) { unpack(*reinterpret_cast<const V *>(p), v); }
+    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[8]) { *reinterpret_cast<V *>(p) = f32_to_bf16x8(v); }
+};
 
 }  // namespace ia

@@ -68,21 +68,6 @@ __device__ __forceinline__ float focal_elem(float x, bool t, float at, float gam
     return (dbce * (at * mod) + (bce * at) * (dmod * dpt)) * gs;
 }
 
-template <typename T> struct LPack;
-template <> struct LPack<float> {
-    static constexpr int N = 4;
-    using V = float4;
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[4]) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-};
-template <> struct LPack<uint16_t> {
-    static constexpr int N = 4;
-    using V = ushort4;
-    static __device__ __forceinline__ void unpack(const V &q, float (&v)[4])
-    {
-        v[0] = bf16_to_f32(q.x); v[1] = bf16_to_f32(q.y); v[2] = bf16_to_f32(q.z); v[3] = bf16_to_f32(q.w);
-    }
-};
-
 // One wavefront per (image, anchor, tile of 256 positions) -- the row-max kernel's tiling:
 // every class-plane access is a contiguous 1 KiB segment, the label / weight of an anchor are
 // read once for all C classes.
@@ -138,7 +123,7 @@ __global__ void __launch_bounds__(64) k_focal(FocalArgs a)
     if (vec) {
         const T *src = cls + pc[0];
         constexpr int K = 8;                               // class planes in flight per wavefront
-        using V = typename LPack<T>::V;
+        using V = typename Elems<T, 4>::V;
         for (int c0 = cbeg; c0 < cend; c0 += K) {
             V q[K];
 #pragma unroll
@@ -151,7 +136,7 @@ __global__ void __launch_bounds__(64) k_focal(FocalArgs a)
                 const int c = c0 + i;
                 if (c < cend) {                            // wave-uniform
                     float v[4], o[4];
-                    LPack<T>::unpack(q[i], v);
+                    Elems<T, 4>::unpack(q[i], v);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const bool t = lab[j] == c + 1;
@@ -464,12 +449,7 @@ __device__ __forceinline__ float focal_op_load(const void *p, int64_t i, int dty
 __device__ __forceinline__ void focal_op_store(void *p, int64_t i, int dtype, float v)
 {
     switch (dtype) {
-    case IA_BF16: {
-        uint32_t u = to_bits(v);
-        u = ((u & 0x7fffffffu) > 0x7f800000u) ? ((u >> 16) | 0x40u) : ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-        static_cast<uint16_t *>(p)[i] = (uint16_t)u;
-        break;
-    }
+    case IA_BF16: static_cast<uint16_t *>(p)[i] = (uint16_t)f32_to_bf16(v); break;
     case IA_F16: static_cast<_Float16 *>(p)[i] = (_Float16)v; break;
     case IA_F64: static_cast<double *>(p)[i] = (double)v; break;
     default: static_cast<float *>(p)[i] = v;

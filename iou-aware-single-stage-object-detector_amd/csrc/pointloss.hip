@@ -28,9 +28,19 @@
 // the reg row optionally raw (d = exp(scale_l * x) formed here).
 //   forward : k_focal_nhwc<fwd, T, unit weights>  k_point_box_nhwc<T, fwd>  k_point_finalize   (3 launches)
 //   backward: k_point_box_nhwc<T, bwd>  k_focal_nhwc<bwd, T, unit weights>  [k_point_scale_finalize]
-// The labels are read from the int64 targets (low words), no packed copy; point_elem, the finalize kernel
-// and the slot layout are those of the NCHW node; the box kernel's backward also writes the zero gradient
-// of a row's padding channels and adds g * d * x into fp64 slots per level (d scale_l).
+// The labels are read from the int64 targets (low words), no packed copy; the finalize kernel and the
+// slot layout are those of the NCHW node; the box kernel's backward also writes the zero gradient of a
+// row's padding channels and adds g * d * x into fp64 slots per level (d scale_l).
+//
+// One body per step of the box loss.  The box kernels of the two layouts (k_point_box: NCHW planes;
+// k_point_box_nhwc: pixel rows of T, optional exp(scale x)) keep block location, the positive test,
+// their loads, their stores and the padding-channel zeros; the rest is shared: point_centre (also the
+// targets kernel's), point_elem, point_fwd_terms (the five sums), point_bwd_terms (the whole chain down
+// to the four distance gradients, exactly 0 at the minimum) and point_block_reduce (early-out, wave
+// sums, fixed tree, one fp64 atomic per term; its one-term form adds d scale_l).  With the same result
+// and upstream vectors the two backward kernels give the same bits (tests/test_gpu_point_loss_nhwc.py).
+// Host: both workspaces come off one Carver head (carve_point_head), both forwards end in
+// clear_point_slots ... launch_point_finalize, both box kernels are picked from a table.
 #include <string.h>
 #include "ia_loss.hpp"
 #include "ia_headloss.hpp"
@@ -85,6 +95,14 @@ __device__ __forceinline__ PtBlock locate_point_block(const HLLevels &lv, int bi
     return r;
 }
 
+// the image coordinates of point p of a level (targets and both box kernels)
+__device__ __forceinline__ void point_centre(int p, int W, int stride, float &px, float &py)
+{
+    const int y = p / W, x = p - y * W;
+    px = (float)(x * stride) + (float)(stride / 2);
+    py = (float)(y * stride) + (float)(stride / 2);
+}
+
 // ------------------------------------------------------------------ targets
 struct PtTargetArgs {
     HLLevels lv;
@@ -118,8 +136,8 @@ __global__ void __launch_bounds__(256) k_point_targets(PtTargetArgs a)
     const int p = r.p0 + threadIdx.x;
     bool is_pos = false;
     if (p < HW) {
-        const int y = p / W, x = p - y * W;
-        const float px = (float)(x * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+        float px, py;
+        point_centre(p, W, s, px, py);
         const float lo = a.lo[r.l], hi = a.hi[r.l];
         // areas.min(dim=1) over the row with non-candidates set to INF: the first minimum
         float best = 0.0f;
@@ -209,6 +227,71 @@ __device__ __forceinline__ PtElem point_elem(float px, float py, const float (&d
     return e;
 }
 
+// ---- one body per step of the box loss: what k_point_box and k_point_box_nhwc share ----
+// forward: -log(u) c | c | BCE_ctr | BCE_iou | 1 of one positive point
+template <bool IOU>
+__device__ __forceinline__ void point_fwd_terms(const PtElem &q, float xc, float xi, double (&acc)[kPtSums])
+{
+    acc[0] = (double)(-logf_(q.u) * q.c);
+    acc[1] = (double)q.c;
+    acc[2] = (double)bce_logits_(xc, q.c);
+    if constexpr (IOU) acc[3] = (double)bce_logits_(xi, q.u);
+    acc[4] = 1.0;
+}
+
+// backward of one positive point with respect to the four distances, the centerness and the IoU logit
+template <bool IOU>
+__device__ __forceinline__ void point_bwd_terms(const PtElem &q, float xc, float xi, const float *res,
+                                                const float *gin, int attach, float (&g_box)[4],
+                                                float &g_ctr, float &g_iou)
+{
+    const float n = res[4], sc = res[5];
+    const float gs_reg = gin[1] / sc, gs_ctr = gin[2] / n;
+    g_ctr = (sigmoidf_(xc) - q.c) * gs_ctr;
+    float gu = -(q.c / q.u) * gs_reg;                    // d(-log(u) c) / du
+    if constexpr (IOU) {
+        const float gs_iou = gin[3] / n;
+        g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
+        if (attach) gu += (-xi) * gs_iou;                // d BCE(xi, u) / du = -xi
+    }
+    // u = ov / un, un = ap + at - ov; both factors are formed as (v / un) / un, so that at
+    // ov == un (prediction == target) d/d ov is -2 d/d ap to the bit and the two halves below
+    // cancel it: the gradient at the loss's minimum is exactly 0
+    const float inv_un = 1.0f / q.un;
+    const float g_ov = gu * (((q.un + q.ov) * inv_un) * inv_un);
+    const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
+    const float g_w = g_ov * q.h, g_h = g_ov * q.w;      // w0, h0 > 0: both boxes hold the point
+    const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
+    // x1 = px - left, x2 = px + right: d/d left = -d/d x1
+    g_box[0] = g_pw + q.sx1 * g_w;
+    g_box[1] = g_ph + q.sy1 * g_h;
+    g_box[2] = g_pw + q.sx2 * g_w;
+    g_box[3] = g_ph + q.sy2 * g_h;
+}
+
+// NT fp64 terms of a 256-thread block into their slots: wave sums, the fixed ((r0 + r1) + r2) + r3
+// order, one atomic per term (term k at sums + k * IA_LOSS_SLOTS).  Positives are rare: a block
+// without one adds nothing.  SKIP: a term left out (-1: none).
+template <int NT, int SKIP>
+__device__ __forceinline__ void point_block_reduce(double *sums, const double (&acc)[NT], bool pos,
+                                                   double (&red)[kPtSums][4])
+{
+    if (!__syncthreads_or(pos)) return;
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        if (k == SKIP) continue;
+        const double s = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) red[k][w] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NT && (int)threadIdx.x != SKIP) {
+        const int k = threadIdx.x;
+        const double s = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
+        atomicAdd(sums + (size_t)k * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask), s);
+    }
+}
+
 template <bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
 {
@@ -227,42 +310,14 @@ __global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
             const float *bp = a.reg[r.l] + (size_t)r.b * 4 * HW + p;
             const float d[4] = {bp[0], bp[(size_t)HW], bp[(size_t)2 * HW], bp[(size_t)3 * HW]};
             const float4 t = reinterpret_cast<const float4 *>(a.bt[r.l])[e1];
-            const int y = p / W, x = p - y * W, s = a.lv.stride[r.l];
-            const float px = (float)(x * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+            float px, py;
+            point_centre(p, W, a.lv.stride[r.l], px, py);
             const PtElem q = point_elem(px, py, d, t);
             const float xc = a.ctr[r.l][e1];
             float xi = 0.0f;
             if constexpr (IOU) xi = a.iou[r.l][e1];
-            if (!BWD) {
-                acc[0] = (double)(-logf_(q.u) * q.c);
-                acc[1] = (double)q.c;
-                acc[2] = (double)bce_logits_(xc, q.c);
-                if constexpr (IOU) acc[3] = (double)bce_logits_(xi, q.u);
-                acc[4] = 1.0;
-            } else {
-                const float n = a.res[4], sc = a.res[5];
-                const float gs_reg = a.gin[1] / sc, gs_ctr = a.gin[2] / n;
-                g_ctr = (sigmoidf_(xc) - q.c) * gs_ctr;
-                float gu = -(q.c / q.u) * gs_reg;                    // d(-log(u) c) / du
-                if constexpr (IOU) {
-                    const float gs_iou = a.gin[3] / n;
-                    g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
-                    if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
-                }
-                // u = ov / un, un = ap + at - ov; both factors are formed as (v / un) / un, so that at
-                // ov == un (prediction == target) d/d ov is -2 d/d ap to the bit and the two halves below
-                // cancel it: the gradient at the loss's minimum is exactly 0
-                const float inv_un = 1.0f / q.un;
-                const float g_ov = gu * (((q.un + q.ov) * inv_un) * inv_un);
-                const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
-                const float g_w = g_ov * q.h, g_h = g_ov * q.w;      // w0, h0 > 0: both boxes hold the point
-                const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
-                // x1 = px - left, x2 = px + right: d/d left = -d/d x1
-                g_box[0] = g_pw + q.sx1 * g_w;
-                g_box[1] = g_ph + q.sy1 * g_h;
-                g_box[2] = g_pw + q.sx2 * g_w;
-                g_box[3] = g_ph + q.sy2 * g_h;
-            }
+            if (!BWD) point_fwd_terms<IOU>(q, xc, xi, acc);
+            else point_bwd_terms<IOU>(q, xc, xi, a.res, a.gin, a.attach, g_box, g_ctr, g_iou);
         }
         if (BWD) {
             float *go = a.g_reg[r.l] + (size_t)r.b * 4 * HW + p;
@@ -274,25 +329,8 @@ __global__ void __launch_bounds__(256) k_point_box(PtBoxArgs a)
             if constexpr (IOU) a.g_iou[r.l][e1] = g_iou;
         }
     }
-    if (!BWD) {
-        // positives are rare: most workgroups have nothing to add
-        if (!__syncthreads_or(pos)) return;
-        const int w = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < kPtSums; ++k) {
-            if (k == 3 && !IOU) continue;
-            const double s = wave_sum(acc[k]);
-            if ((threadIdx.x & 63) == 0) red[k][w] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < kPtSums && (IOU || threadIdx.x != 3)) {
-            const int k = threadIdx.x;
-            const double s = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-            atomicAdd(a.sums + (size_t)k * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask), s);
-        }
-    }
+    if (!BWD) point_block_reduce<kPtSums, IOU ? -1 : 3>(a.sums, acc, pos, red);
 }
-
 
 // ------------------------------------------------------------------ channels-last rows, fp32 / bf16
 struct PtBoxNhwcArgs {
@@ -313,37 +351,8 @@ struct PtBoxNhwcArgs {
     int32_t attach;
 };
 
-template <typename T> struct PtStore;
-template <> struct PtStore<float> {
-    static __device__ __forceinline__ void one(float *p, float v) { *p = v; }
-    static __device__ __forceinline__ void four(float *p, const float (&v)[4])
-    {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-};
-template <> struct PtStore<uint16_t> {                     // one round-to-nearest-even each
-    static __device__ __forceinline__ void one(uint16_t *p, float v) { *p = (uint16_t)f32_to_bf16(v); }
-    static __device__ __forceinline__ void four(uint16_t *p, const float (&v)[4])
-    {
-        *reinterpret_cast<uint2 *>(p) = make_uint2(f32_to_bf16(v[0]) | (f32_to_bf16(v[1]) << 16),
-                                                   f32_to_bf16(v[2]) | (f32_to_bf16(v[3]) << 16));
-    }
-};
-template <typename T> __device__ __forceinline__ void load4_f32(const T *p, float (&v)[4]);
-template <> __device__ __forceinline__ void load4_f32<float>(const float *p, float (&v)[4])
-{
-    const float4 q = *reinterpret_cast<const float4 *>(p);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-}
-template <> __device__ __forceinline__ void load4_f32<uint16_t>(const uint16_t *p, float (&v)[4])
-{
-    const uint2 q = *reinterpret_cast<const uint2 *>(p);
-    v[0] = bf16_to_f32((uint16_t)(q.x & 0xffffu)); v[1] = bf16_to_f32((uint16_t)(q.x >> 16));
-    v[2] = bf16_to_f32((uint16_t)(q.y & 0xffffu)); v[3] = bf16_to_f32((uint16_t)(q.y >> 16));
-}
-
-// k_point_box on pixel rows: the blocks, the positive test, point_elem and the fp64 sums are the NCHW
-// kernel's; every point's gradient row is written whole (maps, and the padding the host counted)
+// k_point_box on pixel rows of T, the reg row optionally raw (d = exp(scale_l x)); every point's gradient
+// row is written whole (maps, and the padding the host counted)
 template <typename T, bool BWD, bool IOU>
 __global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
 {
@@ -354,7 +363,7 @@ __global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
     if (BWD && blockIdx.x == 0 && threadIdx.x == 0) a.fgin[3 * a.lv.L] = a.gin[0];
     const bool raw = a.reg_scale != nullptr;              // uniform
     double acc[kPtSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    double acc_s = 0.0;
+    double acc_s[1] = {0.0};
     bool pos = false;
     if (p < HW) {
         const int64_t e1 = (int64_t)r.b * HW + p;
@@ -362,42 +371,21 @@ __global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
         float g_box[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g_ctr = 0.0f, g_iou = 0.0f;
         if (pos) {
             float x[4], d[4];
-            load4_f32<T>(static_cast<const T *>(a.reg[r.l]) + e1 * a.ps_reg[r.l], x);
+            Elems<T, 4>::load(static_cast<const T *>(a.reg[r.l]) + e1 * a.ps_reg[r.l], x);
             const float sc = raw ? a.reg_scale[r.l] : 1.0f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) d[k] = raw ? expf_(sc * x[k]) : x[k];
             const float4 t = reinterpret_cast<const float4 *>(a.bt[r.l])[e1];
-            const int y = p / W, xx = p - y * W, s = a.lv.stride[r.l];
-            const float px = (float)(xx * s) + (float)(s / 2), py = (float)(y * s) + (float)(s / 2);
+            float px, py;
+            point_centre(p, W, a.lv.stride[r.l], px, py);
             const PtElem q = point_elem(px, py, d, t);
             const float xc = load_f32<T>(static_cast<const T *>(a.ctr[r.l]) + e1 * a.ps_ctr[r.l]);
             float xi = 0.0f;
             if constexpr (IOU) xi = load_f32<T>(static_cast<const T *>(a.iou[r.l]) + e1 * a.ps_iou[r.l]);
             if (!BWD) {
-                acc[0] = (double)(-logf_(q.u) * q.c);
-                acc[1] = (double)q.c;
-                acc[2] = (double)bce_logits_(xc, q.c);
-                if constexpr (IOU) acc[3] = (double)bce_logits_(xi, q.u);
-                acc[4] = 1.0;
+                point_fwd_terms<IOU>(q, xc, xi, acc);
             } else {
-                const float n = a.res[4], sn = a.res[5];
-                const float gs_reg = a.gin[1] / sn, gs_ctr = a.gin[2] / n;
-                g_ctr = (sigmoidf_(xc) - q.c) * gs_ctr;
-                float gu = -(q.c / q.u) * gs_reg;                    // d(-log(u) c) / du
-                if constexpr (IOU) {
-                    const float gs_iou = a.gin[3] / n;
-                    g_iou = (sigmoidf_(xi) - q.u) * gs_iou;
-                    if (a.attach) gu += (-xi) * gs_iou;              // d BCE(xi, u) / du = -xi
-                }
-                const float inv_un = 1.0f / q.un;
-                const float g_ov = gu * (((q.un + q.ov) * inv_un) * inv_un);    // as in k_point_box
-                const float g_ap = gu * (-(q.ov * inv_un) * inv_un);
-                const float g_w = g_ov * q.h, g_h = g_ov * q.w;
-                const float g_pw = g_ap * q.ph, g_ph = g_ap * q.pw;
-                g_box[0] = g_pw + q.sx1 * g_w;
-                g_box[1] = g_ph + q.sy1 * g_h;
-                g_box[2] = g_pw + q.sx2 * g_w;
-                g_box[3] = g_ph + q.sy2 * g_h;
+                point_bwd_terms<IOU>(q, xc, xi, a.res, a.gin, a.attach, g_box, g_ctr, g_iou);
                 if (raw) {
                     // d = exp(scale x): dL/dx = (g d) scale, dL/dscale += (g d) x
                     float ts = 0.0f;
@@ -407,50 +395,28 @@ __global__ void __launch_bounds__(256) k_point_box_nhwc(PtBoxNhwcArgs a)
                         ts += gd * x[k];
                         g_box[k] = gd * sc;
                     }
-                    acc_s = (double)ts;
+                    acc_s[0] = (double)ts;
                 }
             }
         }
         if (BWD) {
             T *gr = static_cast<T *>(a.g_reg[r.l]) + e1 * a.pg_reg[r.l];
             T *gc = static_cast<T *>(a.g_ctr[r.l]) + e1 * a.pg_ctr[r.l];
-            PtStore<T>::four(gr, g_box);
-            PtStore<T>::one(gc, g_ctr);
+            Elems<T, 4>::store(gr, g_box);                           // bf16: one round-to-nearest-even each
+            store_f32<T>(gc, g_ctr);
             T *tail = gr + 4;                                        // behind d(reg), or behind d(iou)
             if constexpr (IOU) {
                 T *gi = static_cast<T *>(a.g_iou[r.l]) + e1 * a.pg_iou[r.l];
-                PtStore<T>::one(gi, g_iou);
+                store_f32<T>(gi, g_iou);
                 tail = gi + 1;
             }
             for (int k = 0; k < a.pad_cls[r.l]; ++k) gc[1 + k] = (T)0;      // +0 in both storage types
             for (int k = 0; k < a.pad_reg[r.l]; ++k) tail[k] = (T)0;
         }
     }
-    if (!BWD) {
-        if (!__syncthreads_or(pos)) return;
-        const int w = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < kPtSums; ++k) {
-            if (k == 3 && !IOU) continue;
-            const double s = wave_sum(acc[k]);
-            if ((threadIdx.x & 63) == 0) red[k][w] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < kPtSums && (IOU || threadIdx.x != 3)) {
-            const int k = threadIdx.x;
-            const double s = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-            atomicAdd(a.sums + (size_t)k * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask), s);
-        }
-    } else if (raw) {
-        // a block is one level's: its g d x sum into that level's slots (nothing without a positive)
-        if (!__syncthreads_or(pos)) return;
-        const double s = wave_sum(acc_s);
-        if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            atomicAdd(a.scale_sums + (size_t)r.l * IA_LOSS_SLOTS + (blockIdx.x & kPtSlotMask),
-                      ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]);
-    }
+    if (!BWD) point_block_reduce<kPtSums, IOU ? -1 : 3>(a.sums, acc, pos, red);
+    // a block is one level's: its g d x sum into that level's slots
+    else if (raw) point_block_reduce<1, -1>(a.scale_sums + (size_t)r.l * IA_LOSS_SLOTS, acc_s, pos, red);
 }
 
 // slots -> d scale_l (fp32); a level without positives has nothing but the memset's zeros: exactly 0
@@ -505,22 +471,67 @@ __global__ void __launch_bounds__(64) k_point_finalize(PtFinArgs a)
     }
 }
 
-struct PtWorkspace { double *sums; float *fgin, *fres; int32_t *lab32; float *w32; size_t bytes; };
+// the workspaces of the two nodes: fp64 slots [L + kPtSums] | the focal kernel's two (3L + 4) vectors, then
+// NCHW: the packed labels | their weights; channels-last: fp64 slots [L] of d scale
+struct PtWorkspace {
+    double *sums;
+    float *fgin, *fres;
+    int32_t *lab32; float *w32;           // NCHW node
+    double *scale_sums;                   // channels-last node
+    size_t bytes;
+};
+
+static Carver carve_point_head(int L, void *workspace, PtWorkspace &r)
+{
+    Carver c(workspace);
+    r.lab32 = nullptr; r.w32 = nullptr; r.scale_sums = nullptr;
+    c.take(r.sums, sizeof(double) * (L + kPtSums) * IA_LOSS_SLOTS);
+    c.take(r.fgin, sizeof(float) * 2 * (3 * L + 4));
+    r.fres = r.fgin ? r.fgin + (3 * L + 4) : nullptr;
+    return c;
+}
 
 static PtWorkspace carve_point(const HLLevels &lv, void *workspace)
 {
-    const size_t slots = align256(sizeof(double) * (lv.L + kPtSums) * IA_LOSS_SLOTS);
-    const size_t fint = align256(sizeof(float) * 2 * (3 * lv.L + 4));
-    const size_t pk = align256(packed_pad(lv) * 4);
-    char *w = static_cast<char *>(workspace);
     PtWorkspace r;
-    r.sums = reinterpret_cast<double *>(w);
-    r.fgin = reinterpret_cast<float *>(w + slots);
-    r.fres = r.fgin + (3 * lv.L + 4);
-    r.lab32 = reinterpret_cast<int32_t *>(w + slots + fint);
-    r.w32 = reinterpret_cast<float *>(w + slots + fint + pk);
-    r.bytes = slots + fint + 2 * pk;
+    Carver c = carve_point_head(lv.L, workspace, r);
+    c.take(r.lab32, packed_pad(lv) * 4);
+    c.take(r.w32, packed_pad(lv) * 4);
+    r.bytes = c.bytes;
     return r;
+}
+
+static PtWorkspace carve_point_nhwc(int L, void *workspace)
+{
+    PtWorkspace r;
+    Carver c = carve_point_head(L, workspace, r);
+    c.take(r.scale_sums, sizeof(double) * L * IA_LOSS_SLOTS);
+    r.bytes = c.bytes;
+    return r;
+}
+
+// the tail of the two forward entries: clear the slots before the first kernel, reduce them after the last
+static int clear_point_slots(double *sums, int L, hipStream_t s)
+{
+    return hip_status(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s));
+}
+
+static int launch_point_finalize(const double *sums, const ia_point_targets *t, int L, int batch, bool with_iou,
+                                 float *result, float *fgin, float *fres, hipStream_t s)
+{
+    PtFinArgs f;
+    f.sums = sums; f.counts = t->counts; f.L = L; f.B = batch; f.iou = with_iou ? 1 : 0;
+    f.res = result; f.fgin = fgin; f.fres = fres;
+    hipLaunchKernelGGL(k_point_finalize, dim3(1), dim3(64), 0, s, f);
+    return hip_status(hipGetLastError());
+}
+
+static int launch_point_box(bool bwd, bool with_iou, const PtBoxArgs &ba, hipStream_t s)
+{
+    static void (*const k[2][2])(PtBoxArgs) = {{k_point_box<false, false>, k_point_box<false, true>},
+                                               {k_point_box<true, false>, k_point_box<true, true>}};
+    hipLaunchKernelGGL(k[bwd][with_iou], dim3((unsigned)ba.lv.blk_off[ba.lv.L]), dim3(256), 0, s, ba);
+    return hip_status(hipGetLastError());
 }
 
 // what forward and backward check alike; fills the focal and box arguments except the outputs
@@ -565,24 +576,6 @@ static int point_loss_args(const ia_point_head_geom *g, const ia_point_level_ptr
 }
 
 // ------------------------------------------------------------------ channels-last rows: host
-// workspace: fp64 slots [L + kPtSums] | the focal kernel's two (3L + 4) vectors | fp64 slots [L] of d scale
-struct PtNhwcWorkspace { double *sums; float *fgin, *fres; double *scale_sums; size_t bytes; };
-
-static PtNhwcWorkspace carve_point_nhwc(int L, void *workspace)
-{
-    const size_t slots = align256(sizeof(double) * (L + kPtSums) * IA_LOSS_SLOTS);
-    const size_t fint = align256(sizeof(float) * 2 * (3 * L + 4));
-    const size_t ss = align256(sizeof(double) * L * IA_LOSS_SLOTS);
-    char *w = static_cast<char *>(workspace);
-    PtNhwcWorkspace r;
-    r.sums = reinterpret_cast<double *>(w);
-    r.fgin = reinterpret_cast<float *>(w + slots);
-    r.fres = r.fgin + (3 * L + 4);
-    r.scale_sums = reinterpret_cast<double *>(w + slots + fint);
-    r.bytes = slots + fint + ss;
-    return r;
-}
-
 static int point_levels_nhwc(const ia_point_head_geom *g, int batch, HLLevels &lv, NhwcLevels &nl)
 {
     ia_head_geom hg;
@@ -613,7 +606,7 @@ static int point_nhwc_args(const ia_point_head_geom *g, const ia_point_level_ptr
                            const ia_point_loss_cfg *cfg, const float *reg_scale, void *workspace,
                            size_t workspace_bytes, bool bwd, const ia_point_level_ptrs *grads,
                            const ia_point_pix_strides *grad_strides, int grad_rows_packed,
-                           FocalNhwcArgs &fa, PtBoxNhwcArgs &ba, PtNhwcWorkspace &ws, bool &with_iou)
+                           FocalNhwcArgs &fa, PtBoxNhwcArgs &ba, PtWorkspace &ws, bool &with_iou)
 {
     if (!p || !strides || !t || !cfg || !workspace || ((uintptr_t)workspace & 255u)) return IA_E_ARG;
     if (dtype != IA_F32 && dtype != IA_BF16) return IA_E_ARG;
@@ -756,8 +749,7 @@ int ia_point_head_loss_fwd(const ia_point_head_geom *g, const ia_point_level_ptr
     fa.tail.big_logits = cfg->exact_large_logits ? 1 : 0;
     ba.sums = ws.sums + (size_t)L * IA_LOSS_SLOTS;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(ws.sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s);
-    if (e != hipSuccess) return (int)e;
+    if ((rc = clear_point_slots(ws.sums, L, s))) return rc;
     if (!t->packed) {
         PtPackArgs pa;
         pa.lv = fa.lv;
@@ -766,14 +758,8 @@ int ia_point_head_loss_fwd(const ia_point_head_geom *g, const ia_point_level_ptr
         hipLaunchKernelGGL(k_point_pack, dim3((unsigned)((fa.lv.pack_off[L] + 255) / 256)), dim3(256), 0, s, pa);
     }
     if ((rc = launch_focal_ml_f32(fa, false, s))) return rc;
-    const unsigned grid = (unsigned)fa.lv.blk_off[L];
-    if (with_iou) hipLaunchKernelGGL((k_point_box<false, true>), dim3(grid), dim3(256), 0, s, ba);
-    else hipLaunchKernelGGL((k_point_box<false, false>), dim3(grid), dim3(256), 0, s, ba);
-    PtFinArgs f;
-    f.sums = ws.sums; f.counts = t->counts; f.L = L; f.B = batch; f.iou = with_iou ? 1 : 0;
-    f.res = result; f.fgin = ws.fgin; f.fres = ws.fres;
-    hipLaunchKernelGGL(k_point_finalize, dim3(1), dim3(64), 0, s, f);
-    return hip_status(hipGetLastError());
+    if ((rc = launch_point_box(false, with_iou, ba, s))) return rc;
+    return launch_point_finalize(ws.sums, t, L, batch, with_iou, result, ws.fgin, ws.fres, s);
 }
 
 int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptrs *p, int batch,
@@ -802,11 +788,8 @@ int ia_point_head_loss_bwd(const ia_point_head_geom *g, const ia_point_level_ptr
     fa.tail.gin = ws.fgin; fa.tail.res = ws.fres;
     ba.res = result; ba.gin = grad_result; ba.fgin = ws.fgin;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)fa.lv.blk_off[L];
     // the box kernel first: it hands the upstream gradient of loss_cls to the focal kernel
-    if (with_iou) hipLaunchKernelGGL((k_point_box<true, true>), dim3(grid), dim3(256), 0, s, ba);
-    else hipLaunchKernelGGL((k_point_box<true, false>), dim3(grid), dim3(256), 0, s, ba);
-    if ((rc = hip_status(hipGetLastError()))) return rc;
+    if ((rc = launch_point_box(true, with_iou, ba, s))) return rc;
     return launch_focal_ml_f32(fa, true, s);
 }
 
@@ -828,7 +811,7 @@ int ia_point_head_loss_fwd_nhwc(const ia_point_head_geom *g, const ia_point_leve
     if (!result) return IA_E_ARG;
     FocalNhwcArgs fa;
     PtBoxNhwcArgs ba;
-    PtNhwcWorkspace ws;
+    PtWorkspace ws;
     bool with_iou;
     int rc = point_nhwc_args(g, p, strides, dtype, batch, t, cfg, reg_scale, workspace, workspace_bytes, false,
                              nullptr, nullptr, 0, fa, ba, ws, with_iou);
@@ -838,15 +821,10 @@ int ia_point_head_loss_fwd_nhwc(const ia_point_head_geom *g, const ia_point_leve
     fa.tail.big_logits = cfg->exact_large_logits ? 1 : 0;
     ba.sums = ws.sums + (size_t)L * IA_LOSS_SLOTS;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(ws.sums, 0, sizeof(double) * (size_t)(L + kPtSums) * IA_LOSS_SLOTS, s);
-    if (e != hipSuccess) return (int)e;
+    if ((rc = clear_point_slots(ws.sums, L, s))) return rc;
     if ((rc = launch_focal_nhwc_unit(fa, dtype, false, s))) return rc;
     if ((rc = launch_point_box_nhwc(dtype, false, with_iou, ba, s))) return rc;
-    PtFinArgs f;
-    f.sums = ws.sums; f.counts = t->counts; f.L = L; f.B = batch; f.iou = with_iou ? 1 : 0;
-    f.res = result; f.fgin = ws.fgin; f.fres = ws.fres;
-    hipLaunchKernelGGL(k_point_finalize, dim3(1), dim3(64), 0, s, f);
-    return hip_status(hipGetLastError());
+    return launch_point_finalize(ws.sums, t, L, batch, with_iou, result, ws.fgin, ws.fres, s);
 }
 
 int ia_point_head_loss_bwd_nhwc(const ia_point_head_geom *g, const ia_point_level_ptrs *p,
@@ -862,7 +840,7 @@ int ia_point_head_loss_bwd_nhwc(const ia_point_head_geom *g, const ia_point_leve
     if ((reg_scale != nullptr) != (grad_scale != nullptr)) return IA_E_ARG;
     FocalNhwcArgs fa;
     PtBoxNhwcArgs ba;
-    PtNhwcWorkspace ws;
+    PtWorkspace ws;
     bool with_iou;
     int rc = point_nhwc_args(g, p, strides, dtype, batch, t, cfg, reg_scale, workspace, workspace_bytes, true,
                              grads, grad_strides, grad_rows_packed, fa, ba, ws, with_iou);

@@ -176,13 +176,6 @@ struct StemBfArgs {
     int32_t B, H, W, Ho, Wo, tiles_x, tiles_y, ntiles;
 };
 
-__device__ __forceinline__ uint32_t stem_bf16_rne(float f)
-{
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 // AL: the image rows are 4-byte aligned (W even): the patch is staged with aligned DWORD copies.  The
 // first element a tile needs, (2 c0 - 3) * 3, is odd, so the LDS row starts ONE ELEMENT EARLIER
 // (LDS[i] = row[e0 - 1 + i], e0 - 1 even) and the K grouping is shifted by one to keep the lanes'
@@ -300,8 +293,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
                     for (int nb = 0; nb < 4; ++nb) {
                         const f32x4s v = acc[mt][nb];
-                        const uint32_t lo = stem_bf16_rne(v.x) | (stem_bf16_rne(v.y) << 16);
-                        const uint32_t hi = stem_bf16_rne(v.z) | (stem_bf16_rne(v.w) << 16);
+                        const uint32_t lo = f32_to_bf16(v.x) | (f32_to_bf16(v.y) << 16);
+                        const uint32_t hi = f32_to_bf16(v.z) | (f32_to_bf16(v.w) << 16);
                         *reinterpret_cast<uint2 *>(yr + (size_t)col * 64 + 16 * nb) = make_uint2(lo, hi);
                     }
                 }

@@ -105,3 +105,22 @@ def input_grad(dz, w, stride, groups, H, W, flip=True, transpose=True, clamp=Fal
             part = torch.einsum('bgoyx,goi->bgiyx', dzg[:, :, :, sy][:, :, :, :, sx], wt)
             dx[:, :, :, dy_.view(-1, 1), dx_.view(1, -1)] += part
     return dx.reshape(B, C, H, W)
+
+
+def pack_fp32(w, scale=None):
+    """numpy transcription of the fp32 operand layout of csrc/ia_gconv.hpp (gconv_pack_elem, plain
+    pack): (C, Cg, 3, 3) fp32 weight -> (SG, 9, NB, 4, NB, 64), element [sg][t][ci][c][co][lane] =
+    W[o][in % Cg][t] * scale[o] (one fp32 product) with o = sg*16*NB + 16*co + (lane & 15),
+    in = sg*16*NB + 16*ci + 4*(lane >> 4) + c, zero across groups"""
+    import numpy as np
+    w = np.asarray(w, np.float32)
+    C, cg = w.shape[0], w.shape[1]
+    nb = 2 if cg == 32 else 1
+    sgc = 16 * nb
+    sg, t, ci, c, co, lane = np.ix_(*(np.arange(n) for n in (C // sgc, 9, nb, 4, nb, 64)))
+    o = sg * sgc + 16 * co + (lane & 15) + 0 * (t + ci + c)
+    i = sg * sgc + 16 * ci + 4 * (lane >> 4) + c + 0 * (t + co)
+    v = w.reshape(C, cg, 9)[o, i % cg, t + 0 * o]
+    if scale is not None:
+        v = v * np.asarray(scale, np.float32)[o]
+    return np.where(o // cg == i // cg, v, np.float32(0)).astype(np.float32)

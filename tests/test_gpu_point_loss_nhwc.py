@@ -404,3 +404,94 @@ def test_point_head_loss_packed(iou_branch, dtype, wc, wr):
             tol = (2.0 ** -7 if rounded else 1e-6) * float(ref.float().abs().max())
             assert float((got - ref.float()).abs().max()) <= tol
         assert abs(float(gs[2 * NL + l]) - float(r_sc[l])) <= 1e-6 * max(abs(float(r_sc[l])), 1e-30)
+
+
+# ------------------------------------------------------------------ 7. one backward body, two layouts
+TWIN_GT_SEED = 133        # chosen on the CPU: positives on three levels (134, 82, 6), none on the last two
+
+
+@functools.lru_cache(maxsize=None)
+def _twin_inputs():
+    """the head outputs of the small case on gts with positives on three levels; every third positive point
+    predicts one edge exactly on the target's (the tie shares), every ninth the whole target box (the
+    loss's minimum)"""
+    gb, gl = S.gts(TWIN_GT_SEED, 2, 120, 150, 3, 8)
+    cls, dist, ctr, iou = S.case_inputs(S.SMALL)[3]
+    lab, tgt = S.np_targets(SIZES, gb, gl)
+    dist = [np.ascontiguousarray(d).copy() for d in dist]
+    i = 0
+    for l in range(NL):
+        d = dist[l].reshape(dist[l].shape[0], 4, -1)                  # a view: (B, 4, N_l)
+        for b, n in zip(*np.nonzero(lab[l] > 0)):
+            if i % 9 == 0:
+                d[b, :, n] = tgt[l][b, n]
+            elif i % 3 == 0:
+                d[b, i % 4, n] = tgt[l][b, n, i % 4]
+            i += 1
+    pos = S.check_conditions(SIZES, gb, gl)
+    assert sum(n > 0 for n in pos) >= 3 and min(pos) == 0, pos
+    assert S.edge_ties(SIZES, lab, tgt, dist) >= 1
+    return gb, gl, (cls, dist, ctr, iou), pos
+
+
+@pytest.mark.parametrize('iou_branch', [True, False], ids=['iou', 'plain'])
+def test_backward_is_one_body_in_both_layouts(iou_branch):
+    """fp32, reg_scale NULL, no padding channels: ia_point_head_loss_bwd on NCHW maps and
+    ia_point_head_loss_bwd_nhwc on the same values as pixel rows, with the same hand-filled result and
+    upstream vectors, give d reg, d ctr and d iou BITWISE equal element for element -- blocks with a
+    tail (320 points), levels of a single block, levels without a positive, ties and the minimum."""
+    import ctypes as C
+    from iouaware import _lib
+    gb, gl, vals, pos = _twin_inputs()
+    n = 4 if iou_branch else 3
+    L, B, geom = _lib.lib(), len(gb), _geom()
+    lab, tgt, counts = _targets(gb, gl)
+    ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    pt = _lib.PointTargets()
+    for l in range(NL):
+        pt.labels[l], pt.bbox_targets[l] = lab[l].data_ptr(), tgt[l].data_ptr()
+    pt.counts = counts.data_ptr()
+    cfg = _lib.PointLossCfg(2.0, 0.25, 1, 0)
+    # not the forwards' own: their fp64 atomics may round the normalisers differently
+    res = torch.tensor([0.71, 0.43, 0.62, 0.37, 222.0, 97.25], device=DEV)
+    gin = torch.tensor([1.0, 0.75, 1.25, 0.5], device=DEV)
+    scratch = torch.empty(6, device=DEV)
+
+    def level_ptrs(maps):
+        p = _lib.PointLevelPtrs()
+        for l in range(NL):
+            p.cls[l], p.reg[l], p.ctr[l] = (m[l].data_ptr() for m in maps[:3])
+            p.iou[l] = maps[3][l].data_ptr() if iou_branch else None
+        return p
+
+    # NCHW maps; the forward leaves the packed labels and the focal kernel's vectors in the workspace
+    planes = [[torch.from_numpy(np.ascontiguousarray(x)).to(DEV) for x in m] for m in vals[:n]]
+    g_planes = [[torch.full_like(t, float('nan')) for t in m] for m in planes]
+    nb = L.ia_point_head_loss_workspace_bytes(geom.ref(), B)
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    p, gp = level_ptrs(planes), level_ptrs(g_planes)
+    assert L.ia_point_head_loss_fwd(geom.ref(), C.byref(p), B, C.byref(pt), C.byref(cfg), ptr(ws), nb,
+                                    ptr(scratch), None) == 0
+    assert L.ia_point_head_loss_bwd(geom.ref(), C.byref(p), B, C.byref(pt), C.byref(cfg), ptr(ws), ptr(res),
+                                    ptr(gin), C.byref(gp), None) == 0
+    # the same values as rows: every map its own rows, pixel stride = its channel count
+    rows = [[t.permute(0, 2, 3, 1).contiguous() for t in m] for m in planes]
+    g_rows = [[torch.full_like(t, float('nan')) for t in m] for m in rows]
+    st = _lib.PointPixStrides()
+    for l in range(NL):
+        st.cls[l], st.reg[l], st.ctr[l], st.iou[l] = S.C, 4, 1, 1
+    nbr = L.ia_point_head_loss_nhwc_workspace_bytes(geom.ref(), B)
+    wsr = torch.empty(nbr, dtype=torch.uint8, device=DEV)
+    pr, gpr = level_ptrs(rows), level_ptrs(g_rows)
+    assert L.ia_point_head_loss_fwd_nhwc(geom.ref(), C.byref(pr), C.byref(st), _lib.IA_F32, B, C.byref(pt),
+                                         C.byref(cfg), None, ptr(wsr), nbr, ptr(scratch), None) == 0
+    assert L.ia_point_head_loss_bwd_nhwc(geom.ref(), C.byref(pr), C.byref(st), _lib.IA_F32, B, C.byref(pt),
+                                         C.byref(cfg), None, ptr(wsr), nbr, ptr(res), ptr(gin), C.byref(gpr),
+                                         C.byref(st), 0, None, None) == 0
+    torch.cuda.synchronize()
+    for k in range(1, n):
+        for l in range(NL):
+            a, b = g_planes[k][l], g_rows[k][l].permute(0, 3, 1, 2).contiguous()
+            assert bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all()), (KINDS[k], l)
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (KINDS[k], l)
+            assert bool((a != 0).any()) == (pos[l] > 0), (KINDS[k], l)
