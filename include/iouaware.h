@@ -867,7 +867,9 @@ int ia_channel_affine_act(void *x, int dtype, const float *scale, const float *s
                           const void *residual, const float *res_scale, const float *res_shift,
                           int relu, int N, int C, int64_t HW, void *stream);
 /* the same on a channels-last tensor: x is (N, H, W, C) in memory (NHW = N*H*W);
- * C must be a multiple of 4 (fp32) / 8 (bf16).                                 */
+ * C must be a multiple of 4 (fp32) / 8 (bf16); x, residual and every per-channel
+ * vector given must be 16-byte aligned (IA_E_ARG otherwise).  With ReLU a NaN
+ * stays a NaN, as in torch.relu.                                               */
 int ia_channel_affine_act_nhwc(void *x, int dtype, const float *scale, const float *shift,
                                const void *residual, const float *res_scale,
                                const float *res_shift, int relu, int64_t NHW, int C, void *stream);
@@ -882,7 +884,9 @@ int ia_nhwc_to_nchw(const void *src, void *dst, int dtype, int N, int C, int64_t
 int ia_affine_relu_maxpool_nhwc(const float *x, const float *scale, const float *shift, int B, int H,
                                 int W, int C, float *out, void *stream);
 /* the same for dtype IA_F32 / IA_BF16 (C % 4 / C % 8 == 0): fp32 arithmetic, a bf16 result is
- * rounded once -- equal to eager's affine -> ReLU -> max-pool on bf16 values                      */
+ * rounded once -- equal to eager's affine -> ReLU -> max-pool on bf16 values.  IA_F32 propagates a
+ * NaN as eager does (an output is NaN exactly when a tap of its window is); IA_BF16 drops it (the
+ * maximum of the other taps, or 0): a known difference, DESIGN 3.26.                              */
 int ia_affine_relu_maxpool_nhwc_dt(const void *x, int dtype, const float *scale, const float *shift,
                                    int B, int H, int W, int C, void *out, void *stream);
 

@@ -249,6 +249,9 @@ extern "C" int ia_channel_affine_act_nhwc(void *x, int dtype, const float *scale
     const int n = dtype == IA_F32 ? 4 : (dtype == IA_BF16 ? 8 : 0);
     if (n == 0 || C % n != 0 || ((uintptr_t)x & 15u) || (residual && ((uintptr_t)residual & 15u)))
         return IA_E_ARG;
+    // the per-channel vectors are read 16 bytes at a time (a NULL one is absent)
+    if ((((uintptr_t)scale | (uintptr_t)shift | (uintptr_t)res_scale | (uintptr_t)res_shift) & 15u))
+        return IA_E_ARG;
     ia::AffineArgs a;
     a.x = x; a.res = residual; a.scale = scale; a.shift = shift; a.rscale = res_scale;
     a.rshift = res_shift; a.HW = 0; a.C = C; a.relu = relu;
@@ -323,11 +326,19 @@ struct PoolArgs {
 
 // one thread: 16 bytes of channels (4 fp32 / 8 bf16) of one output pixel; the arithmetic is fp32,
 // a bf16 output is rounded once at the end (rounding and ReLU are monotonic: the result equals
-// affine -> round -> ReLU -> max-pool on bf16 values, the eager sequence)
+// affine -> round -> ReLU -> max-pool on bf16 values, the eager sequence).
+// NaN.  fp32 propagates it as the module route does (torch's max_pool2d and relu both keep it): an
+// output is NaN exactly when a tap of its window is, so a poisoned conv1 output does not come out of
+// the stem as clean zeros.  bf16 still DROPS it (a NaN tap never wins the maximum, a NaN maximum
+// becomes 0): the bf16 kernel is bound by its instruction count, and the two extra compares per tap
+// cost 6.6 % of its time at the benchmark's stem shape (78.3 against 73.5 us), while in
+// fp32 they are free.  A known difference from eager, recorded as expected failures in
+// tests/test_gpu_elementwise_edges.py.
 template <typename T>
 __global__ void __launch_bounds__(256) k_affine_relu_maxpool(PoolArgs a)
 {
     constexpr int N = Pack<T>::N;
+    constexpr bool kKeepNaN = sizeof(T) == 4;
     using V = typename Pack<T>::V;
     const int cvn = a.C / N;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -356,7 +367,8 @@ __global__ void __launch_bounds__(256) k_affine_relu_maxpool(PoolArgs a)
         for (int dx = 0; dx < 3; ++dx) {
             const int xx = 2 * xo - 1 + dx;
             const int xc = (xx < 0) ? 0 : ((xx >= a.W) ? a.W - 1 : xx);
-            // clamped address: the duplicate of an in-range tap never changes a maximum
+            // clamped address: the clamped pixel lies inside the window, and the duplicate of an
+            // in-range tap never changes a maximum (nor brings a NaN from outside the window)
             taps[dy * 3 + dx] = *reinterpret_cast<const V *>(x + (((size_t)b * a.H + yc) * a.W + xc) * a.C + c);
         }
     }
@@ -369,11 +381,15 @@ __global__ void __launch_bounds__(256) k_affine_relu_maxpool(PoolArgs a)
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             const float w = v[j] * s[j] + t[j];
-            m[j] = (m[j] < w) ? w : m[j];
+            if (kKeepNaN) m[j] = (m[j] < w || w != w) ? w : m[j];      // a NaN tap takes the maximum and keeps it
+            else m[j] = (m[j] < w) ? w : m[j];
         }
     }
 #pragma unroll
-    for (int j = 0; j < N; ++j) m[j] = (m[j] > 0.f) ? m[j] : 0.f;
+    for (int j = 0; j < N; ++j) {
+        if (kKeepNaN) m[j] = (m[j] <= 0.f) ? 0.f : m[j];               // ReLU; a NaN stays a NaN
+        else m[j] = (m[j] > 0.f) ? m[j] : 0.f;
+    }
     Pack<T>::store(static_cast<T *>(a.out) + (((size_t)b * a.Ho + yo) * a.Wo + xo) * a.C + c, m);
 }
 

@@ -638,12 +638,38 @@ def nms_indices(dets, iou_thr):
     return keep[:m].to(torch.long)
 
 
+def _channel_vector(v, name, x, aligned):
+    """a per-channel operand of channel_affine_act_ as the kernels read it: a contiguous fp32 vector
+    of x.shape[1] elements on x's device (`aligned`: at a 16-byte address), or None"""
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+        raise TypeError('%s must be a float32 tensor, got %s'
+                        % (name, v.dtype if isinstance(v, torch.Tensor) else type(v).__name__))
+    if v.device != x.device:
+        raise ValueError('%s is on %s, x on %s' % (name, v.device, x.device))
+    if v.dim() != 1 or v.shape[0] != x.shape[1]:
+        raise ValueError('%s must be a vector of %d elements, got shape %s' % (name, x.shape[1], tuple(v.shape)))
+    if not v.is_contiguous():
+        v = v.contiguous()
+    if aligned and v.data_ptr() & 15:
+        v = v.clone()                                   # a slice at an odd offset: fresh (aligned) storage
+    return v
+
+
 def channel_affine_act_(x, scale=None, shift=None, residual=None, res_scale=None, res_shift=None,
                         relu=False):
-    """In place on a contiguous NCHW tensor: x = act(x*scale[c] + shift[c] [+ residual affine])."""
+    """In place on a contiguous NCHW or channels-last tensor:
+    x = act(x*scale[c] + shift[c] [+ residual*res_scale[c] + res_shift[c]]); scale / shift / res_scale /
+    res_shift: fp32 vectors of C elements on x's device, or None (1 / 0).  With relu a NaN stays a NaN."""
     _require_gpu(x, 'x')
     N, Cn = x.shape[0], x.shape[1]
-    if not x.is_contiguous():
+    nhwc = not x.is_contiguous()
+    scale = _channel_vector(scale, 'scale', x, nhwc)
+    shift = _channel_vector(shift, 'shift', x, nhwc)
+    res_scale = _channel_vector(res_scale, 'res_scale', x, nhwc)
+    res_shift = _channel_vector(res_shift, 'res_shift', x, nhwc)
+    if nhwc:
         if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):
             if residual is not None:
                 if residual.shape != x.shape or residual.dtype != x.dtype:
